@@ -105,7 +105,14 @@ def parse_args(argv=None):
     ap.add_argument('--inference-frames', type=int, default=1024, help='timed frames of each inference pass (after 64 warm-up frames of the same loader)')
     ap.add_argument('--no-planes3', action='store_true',
                     help='skip the `planes3` legs (main config and second_trunk re-timed on three bf16 planes / six products)')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps of the headline workload, write what its last step returned (total loss, every '
+                         'logged loss term) and left in the model (parameters, buffers, gradients) as DIR/<name>.npy, float32 / '
+                         'float64, at most 64 MB in all (see dump_outputs)')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def visible_gpus():
@@ -160,7 +167,7 @@ def run_workload(config, batch, steps, warmup, args, rank, world, device, sites=
     """Build the model of `config`, step it `warmup` + `steps` times on two resident batches.
     `sites`: (site, cap, key) timing sessions armed for the timed steps (rank 0). `planes`: arithmetic of the matrix
     kernels the Runner selects (config key `gga_dense_planes`; None = the Runner's default, two fp16 planes under its guard).
-    -> dict(dt, loss, timings {site: [ms]}, model, batches, cfg)."""
+    -> dict(dt, loss, timings {site: [ms]}, model, batches, cfg, runner, out: what the last timed step returned)."""
     import torch
     import torch.distributed as dist
     from gga_amd import Config, build_model, synthetic, _lib
@@ -226,7 +233,7 @@ def run_workload(config, batch, steps, warmup, args, rank, world, device, sites=
     dt = float(t.item())
     loss = float(out['loss'].detach()) if torch.is_tensor(out['loss']) else float(out['loss'])
     assert loss == loss, f'loss is NaN ({config})'
-    return dict(dt=dt, loss=loss, timings=timings, model=model, batches=batches, cfg=cfg, runner=runner)
+    return dict(dt=dt, loss=loss, timings=timings, model=model, batches=batches, cfg=cfg, runner=runner, out=out)
 
 
 def run_mono_workload(batch, steps, warmup, args, rank, world, device):
@@ -896,6 +903,46 @@ def cpu_baseline(cfg, frames=16, parity=None):
     return out, parity_out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(run, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write what the last timed step of `run` (a run_workload result) handed its caller, one .npy per array: `loss` and
+    `log_vars.<name>` from the step's return value; `state.<name>` (parameters and buffers after the optimizer step) and
+    `grad.<name>` (the gradients that step applied) from the model. Logical (contiguous) layout whatever the memory format;
+    floating tensors as float32, integer ones (BatchNorm counters) as float64. When the whole exceeds `limit` bytes every
+    array of more than 4096 elements is cut down to a fixed sample of its flattened elements: indices drawn with a seed
+    derived from the array's name, sorted, the same in every run. -> {name: number of elements written}."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {'loss': run['out']['loss']}
+    arrays.update(('log_vars.' + k, v) for k, v in run['out']['log_vars'].items())
+    model = run['model']
+    arrays.update(('state.' + k, v) for k, v in model.state_dict().items())
+    arrays.update(('grad.' + k, p.grad) for k, p in model.named_parameters() if p.grad is not None)
+    host = {}
+    for name, v in arrays.items():
+        v = torch.as_tensor(v).detach()
+        v = v.to(torch.float32) if v.is_floating_point() else v.to(torch.float64)
+        host[name] = v.contiguous().cpu().numpy()
+    header = 128                                            # bytes of an .npy header (format 1.0, small shapes)
+    total = sum(a.nbytes + header for a in host.values())
+    if total > limit:
+        big = {k: a for k, a in host.items() if a.size > 4096}
+        fixed = total - sum(a.nbytes for a in big.values())
+        keep = (limit - fixed) / sum(a.nbytes for a in big.values())
+        assert keep > 0, f'--dump-outputs: {len(host)} arrays do not fit in {limit} bytes'
+        for k, a in big.items():
+            n = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, n, replace=False))
+            host[k] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {k: int(a.size) for k, a in host.items()}
+
+
 def main():
     if os.environ.get('GGA_BENCH_HANG_DUMP') and 'RANK' in os.environ:       # debugging aid (ranks of an N-rank run): every thread's Python stack to stderr after N seconds, then exit
         import faulthandler
@@ -944,6 +991,11 @@ def main():
         sites = [(_lib.TIME_SCATTER_FWD, args.steps, 0),
                  (_lib.TIME_DENSE_CONV, 36 * args.steps, _lib.timing_conv_key(128, 128, (fh // 2) * (fw // 2)))]
     main_run = run_workload(args.config, args.batch, args.steps, args.warmup, args, rank, world, device, sites)
+    if rank == 0 and args.dump_outputs:
+        # before anything else runs on the model (bench_size_gpu_losses' forward passes move the BatchNorm statistics)
+        written = dump_outputs(main_run, args.dump_outputs)
+        print(f'--dump-outputs: {len(written)} arrays ({sum(written.values())} elements) of the last timed step in '
+              f'{args.dump_outputs}', file=sys.stderr)
     dt = main_run['dt']
     ms_per_step = dt / args.steps * 1e3
 

@@ -2,6 +2,7 @@
 own ``KittiDataset_GGA_train`` / ``_load_GGA_labels`` / ``create_groundtruth_database`` on three frames
 (tests/golden/gt_database.npz + the info fixture the reference's converter produced,
 tools_dev/make_golden.py::golden_gt_database)."""
+import json
 import os
 import pickle
 
@@ -167,11 +168,11 @@ def test_match_dataset_converts_detections_like_the_reference():
     cfg = Config.fromfile(os.path.join(REPO, 'configs', 'gga', 'gga_kitti_matching_config.py'))
     assert cfg.data['test']['type'] == 'KittiDataset_GGA_match' and DATASETS.get('KittiDataset_GGA_match') is KittiDataset_GGA_match
     assert cfg.model['type'] == 'GGA' and cfg.optimizer['type'] == 'AdamW'            # everything else is gga_kitti_config.py
-    ref_cfg = '/root/reference/configs/gga/gga_kitti_matching_config.py'
-    if os.path.exists(ref_cfg):
-        r = Config.fromfile(ref_cfg)
-        for k in ('type', 'ann_file', 'split', 'pts_prefix', 'test_mode', 'box_type_3d'):
-            assert cfg.data['test'][k] == r.data['test'][k], k
+    # the reference's file as its _base_ chain resolves (tests/golden/reference_configs.json, make_golden.py::golden_configs)
+    with open(os.path.join(GOLDEN, 'reference_configs.json')) as f:
+        r = Config(json.load(f)['configs/gga/gga_kitti_matching_config.py'])
+    for k in ('type', 'ann_file', 'split', 'pts_prefix', 'test_mode', 'box_type_3d'):
+        assert cfg.data['test'][k] == r.data['test'][k], k
     infos, outputs = make_match_case()
     ds = KittiDataset_GGA_match.__new__(KittiDataset_GGA_match)
     ds.data_infos, ds.pcd_limit_range, ds.CLASSES = infos, [0, -40, -3, 70.4, 40, 0.0], ('Pedestrian', 'Cyclist', 'Car')

@@ -3,6 +3,7 @@ oracle/mink_ref.py (parity unpinned: ME is un-vendored), the head's target assig
 vectors from a run of the reference's FCAF3DHead (tests/golden/fcaf3d_head.npz, tools_dev/make_golden.py::golden_fcaf3d),
 the merged config against the reference's, and the whole detector stepping on synthetic SUN RGB-D-shaped scenes."""
 import copy
+import json
 import os
 import sys
 
@@ -159,15 +160,15 @@ def test_rotated_iou_3d_known_answers():
 
 def test_config_equals_the_reference_and_builds():
     mine = Config.fromfile(CFG)
-    ref_path = '/root/reference/configs/fcaf3d/fcaf3d_8x2_sunrgbd-3d-10class.py'
-    if os.path.exists(ref_path):
-        ref = Config.fromfile(ref_path)
-        plain = lambda v: {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else \
-            [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
-        for key in ('model', 'optimizer', 'optimizer_config', 'lr_config', 'runner', 'checkpoint_config', 'custom_hooks'):
-            assert plain(mine[key]) == plain(ref[key]), key
-        assert mine.data['samples_per_gpu'] == ref.data['samples_per_gpu'] == 8
-        assert plain(mine.train_pipeline) == plain(ref.train_pipeline)
+    # the reference's file as its _base_ chain resolves (tests/golden/reference_configs.json, make_golden.py::golden_configs)
+    with open(os.path.join(GOLDEN, 'reference_configs.json')) as f:
+        ref = Config(json.load(f)['configs/fcaf3d/fcaf3d_8x2_sunrgbd-3d-10class.py'])
+    plain = lambda v: {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else \
+        [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
+    for key in ('model', 'optimizer', 'optimizer_config', 'lr_config', 'runner', 'checkpoint_config', 'custom_hooks'):
+        assert plain(mine[key]) == plain(ref[key]), key
+    assert mine.data['samples_per_gpu'] == ref.data['samples_per_gpu'] == 8
+    assert plain(mine.train_pipeline) == plain(ref.train_pipeline)
     model = build_model(mine.model)
     assert isinstance(model, MF.MinkSingleStage3DDetector) and isinstance(model.backbone, MF.MinkResNet)
     names = dict(model.named_parameters())

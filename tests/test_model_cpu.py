@@ -1,5 +1,6 @@
 """Host-side logic of the drop-in boundary, on CPU: registry / config surface, module and
 state_dict naming, target packing against the oracle + golden vectors, schedules."""
+import json
 import os
 
 import numpy as np
@@ -7,7 +8,7 @@ import pytest
 import torch
 
 import gga_amd
-from conftest import REPO, TRAIN_CFG, load_head_case
+from conftest import GOLDEN, REPO, TRAIN_CFG, load_head_case
 from gga_amd import Config, build_model, synthetic
 from gga_amd.registry import MODELS, Registry, build_from_cfg
 from gga_amd.train import CyclicSchedule
@@ -67,9 +68,15 @@ def test_pp_model_structure(pp_model):
     assert pp_model.pts_voxel_layer.max_voxels == (16000, 40000)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference tree only exists in the build container')
+def _reference_config(rel):
+    """The reference's config file `rel` as its _base_ chain resolves: the sections the tests compare, stored in
+    tests/golden/reference_configs.json (tools_dev/make_golden.py::golden_configs)."""
+    with open(os.path.join(GOLDEN, 'reference_configs.json')) as f:
+        return Config(json.load(f)[rel])
+
+
 def test_reference_config_model_section_loads_unchanged():
-    cfg = Config.fromfile('/root/reference/configs/gga/gga_kitti_config.py')
+    cfg = _reference_config('configs/gga/gga_kitti_config.py')
     mine = Config.fromfile(os.path.join(REPO, 'configs', 'gga', 'gga_kitti_config.py'))
     def norm(x):
         if isinstance(x, dict):
@@ -206,17 +213,15 @@ def test_pgd_config_equals_reference_and_builds():
     """configs/gga/gga_pdg.py (the `_base_` chain merged by hand) resolves to the same model / optimizer /
     schedule sections as the reference's file, and builds through the registries: FCOSMono3D = ResNet-101
     (caffe style) + FPN + PGDHead with DCNv2 on the last tower convolutions."""
-    ref_path = '/root/reference/configs/gga/gga_pdg.py'
     mine = Config.fromfile(os.path.join(REPO, 'configs', 'gga', 'gga_pdg.py'))
-    if os.path.exists(ref_path):
-        ref = Config.fromfile(ref_path)
-        plain = lambda v: {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else \
-            [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
-        for key in ('model', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs', 'runner', 'evaluation',
-                    'checkpoint_config'):
-            assert plain(mine[key]) == plain(ref[key]), key
-        assert mine.data['samples_per_gpu'] == ref.data['samples_per_gpu'] == 12
-        assert plain(mine.data['train']['ann_file']) == plain(ref.data['train']['ann_file'])
+    ref = _reference_config('configs/gga/gga_pdg.py')
+    plain = lambda v: {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else \
+        [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
+    for key in ('model', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs', 'runner', 'evaluation',
+                'checkpoint_config'):
+        assert plain(mine[key]) == plain(ref[key]), key
+    assert mine.data['samples_per_gpu'] == ref.data['samples_per_gpu'] == 12
+    assert plain(mine.data['train']['ann_file']) == plain(ref.data['train']['ann_file'])
     model = build_model(mine.model)
     from gga_amd.dcn import ModulatedDeformConv2dPack
     from gga_amd.mono3d_detectors import FCOSMono3D

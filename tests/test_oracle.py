@@ -238,7 +238,7 @@ def test_sparse_pair_list_restatement_equals_dense_restatement(cfg):
 
 
 def test_circle_nms_reference_known_answer():
-    # /root/reference/tests/test_utils/test_nms.py:63-79
+    # reference tests/test_utils/test_nms.py:63-79
     boxes = np.array([[-11.1100, 2.1300, 0.8823], [-11.2810, 2.2422, 0.8914], [-10.3966, -0.3198, 0.8643],
                       [-10.2906, -13.3159, 0.8401], [5.6518, 9.9791, 0.8271], [-11.2652, 13.3637, 0.8267],
                       [4.7768, -13.0409, 0.7810], [5.6621, 9.0422, 0.7753], [-10.5561, 18.9627, 0.7518],

@@ -1334,6 +1334,42 @@ def golden_match(ref):
     np.savez_compressed(os.path.join(OUT, 'match_dataset.npz'), **out)
 
 
+# the reference's config files the config tests compare this repository's against, and the resolved sections they read
+REFERENCE_CONFIG_SECTIONS = {
+    'configs/gga/gga_kitti_config.py': ('model', 'optimizer', 'optimizer_config', 'lr_config', 'momentum_config', 'runner'),
+    'configs/gga/gga_pdg.py': ('model', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs', 'runner', 'evaluation',
+                               'checkpoint_config', 'data'),
+    'configs/fcaf3d/fcaf3d_8x2_sunrgbd-3d-10class.py': ('model', 'optimizer', 'optimizer_config', 'lr_config', 'runner',
+                                                        'checkpoint_config', 'custom_hooks', 'data', 'train_pipeline'),
+    'configs/gga/gga_kitti_matching_config.py': ('data',),
+}
+
+
+def plain_config(v):
+    """A config value as JSON holds it: dicts and lists, tuples as lists."""
+    if isinstance(v, dict):
+        return {k: plain_config(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [plain_config(x) for x in v]
+    return v
+
+
+def golden_configs(ref):
+    """The reference's config files resolved (``_base_`` chains merged) by this repository's Config loader: the sections
+    tests/test_model_cpu.py, test_fcaf3d.py and test_datasets.py compare the configs under configs/ against."""
+    import json
+    from gga_amd import Config
+    out = {}
+    for rel, keys in REFERENCE_CONFIG_SECTIONS.items():
+        cfg = Config.fromfile(os.path.join(REF, rel))
+        out[rel] = {k: plain_config(cfg[k]) for k in keys}
+    assert json.loads(json.dumps(out)) == out, 'a config section does not survive JSON'
+    with open(os.path.join(OUT, 'reference_configs.json'), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('  reference configs:', ', '.join(f'{rel} ({len(keys)} sections)' for rel, keys in REFERENCE_CONFIG_SECTIONS.items()))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -1354,6 +1390,7 @@ def main():
     golden_rga(ref)
     golden_gt_database(ref)
     golden_pgd(ref)
+    golden_configs(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
