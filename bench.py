@@ -21,11 +21,15 @@ functional check, reported as such in ``config.backend``).
 Rank 0 prints ONE JSON line; ``roofline`` is the pillar scatter (BASELINE's HBM metric),
 ``mfma_roofline`` the 128 -> 128 dense 3x3 convolutions of SECOND's second stage (the dominant instantiation of the dense
 kernel; its share of the step is in the object), both timed with
-HIP events inside the timed steps; ``second_trunk`` is the reference's shipped model
-(configs/gga/gga_kitti_config.py: sparse-conv trunk, BASELINE config #3's per-GPU workload, bs 8)
-and ``pgd_trunk`` the camera-only retraining model (configs/gga/gga_pdg.py, BASELINE config #5, bs 12)
-stepped in the same run; ``cpu_baseline`` is the oracle's CPU restatement of the same step on a
-bounded sample plus its pieces (N=1 only).
+HIP events inside the timed steps.
+
+A plain run stops there: set-up, warm-up, the timed steps, ``--dump-outputs`` and the headline line. ``--full`` adds
+everything that takes runs of its own: ``second_trunk`` is the reference's shipped model
+(configs/gga/gga_kitti_config.py: sparse-conv trunk, BASELINE config #3's per-GPU workload, bs 8, with a ``roofline``
+from extra steps), ``pgd_trunk`` the camera-only retraining model (configs/gga/gga_pdg.py, BASELINE config #5, bs 12),
+then ``fcaf3d_trunk``, ``loader_fed``, ``inference`` and ``planes3``; ``cpu_baseline`` is the oracle's CPU restatement
+of the same step on a bounded sample plus its pieces, ``parity_at_bench_size`` its comparison with the timed weights
+(N=1 only). The ``--no-*`` switches drop single legs of a ``--full`` run.
 """
 import argparse
 import gc
@@ -87,6 +91,10 @@ def parse_args(argv=None):
     ap.add_argument('--head-init-scale', type=float, default=0.05,
                     help='damp the random init of the regression heads\' output convs (see damp_head_init)')
     ap.add_argument('--miopen-find', action='store_true', help='torch.backends.cudnn.benchmark=True (MIOpen find mode)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every leg that takes runs of its own (second_trunk with its roofline, '
+                         'pgd_trunk, fcaf3d_trunk, loader_fed, inference, planes3, cpu_baseline, parity_at_bench_size); '
+                         'off: the headline only. The --no-* switches below drop single legs of a --full run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--device-warmup-seconds', type=float, default=2.0,
                     help='keep the device busy with generic matrix products for this long before anything is built or timed '
@@ -1029,15 +1037,16 @@ def main():
         if main_run['runner'].planes != 2:
             res['dtype'] = DTYPE_PLANES3
         res['range_guard'] = main_run['runner'].range_reports
+    # everything below takes runs of its own and belongs to --full; a plain run prints the line above
     cfg_main = main_run['cfg']
     parity_pack = None
-    if rank == 0 and world == 1 and is_pp and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and is_pp and not args.no_cpu_baseline:
         parity_pack = bench_size_gpu_losses(main_run)
     del main_run
     gc.collect()
     torch.cuda.empty_cache()
 
-    if is_pp and not args.no_second_trunk:
+    if args.full and is_pp and not args.no_second_trunk:
         # the reference's shipped model section (sparse-conv trunk), same run, same launch
         s_sites = [(_lib.TIME_SPARSE_CONV, 64 * args.steps, 0), (_lib.TIME_SPARSE_WGRAD, 32 * args.steps, 0)] if rank == 0 else []
         # (Rounds 3-4 warmed this leg up for 20 steps to step over a "first-process transient": its first 15-25 steps ran 53-70 ms
@@ -1074,7 +1083,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    if is_pp and not args.no_pgd:
+    if args.full and is_pp and not args.no_pgd:
         lw = args.warmup
         pg = run_mono_workload(args.pgd_batch, args.steps, lw, args, rank, world, device)
         if rank == 0:
@@ -1092,7 +1101,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    if is_pp and not args.no_fcaf3d:
+    if args.full and is_pp and not args.no_fcaf3d:
         lw = args.warmup
         fc = run_indoor_workload(args.fcaf3d_batch, args.steps, lw, args, rank, world, device)
         if rank == 0:
@@ -1109,10 +1118,10 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    if is_pp and world == 1 and not args.no_loader_fed:
+    if args.full and is_pp and world == 1 and not args.no_loader_fed:
         res['loader_fed'] = run_loader_fed(args, device, res['value'])
 
-    if is_pp and world == 1 and not args.no_inference:
+    if args.full and is_pp and world == 1 and not args.no_inference:
         from gga_amd import synthetic as _syn
         res['inference'] = run_inference(args, device, args.config, _syn.RANGE_PP, frames=args.inference_frames)
         res['inference']['vs_train_step_frames_per_s'] = round(res['inference']['samples_per_gpu_16']['value'] / res['value'], 2)
@@ -1121,7 +1130,7 @@ def main():
             res['inference']['second_trunk']['vs_train_step_frames_per_s'] = round(
                 res['inference']['second_trunk']['samples_per_gpu_16']['value'] / res['second_trunk']['value'], 2)
 
-    if is_pp and not args.no_planes3:
+    if args.full and is_pp and not args.no_planes3:
         # the same steps on the library's default arithmetic (three bf16 planes / six products: fp32 semantics per element)
         s3, w3 = args.steps, args.warmup          # the same protocol as the headline
         p3 = run_workload(args.config, args.batch, s3, w3, args, rank, world, device, planes=3)
@@ -1144,7 +1153,7 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'], res['parity_at_bench_size'] = cpu_baseline(cfg_main, parity=parity_pack)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -64,3 +64,9 @@ def test_steps_sets_the_timed_steps_and_must_be_positive():
     assert bench.parse_args([]).dump_outputs is None
     with pytest.raises(SystemExit):
         bench.parse_args(['--steps', '0'])
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1']).full is False
+    args = bench.parse_args(['--full', '--no-pgd'])
+    assert args.full and args.no_pgd and not args.no_second_trunk

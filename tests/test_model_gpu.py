@@ -612,7 +612,7 @@ def test_bench_gpus2_plain_command_starts_its_own_ranks():
     ranks share the device over gloo; the real detector runs under DistributedDataParallel with the
     custom autograd Functions inside DDP's reducer hooks and host-side label inputs. Both configs:
     the PointPillars trunk as the main line, the shipped sparse trunk as `second_trunk`."""
-    res = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--second-batch', '2', '--pgd-batch', '1',
+    res = _run_bench(['--gpus', '2', '--full', '--steps', '2', '--warmup', '1', '--batch', '2', '--second-batch', '2', '--pgd-batch', '1',
                       '--fcaf3d-batch', '1', '--no-roofline', '--no-planes3'])
     assert res['n_gpus'] == 2 and 'loader_fed' not in res and res['value'] > 0 and res['config']['global_batch'] == 4
     assert res['config']['parallelism'] == 'dp2'
@@ -629,7 +629,7 @@ def test_two_rank_rccl_both_configs():
     """Two ranks on two GPUs, backend nccl (= RCCL): gradient all-reduce over xGMI for the
     PointPillars config and for configs/gga/gga_kitti_config.py (BASELINE config #3's workload)."""
     env = dict(os.environ, GGA_DIST_BACKEND='nccl')
-    res = _run_bench(['--gpus', '2', '--steps', '3', '--warmup', '2', '--batch', '4', '--second-batch', '4', '--pgd-batch', '2',
+    res = _run_bench(['--gpus', '2', '--full', '--steps', '3', '--warmup', '2', '--batch', '4', '--second-batch', '4', '--pgd-batch', '2',
                       '--fcaf3d-batch', '2', '--no-roofline', '--no-planes3'], env=env)
     assert res['n_gpus'] == 2 and res['config']['backend'].startswith('nccl')
     assert res['config']['global_batch'] == 8 and res['second_trunk']['global_batch'] == 8
@@ -657,8 +657,8 @@ def test_ddp_over_rccl_one_rank_is_bit_identical():
 
 
 def test_bench_line_contract_single_gpu():
-    """The default single-GPU line carries every field the driver and the judge read."""
-    res = _run_bench(['--steps', '2', '--warmup', '1', '--batch', '2', '--second-batch', '2', '--pgd-batch', '1', '--fcaf3d-batch', '1',
+    """The single-GPU `--full` line carries every field of the headline and of every leg."""
+    res = _run_bench(['--full', '--steps', '2', '--warmup', '1', '--batch', '2', '--second-batch', '2', '--pgd-batch', '1', '--fcaf3d-batch', '1',
                       '--no-cpu-baseline', '--loader-frames', '100', '--loader-workers', '2', '--inference-frames', '32'])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'arith', 'data', 'config', 'roofline', 'mfma_roofline', 'second_trunk', 'pgd_trunk',
@@ -679,6 +679,18 @@ def test_bench_line_contract_single_gpu():
     assert res['planes3']['dtype'].startswith('f32 tensors, products on 3 x bf16') and res['planes3']['steps'] == res['steps']
     assert res['config']['matrix_planes'] == 2 and res['range_guard'][0]['iter'] == 0
     assert res['planes3']['ms_per_step'] > 0 and res['planes3']['second_trunk']['ms_per_step'] > 0
+
+
+def test_bench_plain_line_is_the_headline_only(tmp_path):
+    """Without --full the line holds the headline and the figures taken inside its timed steps, and no leg that needs runs of
+    its own; --dump-outputs still writes the last timed step."""
+    res = _run_bench(['--steps', '2', '--warmup', '1', '--batch', '2', '--dump-outputs', str(tmp_path)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline', 'mfma_roofline', 'range_guard'):
+        assert k in res, k
+    assert res['steps'] == 2 and res['warmup'] == 1 and res['value'] > 0 and res['config']['frames_per_gpu'] == 2
+    for k in ('second_trunk', 'pgd_trunk', 'fcaf3d_trunk', 'loader_fed', 'inference', 'planes3', 'cpu_baseline', 'parity_at_bench_size'):
+        assert k not in res, k
+    assert os.path.exists(tmp_path / 'loss.npy') and np.isfinite(np.load(tmp_path / 'loss.npy'))
 
 
 def test_edge_cases_empty_inputs():

@@ -1,5 +1,5 @@
 """Same-box A/B of the dense-convolution routing: `python tools_dev/ab_dense.py MODE` runs bench.py
-(--no-cpu-baseline) with MODE in {full, nowide (256-channel convs back on MIOpen), notr (no
+(--full --no-cpu-baseline) with MODE in {full, nowide (256-channel convs back on MIOpen), notr (no
 transposed tile walk), nowide_notr}. Boxes differ by a few per cent, so alternate the modes in one
 gpurun call."""
 import os, sys
@@ -13,5 +13,5 @@ if 'nowide' in mode:
 if 'notr' in mode:
     d._transposed = lambda H, W: False
     d._cdiv_orig = d._cdiv
-sys.argv = ['bench.py', '--no-cpu-baseline']
+sys.argv = ['bench.py', '--full', '--no-cpu-baseline']
 runpy.run_path('bench.py', run_name='__main__')

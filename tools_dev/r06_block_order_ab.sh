@@ -2,7 +2,7 @@
 # sparse config: mask order within spatial blocks (GGA_SP_BLOCK_ROWS) x XCD-major tile walk (GGA_SP_TILE_ORDER=1)
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-B="python bench.py --no-pgd --no-fcaf3d --no-loader-fed --no-planes3 --no-cpu-baseline --no-inference --steps 10 --warmup 8"
+B="python bench.py --full --no-pgd --no-fcaf3d --no-loader-fed --no-planes3 --no-cpu-baseline --no-inference --steps 10 --warmup 8"
 run() { tag=$1; shift; env "$@" $B > gpurun_out/bench_blk_$tag.json 2> gpurun_out/bench_blk_$tag.err; python - "$tag" <<'PY'
 import json, sys
 t=sys.argv[1]

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 python tools_dev/sparse_precision.py new > gpurun_out/sp_prec_new.log 2>&1
 GGA_SP_HALO=0 python tools_dev/sparse_precision.py new_nohalo > gpurun_out/sp_prec_new_nohalo.log 2>&1
 GGA_SP_OFFSET_SUMS=0 python tools_dev/sparse_precision.py old > gpurun_out/sp_prec_old.log 2>&1
-B="python bench.py --no-pgd --no-fcaf3d --no-loader-fed --no-planes3 --no-cpu-baseline --steps 20 --warmup 8"
+B="python bench.py --full --no-pgd --no-fcaf3d --no-loader-fed --no-planes3 --no-cpu-baseline --steps 20 --warmup 8"
 $B > gpurun_out/bench_sp_new.json 2> gpurun_out/bench_sp_new.err
 GGA_SP_HALO=0 $B > gpurun_out/bench_sp_new_nohalo.json 2> gpurun_out/bench_sp_new_nohalo.err
 GGA_SP_OFFSET_SUMS=0 $B > gpurun_out/bench_sp_old.json 2> gpurun_out/bench_sp_old.err
