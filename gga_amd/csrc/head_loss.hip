@@ -262,14 +262,15 @@ __global__ __launch_bounds__(256) void box_slot_kernel(const float* __restrict__
 
     // ---- Semantic Ratio Loss (head:703-712): max(l,w) - min(l,w) * srl
     const float coef = a[4];
-    const bool l_is_max = d.l >= d.w;
-    const float rw = l_is_max ? d.w : d.l, rl = l_is_max ? d.l : d.w;
+    // torch.min / torch.max return the FIRST index on a tie: with l == w both the shorter and the longer side are l
+    const bool l_is_max = d.l >= d.w, l_is_min = d.l <= d.w;
+    const float rw = l_is_min ? d.l : d.w, rl = l_is_max ? d.l : d.w;
     const float srl = rl - rw * coef;
     part[1 * n + s] = fabsf(srl) * bw[4];
     const float ks = prm.l1_loss_weight * prm.w_srl / avg * bw[4] * sgn(srl);
     float* gs = grad_pred + ((int64_t)GGA_L_SRL * n + s) * 8;
-    gs[3] = ks * (l_is_max ? d.l : -coef * d.l);
-    gs[4] = ks * (l_is_max ? -coef * d.w : d.w);
+    gs[3] = ks * (l_is_max ? (l_is_min ? d.l - coef * d.l : d.l) : -coef * d.l);
+    gs[4] = ks * (l_is_max ? (l_is_min ? 0.0f : -coef * d.w) : d.w);
 }
 
 // One wavefront per object with in-box points (head:184-239).

@@ -119,6 +119,70 @@ def head_loss(preds, tg, tc, alpha=0.0, gamma=4.0, l1_weight=0.25):
     return losses
 
 
+def gather_pred(reg, height, dim, rot, ind):
+    """cat(reg, height, dim, rot) of NCHW maps gathered at ``ind`` [B,K] -> pred [B,K,8] (head:657-676). ``torch.gather``'s
+    backward is a scatter-add: slots that name one cell sum on it, as in the reference."""
+    cat = torch.cat([reg, height, dim, rot], 1)
+    B, C = cat.shape[:2]
+    return cat.reshape(B, C, -1).gather(2, ind[:, None, :].expand(B, C, ind.shape[1])).transpose(1, 2)
+
+
+def pal_distances_packed(xy, offsets, slot, bev):
+    """``pal_distances`` on the packed form the kernels take: ``xy`` [P,2] points, ``offsets`` [n_obj+1], ``slot`` [n_obj]
+    flat slot of every entry (-1 or out of range: skipped), ``bev`` [n,5] in the dtype the result is wanted in
+    -> three [n] sums (min distance, relu beyond 2l, relu beyond 2w)."""
+    n = bev.shape[0]
+    keep, vals = [], []
+    for o in range(len(slot)):
+        s = int(slot[o])
+        if s < 0 or s >= n:
+            continue
+        p = xy[int(offsets[o]):int(offsets[o + 1])].to(bev.dtype)
+        bx = bev[s]
+        c, sn = torch.cos(bx[4]), torch.sin(bx[4])
+        rx, ry = p[:, 0] * c + p[:, 1] * sn, -p[:, 0] * sn + p[:, 1] * c
+        cx, cy = bx[0] * c + bx[1] * sn, -bx[0] * sn + bx[1] * c
+        hl, hw = bx[2] / 2.0, bx[3] / 2.0
+        d = torch.stack([rx - (cx - hl), rx - (cx + hl), ry - (cy - hw), ry - (cy + hw)], 1).abs()
+        keep.append(s)
+        vals.append(torch.stack([d.min(1)[0].sum(), torch.relu((rx - cx).abs() - 2 * hl).sum(),
+                                 torch.relu((ry - cy).abs() - 2 * hw).sum()]))
+    out = bev.new_zeros(n, 3)
+    if keep:
+        out = out.index_add(0, torch.tensor(keep, dtype=torch.int64), torch.stack(vals))
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
+def box_loss_terms(pred, ind, mask, anno, lidar2img, bound_mask, xy, offsets, slot, tc, l1_loss_weight=0.25, w_bpl=0.3,
+                   w_srl=0.1, w_pal=0.1):
+    """The five geometry-aware losses of one task on packed tensors (what ``gga_amd.functional.box_losses`` takes), in
+    the dtype of ``pred``: float64 inputs give the float64 yardstick, with the fp32 constants (and so the kinks) of the
+    fp32 path. -> ``losses`` [5] (bpl, srl, pal_min, pal_x, pal_y), ``box_out`` [B,K,12] (rot, l, w, box2d[4], X, Y,
+    the three point sums), ``parts``: eight scalars (bpl by box side, srl, the three point terms) that add up to the
+    losses - a gradient taken of each one separately gives the magnitude of what cancels in the total."""
+    dt = pred.dtype
+    B, K = ind.shape
+    cw = torch.tensor(tc['code_weights'], dtype=torch.float32)
+    rot, ratio, box, bev = box_geometry(pred, ind, lidar2img.to(dt), tc)
+    anno = anno.to(dt)
+    avg = mask.float().sum() + 1e-4
+    bw = mask[..., None].float() * (~torch.isnan(anno)).float() * cw
+    if slot is not None and len(slot):
+        dmin, dx, dy = (v.view(B, K, 1) for v in pal_distances_packed(xy, offsets, slot, bev.reshape(B * K, 5)))
+    else:
+        dmin = dx = dy = pred.new_zeros(B, K, 1)
+    zero = torch.zeros_like(dmin)
+    rw, rl = ratio.min(-1, keepdim=True)[0], ratio.max(-1, keepdim=True)[0]
+    srl = rl - rw * anno[..., 4:5]
+    wb = bw[..., :4] * bound_mask.float()
+    parts = [l1(box[..., j], anno[..., j], wb[..., j], avg, l1_loss_weight) * w_bpl for j in range(4)]
+    parts.append(l1(srl, torch.zeros_like(srl), bw[..., 4:5], avg, l1_loss_weight) * w_srl)
+    parts += [l1(v, zero, bw[..., 0:1], avg, l1_loss_weight) * w_pal for v in (dmin, dx, dy)]
+    losses = torch.stack([l1(box, anno[..., :4], wb, avg, l1_loss_weight) * w_bpl] + parts[4:])
+    box_out = torch.cat([rot[..., None], ratio, box, bev[..., :2], dmin, dx, dy], -1)
+    return losses, box_out, parts
+
+
 def scatter(feats, coors, batch_size, ny, nx):
     C = feats.shape[1]
     canvas = feats.new_zeros(batch_size, C, ny * nx)
