@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lib = None
 
@@ -72,22 +72,10 @@ SIGNATURES = {
     'gga_sparse_morton_order_workspace_bytes': (sz, [i64]),
     'gga_sparse_morton_order': (i32, [vp, i64, i32, i32, vp, vp, sz, vp]),
     'gga_sparse_mask_order': (i32, [vp, i64, i32, vp, vp, sz, vp]),
-    'gga_sparse_packed_weight_bytes': (sz, [i32, i32, i32]),
-    'gga_sparse_pack_weight': (i32, [vp, i32, i32, i32, i32, vp, vp]),
     'gga_sparse_split_weight_bytes': (sz, [i32, i32, i32]),
-    'gga_sparse_pack_weight_split': (i32, [vp, i32, i32, i32, i32, vp, vp]),
-    'gga_sparse_conv_apply_split': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
-    'gga_sparse_conv_apply_split_strided': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp]),
-    'gga_sparse_conv_wgrad_split_strided': (i32, [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, vp, sz, vp]),
-    'gga_sparse_conv_apply': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
-    'gga_sparse_conv_wgrad': (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp]),
     'gga_sparse_conv_wgrad_workspace_bytes': (sz, [i64, i32, i32, i32]),
-    'gga_sparse_conv_wgrad_split': (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp, sz, vp]),
-    'gga_dense_conv3x3_pack': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, vp, vp]),
     'gga_dense_wgrad3x3_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
-    'gga_dense_wgrad3x3': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, i32, vp, sz, vp]),
     'gga_sparse_pack_weight_planes': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
-    'gga_sparse_conv_apply_planes': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp]),
     'gga_sparse_conv_apply_stats': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp]),
     'gga_sparse_conv_apply_tiles': (i64, [i64]),
     'gga_sparse_conv_apply_bn_bwd': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
@@ -99,32 +87,20 @@ SIGNATURES = {
     'gga_sparse_conv_wgrad_planes': (i32, [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     'gga_absmax_bits': (i32, [vp, i64, i32, i64, vp, vp]),
     'gga_dense_conv3x3_pack_planes': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp]),
-    'gga_dense_conv3x3_planes': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, i32, vp, vp, vp]),
     'gga_dense_conv3x3_levels': (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp]),
     'gga_dense_conv3x3_bn_bwd_pays': (i32, [i32, i32, i32, i32]),
     'gga_dense_conv3x3_bn_bwd_pays_planes': (i32, [i32, i32, i32, i32, i32]),
     'gga_dense_conv3x3_bn_bwd': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
-    'gga_dense_wgrad3x3_planes': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, i32, i32, vp, vp, vp, sz, vp]),
     'gga_absmax_table_blocks': (i64, [i64]),
     'gga_absmax_table': (i32, [vp, i32, i64, vp, i32, vp]),
     'gga_pack_weights_table': (i32, [vp, i32, i64, i32, vp]),
     'gga_dense_wgrad3x3_block_amax': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, i32, i32, vp, i32, vp, i32, vp, sz, vp]),
-    'gga_dense_conv3x3_tiles': (i64, [i32, i32, i32, i32]),
-    'gga_dense_conv3x3_tiles_planes': (i64, [i32, i32, i32, i32, i32]),
     'gga_dense_conv3x3_tile_rows': (i32, [i32, i32, i32, i32, i32]),
     'gga_dense_conv3x3_stat_rows': (i64, [i32, i32, i32, i32, i32, i32]),
-    'gga_dense_conv3x3_slice': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, vp]),
-    'gga_dense_conv3x3_stats': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
-    'gga_bn_relu_fwd_partials': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, vp, i64, vp, vp, vp, i32, vp, sz, vp]),
     'gga_bn_stats_partials': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, i32, vp]),
     'gga_bn_stats_partials_cols': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
-    'gga_dense_conv3x3': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     'gga_bn_relu_workspace_bytes': (sz, [i64, i32]),
     'gga_bn_relu_mask_bytes': (sz, [i64, i32]),
-    'gga_bn_relu_fwd': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    'gga_bn_relu_bwd': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    'gga_bn_relu_fwd_strided': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp, i64, vp, vp, vp, sz, vp]),
-    'gga_bn_relu_bwd_strided': (i32, [vp, i64, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'gga_bn_relu_fwd_ex': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, sz, vp]),
     'gga_bn_relu_bwd_ex': (i32, [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_column_sums': (i32, [vp, i64, i32, vp, vp, sz, vp]),

@@ -374,14 +374,14 @@ static int bn_fwd_impl(const float* x, const float* residual, const float* gamma
                        void* mask_bits, float* saved, const double* given_partials, int n_given, void* workspace,
                        size_t workspace_bytes, void* stream_, uint32_t* amax_y = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_relu_fwd", rows, channels)) return rc;
+    if (int rc = bn_check("gga_bn_relu_fwd_ex", rows, channels)) return rc;
     GGA_REQUIRE(y_row_stride >= channels && y_row_stride % 4 == 0 && ((uintptr_t)y & 15) == 0,
-                "gga_bn_relu_fwd: y row stride %lld must be a multiple of 4 floats >= channels, y 16 B aligned",
+                "gga_bn_relu_fwd_ex: y row stride %lld must be a multiple of 4 floats >= channels, y 16 B aligned",
                 (long long)y_row_stride);
     GGA_REQUIRE(x && y && saved && workspace && running_mean && running_var && (!relu || mask_bits),
-                "gga_bn_relu_fwd: null pointer argument");
+                "gga_bn_relu_fwd_ex: null pointer argument");
     if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_relu_fwd: workspace too small");
+        gga_set_error("gga_bn_relu_fwd_ex: workspace too small");
         return GGA_ERR_WORKSPACE;
     }
     const BnGeom g = bn_geom(rows, channels, y_row_stride);
@@ -419,9 +419,9 @@ extern "C" int gga_bn_stats_partials_cols(const float* gamma, const float* beta,
                                           float* scale_shift, const double* partials, int n_partials, int partials_width,
                                           int column_offset, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_stats_partials", rows, channels)) return rc;
+    if (int rc = bn_check("gga_bn_stats_partials_cols", rows, channels)) return rc;
     GGA_REQUIRE(saved && scale_shift && running_mean && running_var && partials && n_partials >= 1,
-                "gga_bn_stats_partials: null pointer argument");
+                "gga_bn_stats_partials_cols: null pointer argument");
     GGA_REQUIRE(column_offset >= 0 && partials_width >= column_offset + channels,
                 "gga_bn_stats_partials_cols: columns %d .. %d of rows %d wide", column_offset, column_offset + channels, partials_width);
     hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, n_partials, channels,
@@ -463,33 +463,6 @@ extern "C" int gga_bn_stats(const float* x, const float* gamma, const float* bet
     return GGA_OK;
 }
 
-extern "C" int gga_bn_relu_fwd_strided(const float* x, const float* residual, const float* gamma, const float* beta,
-                                       float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                                       float momentum, int training, int relu, float* y, int64_t y_row_stride,
-                                       void* mask_bits, float* saved, void* workspace, size_t workspace_bytes,
-                                       void* stream_) {
-    return bn_fwd_impl(x, residual, gamma, beta, running_mean, running_var, rows, channels, eps, momentum, training, relu,
-                       y, y_row_stride, mask_bits, saved, nullptr, 0, workspace, workspace_bytes, stream_);
-}
-
-extern "C" int gga_bn_relu_fwd_partials(const float* x, const float* residual, const float* gamma, const float* beta,
-                                        float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                                        float momentum, int relu, float* y, int64_t y_row_stride, void* mask_bits,
-                                        float* saved, const double* partials, int n_partials, void* workspace,
-                                        size_t workspace_bytes, void* stream_) {
-    GGA_REQUIRE(partials && n_partials >= 1, "gga_bn_relu_fwd_partials: no partial sums given");
-    return bn_fwd_impl(x, residual, gamma, beta, running_mean, running_var, rows, channels, eps, momentum, 1, relu, y,
-                       y_row_stride, mask_bits, saved, partials, n_partials, workspace, workspace_bytes, stream_);
-}
-
-extern "C" int gga_bn_relu_fwd(const float* x, const float* residual, const float* gamma, const float* beta,
-                               float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                               float momentum, int training, int relu, float* y, void* mask_bits, float* saved,
-                               void* workspace, size_t workspace_bytes, void* stream_) {
-    return gga_bn_relu_fwd_strided(x, residual, gamma, beta, running_mean, running_var, rows, channels, eps, momentum,
-                                   training, relu, y, channels, mask_bits, saved, workspace, workspace_bytes, stream_);
-}
-
 // Library-internal: fold [nblocks][2][C] partial sums (at the head of `workspace`) into grad_gamma / grad_beta and
 // the coefficient table the apply passes read (returned in *coef, inside the workspace).
 int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64_t rows, const float* gamma,
@@ -502,28 +475,20 @@ int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64
     return GGA_OK;
 }
 
-extern "C" int gga_bn_relu_bwd_strided(const float* grad_y, int64_t grad_y_row_stride, const float* x,
-                                       const void* mask_bits, const float* gamma, const float* saved, int64_t rows,
-                                       int channels, int relu, float* grad_x, float* grad_residual, float* grad_gamma,
-                                       float* grad_beta, void* workspace, size_t workspace_bytes, void* stream_) {
-    return gga_bn_relu_bwd_ex(grad_y, grad_y_row_stride, x, mask_bits, gamma, saved, rows, channels, relu, 1, grad_x, grad_residual,
-                              grad_gamma, grad_beta, nullptr, workspace, workspace_bytes, stream_);
-}
-
 extern "C" int gga_bn_relu_bwd_ex(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
                                   const float* gamma, const float* saved, int64_t rows, int channels, int relu, int training,
                                   float* grad_x,
                                   float* grad_residual, float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x,
                                   void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_relu_bwd", rows, channels)) return rc;
+    if (int rc = bn_check("gga_bn_relu_bwd_ex", rows, channels)) return rc;
     GGA_REQUIRE(grad_y_row_stride >= channels && grad_y_row_stride % 4 == 0 && ((uintptr_t)grad_y & 15) == 0,
-                "gga_bn_relu_bwd: grad_y row stride %lld must be a multiple of 4 floats >= channels, grad_y 16 B aligned",
+                "gga_bn_relu_bwd_ex: grad_y row stride %lld must be a multiple of 4 floats >= channels, grad_y 16 B aligned",
                 (long long)grad_y_row_stride);
     GGA_REQUIRE(grad_y && x && saved && grad_x && workspace && (!relu || mask_bits),
-                "gga_bn_relu_bwd: null pointer argument");
+                "gga_bn_relu_bwd_ex: null pointer argument");
     if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_relu_bwd: workspace too small");
+        gga_set_error("gga_bn_relu_bwd_ex: workspace too small");
         return GGA_ERR_WORKSPACE;
     }
     const BnGeom g = bn_geom(rows, channels, grad_y_row_stride);
@@ -600,12 +565,4 @@ extern "C" int gga_bn_relu_bwd_partials(const float* grad_masked, int64_t grad_r
                        (const unsigned long long*)nullptr, saved, coef, g, 0, (float4*)grad_x, (float4*)nullptr, amax_grad_x);
     GGA_CHECK_LAUNCH("bn_bwd_apply_kernel");
     return GGA_OK;
-}
-
-extern "C" int gga_bn_relu_bwd(const float* grad_y, const float* x, const void* mask_bits, const float* gamma,
-                               const float* saved, int64_t rows, int channels, int relu, float* grad_x,
-                               float* grad_residual, float* grad_gamma, float* grad_beta, void* workspace,
-                               size_t workspace_bytes, void* stream_) {
-    return gga_bn_relu_bwd_strided(grad_y, channels, x, mask_bits, gamma, saved, rows, channels, relu, grad_x,
-                                   grad_residual, grad_gamma, grad_beta, workspace, workspace_bytes, stream_);
 }

@@ -27,7 +27,7 @@
 // 32 + 16 pad, conflict-free ds_read_b128) and then feeds all nine taps - lane (r, h) reads
 // pixel (row + ky, r + kx), channels 8h .. 8h+7 - so there are no per-tap gathers and no per-use
 // split. The weight stage of one (tap, chunk) goes through LDS double buffered (the 32-byte half
-// rows of the packed layout of gga_sparse_pack_weight_split with kvol = 9); the next chunk's halo
+// rows of the packed layout of gga_sparse_pack_weight_planes with kvol = 9); the next chunk's halo
 // is requested from global memory before the taps of the current chunk run. 66 KB of LDS: two
 // workgroups per CU.
 #ifndef DC_PIPE_ON
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(TR / MT * 64, (P4 && NT == 4 && NP == 2) ? 1 : 2) v
 
 // Packs a 3x3 convolution weight straight from the framework tensor (any strides, e.g. the
 // channels-last memory of a [cout, cin, 3, 3] parameter) into the split layout of
-// gga_sparse_pack_weight_split with kvol = 9; `backward` builds the operand of the backward-data
+// gga_sparse_pack_weight_planes with kvol = 9; `backward` builds the operand of the backward-data
 // convolution instead (taps reversed, channel roles swapped). One thread per (tap, chunk, col, ch).
 __global__ __launch_bounds__(256) void dense_pack_weight_kernel(const float* __restrict__ W, int64_t s_co, int64_t s_ci,
                                                                int64_t s_ky, int64_t s_kx, int cin, int cout,
@@ -476,19 +476,13 @@ __global__ __launch_bounds__(256) void dense_pack_weight_kernel(const float* __r
     }
 }
 
-extern "C" int gga_dense_conv3x3_pack(const float* weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                                      int64_t stride_kx, int cin, int cout, int backward, void* packed, void* stream) {
-    return gga_dense_conv3x3_pack_planes(weight, stride_co, stride_ci, stride_ky, stride_kx, cin, cout, backward, 3, nullptr,
-                                         packed, stream);
-}
-
 extern "C" int gga_dense_conv3x3_pack_planes(const float* weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
                                              int64_t stride_kx, int cin, int cout, int backward, int planes,
                                              const uint32_t* amax_weight, void* packed, void* stream) {
-    GGA_REQUIRE(weight && packed, "gga_dense_conv3x3_pack: null pointer argument");
-    GGA_REQUIRE(planes == 3 || (planes == 2 && amax_weight), "gga_dense_conv3x3_pack: planes must be 3 (bf16) or 2 (fp16, with amax_weight)");
+    GGA_REQUIRE(weight && packed, "gga_dense_conv3x3_pack_planes: null pointer argument");
+    GGA_REQUIRE(planes == 3 || (planes == 2 && amax_weight), "gga_dense_conv3x3_pack_planes: planes must be 3 (bf16) or 2 (fp16, with amax_weight)");
     const int n_in = backward ? cout : cin, n_out = backward ? cin : cout;
-    GGA_REQUIRE(n_in >= 1 && n_out >= 1 && n_out <= 128, "gga_dense_conv3x3_pack: bad sizes (%d -> %d)", n_in, n_out);
+    GGA_REQUIRE(n_in >= 1 && n_out >= 1 && n_out <= 128, "gga_dense_conv3x3_pack_planes: bad sizes (%d -> %d)", n_in, n_out);
     const int64_t total = (int64_t)(gga_sparse_split_weight_bytes(9, n_in, n_out) / (3 * sizeof(uint16_t)));
     hipLaunchKernelGGL(dense_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        weight, stride_co, stride_ci, stride_ky, stride_kx, cin, cout, backward, mf_nt(n_out), total, planes,
@@ -514,7 +508,7 @@ int dc_tile_rows(int B, int H, int W, int cout, int planes) {
     return 1000 * r16 <= 535 * r8 ? 16 : 8;
 }
 
-extern "C" int64_t gga_dense_conv3x3_tiles_planes(int B, int H, int W, int cout, int planes) {   // H, W of the tile space (swapped when transposed)
+static int64_t dc_tiles(int B, int H, int W, int cout, int planes) {   // H, W of the tile space (swapped when transposed)
     const int tr = dc_tile_rows(B, H, W, cout, planes);
     return (int64_t)B * ((W + DC_TW - 1) / DC_TW) * ((H + tr - 1) / tr);
 }
@@ -522,14 +516,12 @@ extern "C" int64_t gga_dense_conv3x3_tiles_planes(int B, int H, int W, int cout,
 // rows of `stats` (per slice) of a launch over n_slices 128-channel slices (1: gga_dense_conv3x3_bn_bwd): the lock-step kernel
 // leaves one row per tile, the producer / consumer form one per workgroup
 extern "C" int64_t gga_dense_conv3x3_stat_rows(int B, int H, int W, int cout, int planes, int n_slices) {
-    const int64_t tiles = gga_dense_conv3x3_tiles_planes(B, H, W, cout, planes);
+    const int64_t tiles = dc_tiles(B, H, W, cout, planes);
     if (dc_ws_enabled(planes)) return dc_ws_grid(tiles * (n_slices > 1 ? n_slices : 1));
     return tiles;
 }
 
 extern "C" int gga_dense_conv3x3_tile_rows(int B, int H, int W, int cout, int planes) { return dc_tile_rows(B, H, W, cout, planes); }
-
-extern "C" int64_t gga_dense_conv3x3_tiles(int B, int H, int W, int cout) { return gga_dense_conv3x3_tiles_planes(B, H, W, cout, 3); }
 
 // Whether the BatchNorm-backward epilogue (gga_dense_conv3x3_bn_bwd) is cheaper than the reduce pass it replaces. Lock-step forms
 // (three planes; measured inside the PointPillars step, 16 frames): 64 output channels (two workgroups per CU, the other one's
@@ -547,19 +539,6 @@ extern "C" int gga_dense_conv3x3_bn_bwd_pays_planes(int B, int H, int W, int cou
 
 extern "C" int gga_dense_conv3x3_bn_bwd_pays(int B, int H, int W, int cout) { return gga_dense_conv3x3_bn_bwd_pays_planes(B, H, W, cout, 3); }
 
-extern "C" int gga_dense_conv3x3_slice(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                                       float* y, int64_t y_pixel_stride, int transposed, double* stats, void* stream_) {
-    return gga_dense_conv3x3_planes(x, split_weight, B, H, W, cin, cout, y, y_pixel_stride, transposed, stats, 3, nullptr, nullptr,
-                                    stream_);
-}
-
-extern "C" int gga_dense_conv3x3_planes(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                                        float* y, int64_t y_pixel_stride, int transposed, double* stats, int planes,
-                                        const uint32_t* amax_x, const uint32_t* amax_weight, void* stream_) {
-    return gga_dense_conv3x3_bn_bwd(x, split_weight, B, H, W, cin, cout, y, y_pixel_stride, transposed, stats, planes, amax_x,
-                                    amax_weight, nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream_);
-}
-
 extern "C" int gga_dense_conv3x3_bn_bwd(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
                                         float* y, int64_t y_pixel_stride, int transposed, double* stats, int planes,
                                         const uint32_t* amax_x, const uint32_t* amax_weight, const float* bn_x,
@@ -572,20 +551,20 @@ extern "C" int gga_dense_conv3x3_bn_bwd(const float* x, const void* split_weight
     bn.y = bn_x; bn.gamma = bn_gamma; bn.beta = bn_beta; bn.mean = bn_mean; bn.invstd = bn_invstd; bn.ystride = (int)bn_x_pixel_stride;
     DcLevels lv;
     lv.n = 0;
-    GGA_REQUIRE(x && split_weight && y, "gga_dense_conv3x3: null pointer argument");
+    GGA_REQUIRE(x && split_weight && y, "gga_dense_conv3x3_bn_bwd: null pointer argument");
     GGA_REQUIRE(planes == 3 || (planes == 2 && amax_x && amax_weight),
-                "gga_dense_conv3x3: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
-    GGA_REQUIRE(y_pixel_stride >= cout && y_pixel_stride < 2147483647ll, "gga_dense_conv3x3: y pixel stride %lld < cout",
+                "gga_dense_conv3x3_bn_bwd: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
+    GGA_REQUIRE(y_pixel_stride >= cout && y_pixel_stride < 2147483647ll, "gga_dense_conv3x3_bn_bwd: y pixel stride %lld < cout",
                 (long long)y_pixel_stride);
     GGA_REQUIRE(B >= 1 && H >= 1 && W >= 1 && cin >= 32 && cin % 32 == 0 && (cout == 64 || cout == 128) &&
                     (int64_t)H * W * cin < 2147483647ll,
-                "gga_dense_conv3x3: need cin %% 32 == 0 and cout 64 or 128 (got %d -> %d)", cin, cout);
+                "gga_dense_conv3x3_bn_bwd: need cin %% 32 == 0 and cout 64 or 128 (got %d -> %d)", cin, cout);
     const int prow = transposed ? 1 : W, pcol = transposed ? W : 1;
     if (transposed) { const int t = H; H = W; W = t; }          // tile space of the transposed walk
     // gga_dense_conv3x3_stat_rows / _tile_rows describe the producer / consumer grid whenever that form is enabled for `planes`: a
     // shape it cannot take must not fall back silently to the lock-step kernel (other tile size, other number of stats rows)
     GGA_REQUIRE(!dc_ws_enabled(planes) || cin <= DC_WS_MAX_CIN,
-                "gga_dense_conv3x3: %d input channels on two planes (the producer / consumer form takes <= %d; use planes = 3 or GGA_DC_WS=0)",
+                "gga_dense_conv3x3_bn_bwd: %d input channels on two planes (the producer / consumer form takes <= %d; use planes = 3 or GGA_DC_WS=0)",
                 cin, DC_WS_MAX_CIN);
     if (dc_ws_enabled(planes)) {      // two fp16 planes: the producer / consumer form (dense_conv_ws.hip)
         hipEvent_t* tev = gga_timing_acquire(GGA_TIME_DENSE_CONV, GGA_TIMING_CONV_KEY(cin, cout, (int64_t)H * W));
@@ -598,7 +577,7 @@ extern "C" int gga_dense_conv3x3_bn_bwd(const float* x, const void* split_weight
     const int trows = dc_tile_rows(B, H, W, cout, planes);
     const int tx = (W + DC_TW - 1) / DC_TW, ty = (H + trows - 1) / trows;
     const int64_t n_tiles = (int64_t)B * tx * ty;
-    GGA_REQUIRE(n_tiles < 2147483647ll, "gga_dense_conv3x3: too many tiles");
+    GGA_REQUIRE(n_tiles < 2147483647ll, "gga_dense_conv3x3_bn_bwd: too many tiles");
     // One tile per workgroup. The kernel also runs as persistent workgroups (grid < tiles, same speed
     // in isolation), but inside the train step a persistent grid starts while the previous kernel's
     // tail still occupies some CUs and the static tile split then leaves stragglers (one bench run in
@@ -700,16 +679,6 @@ extern "C" int gga_dense_conv3x3_levels(int n_entries, const float* const* x, co
 #undef DC_LV
     GGA_CHECK_LAUNCH("dense_conv3x3_x9_kernel (levels)");
     return GGA_OK;
-}
-
-extern "C" int gga_dense_conv3x3_stats(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                                       float* y, double* stats, void* stream) {
-    return gga_dense_conv3x3_slice(x, split_weight, B, H, W, cin, cout, y, cout, 0, stats, stream);
-}
-
-extern "C" int gga_dense_conv3x3(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                                 float* y, void* stream) {
-    return gga_dense_conv3x3_slice(x, split_weight, B, H, W, cin, cout, y, cout, 0, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------ dense 3x3 weight gradient
@@ -960,22 +929,6 @@ extern "C" size_t gga_dense_wgrad3x3_workspace_bytes(int B, int H, int W, int ci
     return (size_t)(n0 > n1 ? n0 : n1) * (cin >> 6) * (cout >> 6) * 9 * 64 * 64 * sizeof(float);
 }
 
-extern "C" int gga_dense_wgrad3x3(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
-                                  float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                                  int64_t stride_kx, int transposed, void* workspace, size_t workspace_bytes,
-                                  void* stream_) {
-    return gga_dense_wgrad3x3_planes(x, grad_y, B, H, W, cin, cout, grad_weight, stride_co, stride_ci, stride_ky, stride_kx,
-                                     transposed, 3, nullptr, nullptr, workspace, workspace_bytes, stream_);
-}
-
-extern "C" int gga_dense_wgrad3x3_planes(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
-                                         float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                                         int64_t stride_kx, int transposed, int planes, const uint32_t* amax_x,
-                                         const uint32_t* amax_grad_y, void* workspace, size_t workspace_bytes, void* stream_) {
-    return gga_dense_wgrad3x3_block_amax(x, grad_y, B, H, W, cin, cout, grad_weight, stride_co, stride_ci, stride_ky, stride_kx,
-                                         transposed, planes, amax_x, 0, amax_grad_y, 0, workspace, workspace_bytes, stream_);
-}
-
 extern "C" int gga_dense_wgrad3x3_block_amax(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
                                              float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
                                              int64_t stride_kx, int transposed, int planes, const uint32_t* amax_x,
@@ -983,16 +936,16 @@ extern "C" int gga_dense_wgrad3x3_block_amax(const float* x, const float* grad_y
                                              void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int xblk = amax_x_per_block ? 1 : 0, gblk = amax_grad_y_per_block ? 1 : 0;
-    GGA_REQUIRE(x && grad_y && grad_weight && workspace, "gga_dense_wgrad3x3: null pointer argument");
+    GGA_REQUIRE(x && grad_y && grad_weight && workspace, "gga_dense_wgrad3x3_block_amax: null pointer argument");
     GGA_REQUIRE(planes == 3 || (planes == 2 && amax_x && amax_grad_y),
-                "gga_dense_wgrad3x3: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
+                "gga_dense_wgrad3x3_block_amax: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
     GGA_REQUIRE(B >= 1 && H >= 1 && W >= 1 && cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0,
-                "gga_dense_wgrad3x3: cin and cout must be multiples of 64 (got %d -> %d)", cin, cout);
+                "gga_dense_wgrad3x3_block_amax: cin and cout must be multiples of 64 (got %d -> %d)", cin, cout);
     GGA_REQUIRE((int64_t)H * W * (cin > cout ? cin : cout) * 4 < ((int64_t)1 << 31),
-                "gga_dense_wgrad3x3: one image of an operand must stay below 2 GiB (32-bit piece offsets; got %d x %d x %d channels)", H, W,
+                "gga_dense_wgrad3x3_block_amax: one image of an operand must stay below 2 GiB (32-bit piece offsets; got %d x %d x %d channels)", H, W,
                 cin > cout ? cin : cout);
     if (workspace_bytes < gga_dense_wgrad3x3_workspace_bytes(B, H, W, cin, cout)) {
-        gga_set_error("gga_dense_wgrad3x3: workspace too small");
+        gga_set_error("gga_dense_wgrad3x3_block_amax: workspace too small");
         return GGA_ERR_WORKSPACE;
     }
     // transposed: strips of 32 pixels along the image's H, rows along its W; the taps swap with them

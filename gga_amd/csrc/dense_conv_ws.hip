@@ -59,12 +59,12 @@ int dc_launch_ws(const float* x, const void* split_weight, int B, int H, int W, 
     sl.n = 0;
     if (slices) sl = *slices;
     const int64_t n_tiles = (int64_t)B * tx * ty * (sl.n > 1 ? sl.n : 1);
-    GGA_REQUIRE(n_tiles < 2147483647ll, "gga_dense_conv3x3: too many tiles");
+    GGA_REQUIRE(n_tiles < 2147483647ll, "dc_launch_ws: too many tiles");
     // one workgroup per CU (512 threads at 256 registers); more tiles than CUs: persistent workgroups, tiles b, b + grid, ...
     static const float* zero_pages[GGA_MAX_DEVICES] = {};           // per device: the address of dc_zero_page (a lookup, not an allocation)
     int dev = 0;
     GGA_CHECK_HIP(hipGetDevice(&dev), "hipGetDevice");
-    GGA_REQUIRE(dev >= 0 && dev < GGA_MAX_DEVICES, "gga_dense_conv3x3: device %d", dev);
+    GGA_REQUIRE(dev >= 0 && dev < GGA_MAX_DEVICES, "dc_launch_ws: device %d", dev);
     if (!zero_pages[dev]) {
         void* p = nullptr;
         GGA_CHECK_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(dc_zero_page)), "hipGetSymbolAddress(dc_zero_page)");

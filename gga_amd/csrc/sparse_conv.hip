@@ -3,7 +3,8 @@
 // transposed, 1x1 and pillar-restricted convolutions of the BEV trunk through arithmetic rule books), its halo form for the
 // submanifold convolutions of densely populated levels (sp_conv_halo_kernel), the deterministic weight gradient
 // (sp_conv_wgrad_x9_kernel), the weight packing and the absmax pass. Index structures and rule books: sparse_index.hip;
-// fp32-MFMA generation for odd widths: sparse_conv_f32.hip; the 3x3 stride-1 dense kernels: dense_conv.hip.
+// the 3x3 stride-1 dense kernels: dense_conv.hip. Input widths that are no multiple of 4 take the scalar-load
+// instantiations (VEC = false) of the same kernels.
 // Reference: mmdet3d/models/middle_encoders/sparse_encoder.py:107-214, mmdet3d/ops/sparse_block.py:82-199 (layers of the
 // un-vendored mmcv / spconv wheels).
 // Experiments that were measured and not shipped (an LDS-DMA ring form of the gather-GEMM, ablation builds of every kernel,
@@ -101,17 +102,12 @@ extern "C" size_t gga_sparse_split_weight_bytes(int kvol, int cin, int cout) {
     return (size_t)kvol * ((cin + MF_TK - 1) / MF_TK) * 3 * 32 * mf_nt(cout) * 32 * sizeof(uint16_t);
 }
 
-extern "C" int gga_sparse_pack_weight_split(const float* weight, int kvol, int cin, int cout, int transpose, void* packed,
-                                            void* stream) {
-    return gga_sparse_pack_weight_planes(weight, kvol, cin, cout, transpose, 3, nullptr, packed, stream);
-}
-
 extern "C" int gga_sparse_pack_weight_planes(const float* weight, int kvol, int cin, int cout, int transpose, int planes,
                                              const uint32_t* amax_weight, void* packed, void* stream) {
-    GGA_REQUIRE(weight && packed, "gga_sparse_pack_weight_split: null pointer argument");
-    GGA_REQUIRE(planes == 3 || (planes == 2 && amax_weight), "gga_sparse_pack_weight_split: planes must be 3 (bf16) or 2 (fp16, with amax_weight)");
+    GGA_REQUIRE(weight && packed, "gga_sparse_pack_weight_planes: null pointer argument");
+    GGA_REQUIRE(planes == 3 || (planes == 2 && amax_weight), "gga_sparse_pack_weight_planes: planes must be 3 (bf16) or 2 (fp16, with amax_weight)");
     GGA_REQUIRE(kvol >= 1 && cin >= 1 && cout >= 1 && cout <= 128,
-                "gga_sparse_pack_weight_split: bad sizes (kvol=%d cin=%d cout=%d; cout <= 128)", kvol, cin, cout);
+                "gga_sparse_pack_weight_planes: bad sizes (kvol=%d cin=%d cout=%d; cout <= 128)", kvol, cin, cout);
     const int64_t total = (int64_t)(gga_sparse_split_weight_bytes(kvol, cin, cout) / (3 * sizeof(uint16_t)));
     hipLaunchKernelGGL(sp_pack_weight_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        weight, kvol, cin, cout, mf_nt(cout), transpose, total, planes, amax_weight, (uint16_t*)packed);
@@ -833,21 +829,6 @@ extern "C" int gga_sparse_conv_apply_halo(const float* x, const void* split_weig
     return GGA_OK;
 }
 
-extern "C" int gga_sparse_conv_apply_split_strided(const float* x, const int32_t* map, const void* split_weight,
-                                                   const int32_t* perm, const uint32_t* rowmask, int64_t n_rows, int kvol,
-                                                   int cin, int cout, int flip, float* y, int64_t y_row_stride, void* stream_) {
-    return gga_sparse_conv_apply_planes(x, map, split_weight, perm, rowmask, n_rows, kvol, cin, cout, flip, y, y_row_stride, 3,
-                                        nullptr, nullptr, stream_);
-}
-
-extern "C" int gga_sparse_conv_apply_planes(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                            const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,
-                                            float* y, int64_t y_row_stride, int planes, const uint32_t* amax_x,
-                                            const uint32_t* amax_weight, void* stream_) {
-    return gga_sparse_conv_apply_stats(x, map, split_weight, perm, rowmask, n_rows, kvol, cin, cout, flip, y, y_row_stride, planes,
-                                       amax_x, amax_weight, nullptr, stream_);
-}
-
 extern "C" int64_t gga_sparse_conv_apply_tiles(int64_t n_rows) { return (n_rows + X9_TM - 1) / X9_TM; }
 
 extern "C" int gga_sparse_conv_apply_stats(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
@@ -869,11 +850,11 @@ extern "C" int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, 
                 "gga_sparse_conv_apply_bn_bwd: the BatchNorm epilogue needs stats, the saved mean / invstd and a row stride >= cout");
     SpBnBwd bn;
     bn.y = bn_x; bn.gamma = bn_gamma; bn.beta = bn_beta; bn.mean = bn_mean; bn.invstd = bn_invstd; bn.ystride = bn_x_row_stride;
-    GGA_REQUIRE(x && map && split_weight && y, "gga_sparse_conv_apply_split: null pointer argument");
+    GGA_REQUIRE(x && map && split_weight && y, "gga_sparse_conv_apply_bn_bwd: null pointer argument");
     GGA_REQUIRE(planes == 3 || (planes == 2 && amax_x && amax_weight),
-                "gga_sparse_conv_apply_split: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
+                "gga_sparse_conv_apply_bn_bwd: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
     GGA_REQUIRE(n_rows >= 1 && kvol >= 1 && cin >= 1 && cout >= 1 && cout <= 128 && y_row_stride >= cout,
-                "gga_sparse_conv_apply_split: bad sizes (rows=%lld kvol=%d cin=%d cout=%d row stride %lld; cout <= 128)",
+                "gga_sparse_conv_apply_bn_bwd: bad sizes (rows=%lld kvol=%d cin=%d cout=%d row stride %lld; cout <= 128)",
                 (long long)n_rows, kvol, cin, cout, (long long)y_row_stride);
     const int64_t n_tiles = (n_rows + X9_TM - 1) / X9_TM;
     static const int tile_order = getenv("GGA_SP_TILE_ORDER") ? atoi(getenv("GGA_SP_TILE_ORDER")) : 0;
@@ -900,12 +881,6 @@ extern "C" int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, 
     GGA_CHECK_LAUNCH("sp_conv_x9_kernel");
     GGA_TIME_STOP(tev, stream);
     return GGA_OK;
-}
-
-extern "C" int gga_sparse_conv_apply_split(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                           const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,
-                                           float* y, void* stream_) {
-    return gga_sparse_conv_apply_split_strided(x, map, split_weight, perm, rowmask, n_rows, kvol, cin, cout, flip, y, cout, stream_);
 }
 
 // ------------------------------------------------------------------------------ weight gradient, bf16 planes
@@ -1218,21 +1193,6 @@ extern "C" size_t gga_sparse_conv_wgrad_workspace_bytes(int64_t n_rows, int kvol
     return (size_t)spw_chunks(n_rows, kvol) * kvol * (ni * 32) * (nj * 32) * sizeof(float);
 }
 
-extern "C" int gga_sparse_conv_wgrad_split(const float* x, const float* grad_out, const int32_t* map, int64_t n_rows,
-                                           int kvol, int cin, int cout, float* grad_weight, void* workspace,
-                                           size_t workspace_bytes, void* stream_) {
-    return gga_sparse_conv_wgrad_split_strided(x, cin, grad_out, cout, map, n_rows, kvol, cin, cout, grad_weight, workspace,
-                                               workspace_bytes, stream_);
-}
-
-extern "C" int gga_sparse_conv_wgrad_split_strided(const float* x, int64_t x_row_stride, const float* grad_out,
-                                                   int64_t grad_out_row_stride, const int32_t* map, int64_t n_rows, int kvol,
-                                                   int cin, int cout, float* grad_weight, void* workspace,
-                                                   size_t workspace_bytes, void* stream_) {
-    return gga_sparse_conv_wgrad_planes(x, x_row_stride, grad_out, grad_out_row_stride, map, n_rows, kvol, cin, cout, grad_weight, 3,
-                                        nullptr, nullptr, workspace, workspace_bytes, stream_);
-}
-
 extern "C" int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride, const float* grad_out,
                                             int64_t grad_out_row_stride, const int32_t* map, int64_t n_rows, int kvol, int cin,
                                             int cout, float* grad_weight, int planes, const uint32_t* amax_x,
@@ -1240,12 +1200,12 @@ extern "C" int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride
                                             void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GGA_REQUIRE(planes == 3 || (planes == 2 && amax_x && amax_grad_out),
-                "gga_sparse_conv_wgrad_split: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
-    GGA_REQUIRE(x && grad_out && map && grad_weight && workspace, "gga_sparse_conv_wgrad_split: null pointer argument");
+                "gga_sparse_conv_wgrad_planes: planes must be 3 (bf16) or 2 (fp16, with the operands' absmax bits)");
+    GGA_REQUIRE(x && grad_out && map && grad_weight && workspace, "gga_sparse_conv_wgrad_planes: null pointer argument");
     GGA_REQUIRE(n_rows >= 1 && kvol >= 1 && cin >= 1 && cin <= 128 && cout >= 1 && cout <= 128 && x_row_stride >= cin &&
-                grad_out_row_stride >= cout, "gga_sparse_conv_wgrad_split: bad sizes (cin, cout <= 128; row strides >= widths)");
+                grad_out_row_stride >= cout, "gga_sparse_conv_wgrad_planes: bad sizes (cin, cout <= 128; row strides >= widths)");
     if (workspace_bytes < gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout)) {
-        gga_set_error("gga_sparse_conv_wgrad_split: workspace %zu B < required %zu B", workspace_bytes,
+        gga_set_error("gga_sparse_conv_wgrad_planes: workspace %zu B < required %zu B", workspace_bytes,
                       gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout));
         return GGA_ERR_WORKSPACE;
     }

@@ -1,6 +1,6 @@
 // a3': sparse 3D convolution for the SECOND-style SparseEncoder (gfx950).
 // (this file: the index structures - hash index, output sites of strided convolutions, rule books, per-row offset masks;
-//  the products are in sparse_conv.hip (split-plane matrix kernels) and sparse_conv_f32.hip (fp32 MFMA, any width))
+//  the products are in sparse_conv.hip (split-plane matrix kernels, any input width))
 //
 // Reference: mmdet3d/models/middle_encoders/sparse_encoder.py:107-214 and
 // mmdet3d/ops/sparse_block.py:82-199 build SubMConv3d / SparseConv3d layers from the

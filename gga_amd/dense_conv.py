@@ -1,5 +1,5 @@
 """3x3 / stride-1 / pad-1 convolutions of the BEV trunk and the head branches on the repo's matrix kernels
-(``gga_dense_conv3x3_planes`` / ``gga_dense_wgrad3x3_planes``): forward, backward-data and weight gradient; every other
+(``gga_dense_conv3x3_bn_bwd`` / ``gga_dense_wgrad3x3_block_amax``): forward, backward-data and weight gradient; every other
 eligible convolution is handed on to ``strided_conv`` (stride-2 3x3, 1x1, kernel = stride transposed).
 
 Reference call sites: the block convolutions of ``SECOND`` (backbones/second.py:58-63) and the
@@ -306,7 +306,7 @@ def _run(x, weight, backward, want_stats=False, x_amax=None, w_amax=None, y=None
         wp, wa = _operand(weight, backward, tr, planes)
         check(L.gga_dense_conv3x3_bn_bwd(F._p(x), F._p(wp), B, H, W, n_in, n_out,
                                          y.data_ptr() + 4 * y_col, ystride, int(tr), F._p(stats), planes, F._p(x_amax),
-                                         F._p(wa), *(bn.part(0, n_out) if bn else none6), F._stream()), 'gga_dense_conv3x3')
+                                         F._p(wa), *(bn.part(0, n_out) if bn else none6), F._stream()), 'gga_dense_conv3x3_bn_bwd')
         if bn:
             stats = [(0, n_out, stats)]
     elif bn is None and n_out // 128 <= 16:
@@ -342,7 +342,7 @@ def _run(x, weight, backward, want_stats=False, x_amax=None, w_amax=None, y=None
             check(L.gga_dense_conv3x3_bn_bwd(F._p(x), F._p(wp), B, H, W, n_in, 128,
                                              y.data_ptr() + 4 * (y_col + c0), ystride, int(tr), F._p(st), planes, F._p(x_amax),
                                              F._p(wa), *(bn.part(c0, 128) if bn else none6), F._stream()),
-                  'gga_dense_conv3x3_slice')
+                  'gga_dense_conv3x3_bn_bwd')
         if bn:
             stats = parts
         elif parts:
@@ -360,7 +360,7 @@ def run_bn_bwd(gy, weight, g_amax, w_amax, src):
 
 
 def _wgrad(x, gy, weight, x_amax=None, g_amax=None, g_per_block=False):
-    """Weight gradient on the matrix path (``gga_dense_wgrad3x3``), in the parameter's memory layout. ``g_per_block``:
+    """Weight gradient on the matrix path (``gga_dense_wgrad3x3_block_amax``), in the parameter's memory layout. ``g_per_block``:
     ``g_amax`` holds one absmax per 64-channel block of ``gy`` (two-plane arithmetic)."""
     L = _lib.lib()
     B, cin, H, W = x.shape
@@ -381,7 +381,7 @@ def _wgrad(x, gy, weight, x_amax=None, g_amax=None, g_per_block=False):
         x_amax = g_amax = None
     check(L.gga_dense_wgrad3x3_block_amax(F._p(x), F._p(gy), B, H, W, cin, cout, F._p(gw), s[0], s[1], s[2], s[3], int(tr), planes,
                                           F._p(x_amax), 0, F._p(g_amax), int(bool(g_per_block) and planes == 2), F._p(ws), ws.numel(),
-                                          F._stream()), 'gga_dense_wgrad3x3')
+                                          F._stream()), 'gga_dense_wgrad3x3_block_amax')
     return gw
 
 
@@ -451,7 +451,7 @@ def _run_levels(xs, weight, backward, x_amaxes, w_amax, bias=None):
     if planes == 2 and RANGE_GUARD.armed:
         RANGE_GUARD.record(weight)
     entries = [(x, y, c0, wp, a) for c0, wp in packs for x, y, a in zip(xs, ys, x_amaxes)]
-    # maps with enough 16-row tiles run the 512-thread form (as gga_dense_conv3x3_planes would pick for them), the small
+    # maps with enough 16-row tiles run the 512-thread form (as gga_dense_conv3x3_bn_bwd would pick for them), the small
     # ones the 8-row form: two launches
     big = lambda x: width == 128 and B * _cdiv(x.shape[3], 32) * _cdiv(x.shape[2], 16) >= 384
     groups = [(16, [e for e in entries if big(e[0])]), (8, [e for e in entries if not big(e[0])])]

@@ -666,7 +666,7 @@ class _BNAct(torch.autograd.Function):
         check(L.gga_bn_relu_fwd_ex(_p(x), _p(residual), _p(gamma), _p(beta), _p(running_mean), _p(running_var), rows, C,
                                    eps, momentum, int(training), int(relu), _p(y), C, _p(bits), _p(saved),
                                    _p(partials) if use else None, int(partials.shape[0]) if use else 0, _p(amax), _p(ws),
-                                   ws.numel(), _stream()), 'gga_bn_relu_fwd')
+                                   ws.numel(), _stream()), 'gga_bn_relu_fwd_ex')
         ctx.save_for_backward(x, gamma, saved, bits)
         ctx.cfg = (rows, C, relu, residual is not None, bool(training))
         if amax is None:
@@ -697,7 +697,7 @@ class _BNAct(torch.autograd.Function):
             dense_conv.set_amax(gx, amax)
             return gx, None, gg, gb, None, None, None, None, None, None, None, None, None
         check(L.gga_bn_relu_bwd_ex(_p(gy), C, _p(x), _p(bits), _p(gamma), _p(saved), rows, C, int(relu), int(training), _p(gx),
-                                   _p(gres), _p(gg), _p(gb), _p(amax), _p(ws), ws.numel(), _stream()), 'gga_bn_relu_bwd')
+                                   _p(gres), _p(gg), _p(gb), _p(amax), _p(ws), ws.numel(), _stream()), 'gga_bn_relu_bwd_ex')
         dense_conv.set_amax(gx, amax)
         return gx, gres, gg, gb, None, None, None, None, None, None, None, None, None
 
@@ -831,7 +831,7 @@ def gn_act(x, gn, relu=True):
 class _BNActCat(torch.autograd.Function):
     """``cat([relu(bn_i(x_i))], dim=1)`` for channels-last inputs of equal [B, ., H, W]: every
     branch writes its column block of the concatenated map and reads its block of the gradient in
-    place (gga_bn_relu_fwd_strided / _bwd_strided)."""
+    place (the row strides of gga_bn_relu_fwd_ex / gga_bn_relu_bwd_ex)."""
 
     @staticmethod
     def forward(ctx, n, cfg, *args):
@@ -860,7 +860,7 @@ class _BNActCat(torch.autograd.Function):
             check(L.gga_bn_relu_fwd_ex(_p(xs[i]), None, _p(gammas[i]), _p(betas[i]), _p(rms[i]), _p(rvs[i]), rows, C,
                                        eps, momentum, int(training), 1, out.data_ptr() + 4 * off, tot, _p(bits),
                                        _p(saved), _p(pt), int(pt.shape[0]) if pt is not None else 0, _p(amax), _p(ws), ws.numel(),
-                                       _stream()), 'gga_bn_relu_fwd_strided')
+                                       _stream()), 'gga_bn_relu_fwd_ex')
             saved_all.append(saved)
             bits_all.append(bits)
             off += C
@@ -904,7 +904,7 @@ class _BNActCat(torch.autograd.Function):
             else:
                 check(L.gga_bn_relu_bwd_ex(g.data_ptr() + 4 * off, tot, _p(x), _p(bits_all[i]), _p(gammas[i]),
                                            _p(saved_all[i]), rows, C, 1, 1, _p(gx), None, _p(gg), _p(gb), _p(amax), _p(ws),
-                                           ws.numel(), _stream()), 'gga_bn_relu_bwd_strided')
+                                           ws.numel(), _stream()), 'gga_bn_relu_bwd_ex')
             dense_conv.set_amax(gx, amax)
             gxs.append(gx), ggs.append(gg), gbs.append(gb)
             off += C

@@ -4,7 +4,7 @@ pieces configs/_base_/models/fcos3d.py names - mmdet's ``ResNet`` (caffe-style b
 BatchNorm) and ``FPN`` - restated with mmdet's layer names so torchvision / detectron2 / mmdet
 checkpoints load (parity unpinned: those modules are not in the reference tree).
 
-Dense 2D convolutions: the 3x3 / stride-1 ones of the residual blocks qualify for ``gga_dense_conv3x3``
+Dense 2D convolutions: the 3x3 / stride-1 ones of the residual blocks qualify for ``gga_dense_conv3x3_bn_bwd``
 (channels-last activations, 64 .. 512 channels); the rest (7x7 stem, 1x1, strided) are MIOpen's.
 """
 import torch

@@ -9,7 +9,7 @@ plain dense convolution (run as strided_conv.py's gather-GEMM over the canvas ro
 * the weight gradient ``sum_cells x^T gy``, where ``x`` is non-zero only at the occupied cells,
 
 i.e. a gather-GEMM over the pillars with the gather map ``gga_pillar_conv_map`` — the same
-kernels as the sparse 3D convolution (``gga_sparse_conv_apply_split`` / ``gga_sparse_conv_wgrad``),
+kernels as the sparse 3D convolution (``gga_sparse_conv_apply_bn_bwd`` / ``gga_sparse_conv_wgrad_planes``),
 with the output gradient (NHWC rows = output cells) as the gathered operand. At batch 16 that
 replaces a 3.1 ms backward-data convolution into an 877 MB canvas gradient (+ its zero fill and
 the scatter's gather) and a 3.3 ms weight-gradient convolution by < 0.5 ms of work; the values

@@ -327,12 +327,6 @@ class SparseSequential(SparseModule):
         return x
 
 
-# fp32 products through three bf16 planes per operand (nine exact partial products on the bf16
-# matrix cores, fp32 accumulation): 1.7x the fp32 MFMA rate at no loss of accuracy
-# (csrc/sparse_conv.hip, tools_dev/micro/bf16x9_probe.hip). False = the native fp32 MFMA kernel.
-SPLIT_BF16 = True
-
-
 # Halo form of the submanifold gather-GEMM (csrc/sparse_conv.hip::sp_conv_halo_kernel; two fp16 planes) for the output widths in
 # HALO_COLUMNS: 128. (The entry point also takes 64 columns - tests/test_sparse_gpu.py keeps that covered - but the product does
 # not send them there: half the matrix work per gathered byte, no difference in the step, profiles/r05_sp_halo2.txt.) It walks
@@ -364,28 +358,25 @@ def amax_bits(t):
     return dense_conv.tensor_amax(t)
 
 
-def _pack_weight(w, kvol, cin, cout, transpose, split=None, w_amax=None):
+def _pack_weight(w, kvol, cin, cout, transpose, w_amax=None):
     """[kvol,cin,cout] (or [kvol,cout,cin] with ``transpose``) -> the conv kernel's operand order
-    (gga_sparse_pack_weight / gga_sparse_pack_weight_split). ``w_amax``: absmax bits of the weight -> two fp16
-    planes; None -> three bf16 planes."""
+    (gga_sparse_pack_weight_planes). ``w_amax``: absmax bits of the weight -> two fp16
+    planes; None -> three bf16 planes (fp32 as the sum of three bf16 numbers: nine exact partial products on the
+    matrix cores, fp32 accumulation - csrc/sparse_conv.hip, tools_dev/micro/bf16x9_probe.hip)."""
     L = _lib.lib()
-    if SPLIT_BF16 if split is None else split:
-        wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, cout) // 2, dtype=torch.int16, device=w.device)
-        check(L.gga_sparse_pack_weight_planes(F._p(w), kvol, cin, cout, transpose, 2 if w_amax is not None else 3, F._p(w_amax),
-                                              F._p(wp), F._stream()), 'gga_sparse_pack_weight_split')
-        return wp
-    wp = torch.empty(L.gga_sparse_packed_weight_bytes(kvol, cin, cout) // 4, dtype=torch.float32, device=w.device)
-    check(L.gga_sparse_pack_weight(F._p(w), kvol, cin, cout, transpose, F._p(wp), F._stream()), 'gga_sparse_pack_weight')
+    wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, cout) // 2, dtype=torch.int16, device=w.device)
+    check(L.gga_sparse_pack_weight_planes(F._p(w), kvol, cin, cout, transpose, 2 if w_amax is not None else 3, F._p(w_amax),
+                                          F._p(wp), F._stream()), 'gga_sparse_pack_weight_planes')
     return wp
 
 
 def _conv_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, x_amax=None, w_amax=None, stats=None, bn=None):
     """``x_amax`` / ``w_amax`` given: ``wp`` holds two fp16 planes (packed with the same ``w_amax``). ``stats``: f64
-    [gga_sparse_conv_apply_tiles(n_rows), 2, cout] for the per-channel sums of y (split-plane kernels only). ``bn``
+    [gga_sparse_conv_apply_tiles(n_rows), 2, cout] for the per-channel sums of y. ``bn``
     (backward-data launches, with ``stats``): ``BnSource.part`` pointers of the BatchNorm + ReLU whose output gradient y
     is - y is stored masked by the ReLU and ``stats`` receives that BatchNorm's backward sums."""
     L = _lib.lib()
-    if (HALO and wp.dtype == torch.int16 and w_amax is not None and rb.coors is not None and cin % 32 == 0 and 9 <= kvol <= 27
+    if (HALO and w_amax is not None and rb.coors is not None and cin % 32 == 0 and 9 <= kvol <= 27
             and cout in HALO_COLUMNS and n_rows >= HALO_MIN_ROWS and rb.occupancy >= HALO_MIN_OCCUPANCY):
         hl = rb.halo()
         check(L.gga_sparse_conv_apply_halo(F._p(x), F._p(wp), F._p(hl.tile_rows), F._p(hl.counts), hl.capacity, F._p(hl.halo_rows),
@@ -393,30 +384,21 @@ def _conv_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, x_amax=None, w_amax
                                            F._p(w_amax), F._p(stats), *(bn if bn else (None, 0, None, None, None, None)), F._stream()),
               'gga_sparse_conv_apply_halo')
         return
-    if wp.dtype == torch.int16:
-        check(L.gga_sparse_conv_apply_bn_bwd(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n_rows,
-                                             kvol, cin, cout, flip, F._p(y), cout, 2 if w_amax is not None else 3, F._p(x_amax),
-                                             F._p(w_amax), F._p(stats), *(bn if bn else (None, 0, None, None, None, None)),
-                                             F._stream()), 'gga_sparse_conv_apply_split')
-    else:
-        check(L.gga_sparse_conv_apply(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n_rows, kvol, cin, cout,
-                                      flip, F._p(y), F._stream()), 'gga_sparse_conv_apply')
+    check(L.gga_sparse_conv_apply_bn_bwd(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n_rows,
+                                         kvol, cin, cout, flip, F._p(y), cout, 2 if w_amax is not None else 3, F._p(x_amax),
+                                         F._p(w_amax), F._p(stats), *(bn if bn else (None, 0, None, None, None, None)),
+                                         F._stream()), 'gga_sparse_conv_apply_bn_bwd')
 
 
 def conv_wgrad(x, gy, nbr, n_rows, kvol, cin, cout, gw, x_amax=None, g_amax=None):
     """gw [kvol,cin,cout] = sum over the pairs of ``nbr`` of x[in]^T gy[out]: the deterministic
-    split-plane kernel (default; two fp16 planes when the operands' absmax bits are given, three bf16 planes
-    otherwise) or the fp32-MFMA kernel with float atomics (``SPLIT_BF16 = False``)."""
+    split-plane kernel (two fp16 planes when the operands' absmax bits are given, three bf16 planes otherwise)."""
     L = _lib.lib()
-    if SPLIT_BF16:
-        ws = F._workspace('sp_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout), x.device)
-        two = x_amax is not None and g_amax is not None
-        check(L.gga_sparse_conv_wgrad_planes(F._p(x), cin, F._p(gy), cout, F._p(nbr), n_rows, kvol, cin, cout, F._p(gw),
-                                             2 if two else 3, F._p(x_amax) if two else None, F._p(g_amax) if two else None,
-                                             F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_split')
-    else:
-        check(L.gga_sparse_conv_wgrad(F._p(x), F._p(gy), F._p(nbr), n_rows, kvol, cin, cout, F._p(gw), F._stream()),
-              'gga_sparse_conv_wgrad')
+    ws = F._workspace('sp_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout), x.device)
+    two = x_amax is not None and g_amax is not None
+    check(L.gga_sparse_conv_wgrad_planes(F._p(x), cin, F._p(gy), cout, F._p(nbr), n_rows, kvol, cin, cout, F._p(gw),
+                                         2 if two else 3, F._p(x_amax) if two else None, F._p(g_amax) if two else None,
+                                         F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_planes')
     return gw
 
 
@@ -430,13 +412,13 @@ class _SparseConvFn(torch.autograd.Function):
         kvol = rb.nbr.shape[0]
         cin, cout = w.shape[-2], w.shape[-1]
         y = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-        two = SPLIT_BF16 and planes() == 2
+        two = planes() == 2
         x_amax = amax_bits(feats) if two else None
-        banked = SPLIT_BF16 and cout <= 128 and w.data_ptr() == weight.data_ptr()      # the parameter itself: its operands live in the weight bank
+        banked = cout <= 128 and w.data_ptr() == weight.data_ptr()      # the parameter itself: its operands live in the weight bank
         w_amax = amax_bits(w.detach()) if two and not banked else None
-        # the per-channel sums of y for the BatchNorm that follows (split-plane kernels; widths the fused BatchNorm takes)
+        # the per-channel sums of y for the BatchNorm that follows (widths the fused BatchNorm takes)
         stats = None
-        if SPLIT_BF16 and cout % 4 == 0 and cout <= 128 and n_out >= 1:
+        if cout % 4 == 0 and cout <= 128 and n_out >= 1:
             stats = torch.empty((int(_lib.lib().gga_sparse_conv_apply_tiles(n_out)), 2, cout), dtype=torch.float64, device=feats.device)
         if banked:
             from . import dense_conv, weight_bank
@@ -450,7 +432,7 @@ class _SparseConvFn(torch.autograd.Function):
         ctx.rb, ctx.rb_t, ctx.amax, ctx.banked = rb, rb_t, (x_amax, w_amax), banked
         # feats = relu(bn(.)) with this convolution as its consumer: the backward-data pass then does that BatchNorm's reduce
         from . import dense_conv
-        ctx.bn_src = dense_conv.bn_source(feats, cin) if (SPLIT_BF16 and cin % 4 == 0) else None
+        ctx.bn_src = dense_conv.bn_source(feats, cin) if cin % 4 == 0 else None
         if stats is None:
             stats = torch.empty(0, dtype=torch.float64, device=feats.device)
         ctx.mark_non_differentiable(stats)

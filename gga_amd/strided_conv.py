@@ -4,11 +4,11 @@ the repo's own matrix kernels: forward, backward-data and weight gradient.
 
 Over the pixel rows of a channels-last image all of them are gather-GEMMs ``y[row] = sum_k x[map[k][row]] W[k]``
 with an ARITHMETIC rule book - exactly what the sparse-convolution kernels compute from a hashed one
-(``gga_sparse_conv_apply_split`` / ``gga_sparse_conv_wgrad_split``: fp32 as six bf16 partial products,
+(``gga_sparse_conv_apply_stats`` / ``gga_sparse_conv_wgrad_planes``: fp32 carried by operand planes,
 deterministic weight gradient). The rule books depend on the shape only and are built once per
 (batch, map size, kernel, stride, padding); rows are visited grouped by their set of valid taps, so a transposed
 convolution's output rows run the one tap of their phase and border rows skip the padding taps.
-Channel widths above 128 run as 128-wide column blocks (``*_strided`` entry points).
+Channel widths above 128 run as 128-wide column blocks (the row strides of those entry points).
 """
 import torch
 from torch import nn
@@ -115,11 +115,11 @@ def _apply(x_rows, m, mask, perm, w_kio, n_rows, x_amax=None, w_amax=None, want_
         else:
             wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, c1 - c0) // 2, dtype=torch.int16, device=y.device)
             check(L.gga_sparse_pack_weight_planes(F._p(w_kio[:, :, c0:c1].contiguous()), kvol, cin, c1 - c0, 0, planes, F._p(w_amax),
-                                                  F._p(wp), F._stream()), 'gga_sparse_pack_weight_split')
+                                                  F._p(wp), F._stream()), 'gga_sparse_pack_weight_planes')
         st = torch.empty((tiles, 2, c1 - c0), dtype=torch.float64, device=y.device) if want_stats else None
         check(L.gga_sparse_conv_apply_stats(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin,
                                             c1 - c0, 0, y.data_ptr() + 4 * c0, cout, planes, F._p(x_amax), F._p(w_amax),
-                                            F._p(st), F._stream()), 'gga_sparse_conv_apply_split_strided')
+                                            F._p(st), F._stream()), 'gga_sparse_conv_apply_stats')
         if want_stats:
             parts.append(st)
     if want_stats:
@@ -147,7 +147,7 @@ def _wgrad(x_rows, g_rows, m, n_rows, x_amax=None, g_amax=None):
             ws = F._workspace('sp_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, i1 - i0, o1 - o0), gw.device)
             check(L.gga_sparse_conv_wgrad_planes(x_rows.data_ptr() + 4 * i0, cin, g_rows.data_ptr() + 4 * o0, cout, F._p(m),
                                                  n_rows, kvol, i1 - i0, o1 - o0, F._p(part), planes, F._p(x_amax), F._p(g_amax),
-                                                 F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_split_strided')
+                                                 F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_planes')
             if not whole:
                 gw[:, i0:i1, o0:o1] = part
     return gw

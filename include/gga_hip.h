@@ -50,10 +50,10 @@ int gga_abi_version(void);
  * (see the site list). Thread-safe; one session per site at a time. */
 enum {
     GGA_TIME_SCATTER_FWD = 0,   /* gga_pillar_scatter_fwd: NHWC fill [+ map] + rows, NCHW canvas kernel */
-    GGA_TIME_DENSE_CONV = 1,    /* gga_dense_conv3x3*: key = GGA_TIMING_CONV_KEY(cin, cout, H*W) */
-    GGA_TIME_SPARSE_CONV = 2,   /* gga_sparse_conv_apply[_split]: key = GGA_TIMING_CONV_KEY(cin, cout, 0); gga_sparse_conv_apply_halo: (cin, cout, kvol) */
-    GGA_TIME_SPARSE_WGRAD = 3,  /* gga_sparse_conv_wgrad: same key */
-    GGA_TIME_DENSE_WGRAD = 4,   /* gga_dense_wgrad3x3: key as GGA_TIME_DENSE_CONV */
+    GGA_TIME_DENSE_CONV = 1,    /* gga_dense_conv3x3_bn_bwd: key = GGA_TIMING_CONV_KEY(cin, cout, H*W) */
+    GGA_TIME_SPARSE_CONV = 2,   /* gga_sparse_conv_apply_stats / _bn_bwd: key = GGA_TIMING_CONV_KEY(cin, cout, 0); gga_sparse_conv_apply_halo: (cin, cout, kvol) */
+    GGA_TIME_SPARSE_WGRAD = 3,  /* gga_sparse_conv_wgrad_planes: key = GGA_TIMING_CONV_KEY(cin, cout, 0) */
+    GGA_TIME_DENSE_WGRAD = 4,   /* gga_dense_wgrad3x3_block_amax: key as GGA_TIME_DENSE_CONV */
     GGA_TIME_SITES = 5
 };
 #define GGA_TIMING_CONV_KEY(cin, cout, hw) \
@@ -228,7 +228,7 @@ int gga_sparse_bev_nhwc_bwd(const float* grad_out, const int32_t* coors, int64_t
  * backward of the first SECOND convolution (second.py:49-57 applied to the canvas of
  * pillar_scatter.py:58-102) runs on the pillars only: its input gradient is needed just at the
  * occupied cells (all the scatter's backward reads) and its weight gradient only sees non-zero
- * input there - gga_sparse_conv_apply[_split] / gga_sparse_conv_wgrad with this map, the
+ * input there - gga_sparse_conv_apply_stats / gga_sparse_conv_wgrad_planes with this map, the
  * output gradient as `x` (rows = output cells) and the pillar features as the other operand. */
 int gga_pillar_conv_map(const int32_t* coors, int64_t m, const int32_t* num_valid, int batch, int ny, int nx,
                         int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int32_t* map,
@@ -276,7 +276,7 @@ int gga_sparse_rulebook(const int32_t* out_coors, int64_t n_out, const int32_t* 
  * tiles whose rows use the same kernel offsets; the conv kernel skips the others. */
 int gga_sparse_rowmask(const int32_t* map, int64_t n_rows, int kvol, uint32_t* mask, void* stream);
 /* order[i] = the row with the i-th smallest mask, rows with equal masks in row order (a stable sort of the int32 masks: the
- * processing order gga_sparse_conv_apply_split takes as `perm`; replaces the framework's stable sort, sparse.py). kvol <= 32
+ * processing order gga_sparse_conv_apply_stats takes as `perm`; replaces the framework's stable sort, sparse.py). kvol <= 32
  * mask bits take part; masks are compared as signed 32-bit values when kvol == 32. workspace: device memory of
  * gga_sparse_mask_order_workspace_bytes(n_rows) bytes. */
 /* order[i] = the row with the i-th smallest Z-order key (sample, then the bit-interleaved (z, y, x)) of coors [n_rows][4] =
@@ -289,79 +289,38 @@ size_t gga_sparse_mask_order_workspace_bytes(int64_t n_rows);
 int gga_sparse_mask_order(const uint32_t* mask, int64_t n_rows, int kvol, int32_t* order, void* workspace,
                           size_t workspace_bytes, void* stream);
 
-/* Weights in the MFMA fragment order the conv kernel stages through LDS (one 16-byte copy per
- * thread instead of a transposing scatter): packed[k][chunk][lane][g][t][j] =
- * W[k][chunk*32 + 2*(4g+j) + lane/32][t*32 + lane%32], zero beyond cin/cout, with
- * t < (cout<=32 ? 1 : cout<=64 ? 2 : 4). `weight` is [kvol,cin,cout] (transpose 0) or
- * [kvol,cout,cin] (transpose 1: the forward weight of a cout->cin conv, for its backward-data
- * pass). Replaces the weight handling inside mmcv's indice_conv (sparse_block.py:9-20 call sites). */
-size_t gga_sparse_packed_weight_bytes(int kvol, int cin, int cout);
-int gga_sparse_pack_weight(const float* weight, int kvol, int cin, int cout, int transpose, float* packed,
-                           void* stream);
-
-/* y[r,:] = sum_k x[map[kk][r],:] @ W[k], kk = flip ? kvol-1-k : k, W given as
- * gga_sparse_pack_weight(.., cin, cout, ..).
- *   forward        : map = nbr,   flip 0
- *   backward-data  : x = grad_out, map = nbr_t (or nbr with flip 1 for SubM), W packed with
- *                    transpose 1, cin/cout swapped
- * perm (optional, [n_rows]): processing order of the rows (e.g. argsort of the row masks);
- * rowmask (optional, [n_rows]): gga_sparse_rowmask of `map`. Output rows are not permuted. */
-int gga_sparse_conv_apply(const float* x, const int32_t* map, const float* packed_weight, const int32_t* perm,
-                          const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,
-                          float* y, void* stream);
-/* The same convolution with fp32 carried by three bfloat16 planes per operand: a fp32 number is
+/* The gather-GEMM y[r,:] = sum_k x[map[kk][r],:] @ W[k], kk = flip ? kvol-1-k : k, runs on the 16-bit matrix
+ * instructions with fp32 carried by operand planes. Three bfloat16 planes (planes = 3): a fp32 number is
  * the exact sum of three bf16 numbers, so every product is the sum of nine bf16 products, each
  * exact in fp32, accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (1.7x the fp32 MFMA rate on
  * gfx950; error vs float64 not larger than the fp32 MFMA's). The kernels issue six of the nine: the
  * three products of the low planes are together below 2^-23 of the product (one fp32 ulp) and the
- * measured error of a convolution does not change; build with -DX9_NINE for all nine.
- * gga_sparse_pack_weight_split splits
- * and lays out the weights: packed[k][chunk][plane][col][32 ch] bf16; arguments as for
- * gga_sparse_pack_weight / gga_sparse_conv_apply. */
+ * measured error of a convolution does not change; build with -DX9_NINE for all nine. Two fp16 planes (planes = 2):
+ * see gga_absmax_bits below. The entry points (gga_sparse_pack_weight_planes, gga_sparse_conv_apply_stats / _bn_bwd,
+ * gga_sparse_conv_wgrad_planes) are declared there, next to the dense kernels that share the arithmetic.
+ * gga_sparse_split_weight_bytes: size of a packed weight operand, packed[k][chunk][plane][col][32 ch] 16-bit elements,
+ * zero beyond cin / cout (sized for three planes whatever `planes` the packing call is given; cout <= 128, else 0).
+ * Replaces the weight handling inside mmcv's indice_conv (sparse_block.py:9-20 call sites). */
 size_t gga_sparse_split_weight_bytes(int kvol, int cin, int cout);
-int gga_sparse_pack_weight_split(const float* weight, int kvol, int cin, int cout, int transpose, void* packed,
-                                 void* stream);
-int gga_sparse_conv_apply_split(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,
-                                float* y, void* stream);
-/* The same with y a column block of a wider [n_rows, y_row_stride] matrix. With an arithmetic rule book over the
- * pixels of a channels-last image this gather-GEMM is also the stride-2 3x3 convolution of a SECOND stage
- * (mmdet3d/models/backbones/second.py:49-57) and the kernel = stride transposed convolution of SECONDFPN
- * (necks/second_fpn.py:52-69), forward and backward-data (gga_amd/strided_conv.py). */
-int gga_sparse_conv_apply_split_strided(const float* x, const int32_t* map, const void* split_weight,
-                                        const int32_t* perm, const uint32_t* rowmask, int64_t n_rows, int kvol, int cin,
-                                        int cout, int flip, float* y, int64_t y_row_stride, void* stream);
 
-/* Dense 3x3 / stride 1 / zero-pad 1 convolution of a channels-last image on the same bf16x9
- * path: x [B,H,W,cin] (cin a multiple of 32), y [B,H,W,cout] (cout 64 or 128), split_weight =
- * gga_sparse_pack_weight_split(weight [9][cin][cout] tap-major (ky*3+kx), kvol 9). The SECOND
+/* Dense 3x3 / stride 1 / zero-pad 1 convolution of a channels-last image on the same plane arithmetic
+ * (gga_dense_conv3x3_bn_bwd, gga_dense_conv3x3_levels below): x [B,H,W,cin] (cin a multiple of 32), y [B,H,W,cout]
+ * (cout 64 or 128), split_weight from gga_dense_conv3x3_pack_planes. The SECOND
  * block convolutions and the first convolution of every head branch (backbones/second.py:58-63,
  * dense_heads/centerpoint_head.py:58-68); backward-data is the same call on grad_y with the
  * taps reversed and the channel roles swapped. Each workgroup fetches its input halo once per
- * 32-channel chunk, splits it into the three bf16 planes on the way into LDS and reuses it for
- * all nine taps. */
-/* The same convolution that also leaves the batch statistics of its output for the BatchNorm
- * that follows: stats [gga_dense_conv3x3_tiles(B,H,W,cout)][2][cout] f64 = per-tile sum and sum of
- * squares per channel - the `partials` of gga_bn_relu_fwd_partials / gga_bn_stats_partials, so
- * the BatchNorm does not read y a second time for its reduction. stats may be NULL. */
-int64_t gga_dense_conv3x3_tiles(int B, int H, int W, int cout);   /* rows of `stats` of a three-plane launch (= ..._tiles_planes(.., 3)) */
-/* rows of `stats` for a launch of this arithmetic: the two-plane launches run the producer / consumer form
- * (dense_conv_ws.hip: tiles of 8 x 32 pixels at 128 output channels, 16 x 32 at 64; GGA_DC_WS=0 puts them back on the
- * lock-step kernel), the three-plane launches tiles of 8 or 16 rows by shape. */
-int64_t gga_dense_conv3x3_tiles_planes(int B, int H, int W, int cout, int planes);
-int64_t gga_dense_conv3x3_stat_rows(int B, int H, int W, int cout, int planes, int n_slices);   /* rows of `stats` (per slice): one per tile (lock-step kernel) or one per workgroup (producer / consumer form, <= 256) */
+ * 32-channel chunk, splits it into the operand planes on the way into LDS and reuses it for
+ * all nine taps.
+ * The convolution can also leave the batch statistics of its output for the BatchNorm
+ * that follows: stats [gga_dense_conv3x3_stat_rows(B,H,W,cout,planes,1)][2][cout] f64 = partial sums and sums of
+ * squares per channel - the `partials` of gga_bn_relu_fwd_ex / gga_bn_stats_partials, so
+ * the BatchNorm does not read y a second time for its reduction.
+ * Rows of `stats` (per slice) for a launch of this arithmetic over n_slices 128-channel output slices: the two-plane launches
+ * run the producer / consumer form (dense_conv_ws.hip: tiles of 8 x 32 pixels at 128 output channels, 16 x 32 at 64, one row
+ * per workgroup, <= 256; GGA_DC_WS=0 puts them back on the lock-step kernel), the three-plane launches the lock-step kernel
+ * (tiles of 8 or 16 rows by shape, one row per tile). H, W are those of the tile space (swapped for a transposed launch). */
+int64_t gga_dense_conv3x3_stat_rows(int B, int H, int W, int cout, int planes, int n_slices);
 int gga_dense_conv3x3_tile_rows(int B, int H, int W, int cout, int planes);      /* 8 or 16: the tile_rows to hand gga_dense_conv3x3_levels for slices of this shape */
-int gga_dense_conv3x3_stats(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                            float* y, double* stats, void* stream);
-/* Weight gradient of the same convolution, bf16x9 with the pixel index as the GEMM's K (transposed
- * LDS reads): x [B,H,W,cin], grad_y [B,H,W,cout] channels-last, cin and cout multiples of 64;
- * grad_weight is written as a [cout, cin, 3, 3] tensor with the given element strides
- * (overwritten, not accumulated). Replaces the convolution-backward-weights call behind autograd
- * for backbones/second.py:58-63 and dense_heads/centerpoint_head.py:58-68,120-121. */
-size_t gga_dense_wgrad3x3_workspace_bytes(int B, int H, int W, int cin, int cout);
-int gga_dense_wgrad3x3(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
-                       float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                       int64_t stride_kx, int transposed, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two-fp16-plane arithmetic for the dense kernels (the default of gga_amd/dense_conv.py): each operand is scaled by
  * the power of two that puts its largest finite magnitude into [2^14, 2^15) and split into two round-to-nearest fp16
@@ -395,17 +354,29 @@ typedef struct {
 int64_t gga_absmax_table_blocks(int64_t n);
 int gga_absmax_table(const GgaAmaxEntry* table_device, int n_entries, int64_t n_blocks, uint32_t* slots, int n_slots, void* stream);
 int gga_pack_weights_table(const GgaPackEntry* table_device, int n_entries, int64_t total, int planes, void* stream);
-/* the gather-GEMM kernels (sparse, strided and transposed convolutions) in the same two forms */
+/* The gather-GEMM kernels (sparse, strided and transposed convolutions) in the same two forms.
+ * gga_sparse_pack_weight_planes splits the weights into planes and lays them out as the kernel stages them:
+ * `weight` is [kvol,cin,cout] (transpose 0) or [kvol,cout,cin] (transpose 1: the forward weight of a cout->cin conv, for
+ * its backward-data pass); `packed`: gga_sparse_split_weight_bytes(kvol, cin, cout) bytes; amax_weight: the weight's absmax
+ * bits (planes == 2; NULL with planes == 3). cout <= 128. */
 int gga_sparse_pack_weight_planes(const float* weight, int kvol, int cin, int cout, int transpose, int planes,
                                   const uint32_t* amax_weight, void* packed, void* stream);
-int gga_sparse_conv_apply_planes(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                 const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip, float* y,
-                                 int64_t y_row_stride, int planes, const uint32_t* amax_x, const uint32_t* amax_weight,
-                                 void* stream);
-/* gga_sparse_conv_apply_planes that also leaves the per-channel sums of its output for the BatchNorm that follows
+/* y[r,:] = sum_k x[map[kk][r],:] @ W[k], kk = flip ? kvol-1-k : k, W given as
+ * gga_sparse_pack_weight_planes(.., cin, cout, .., planes, ..); y is a column block of a [n_rows, y_row_stride] matrix
+ * (y_row_stride = cout: a plain [n_rows, cout] result).
+ *   forward        : map = nbr,   flip 0
+ *   backward-data  : x = grad_out, map = nbr_t (or nbr with flip 1 for SubM), W packed with
+ *                    transpose 1, cin/cout swapped
+ * perm (optional, [n_rows]): processing order of the rows (e.g. gga_sparse_mask_order of the row masks);
+ * rowmask (optional, [n_rows]): gga_sparse_rowmask of `map`. Output rows are not permuted. amax_x, amax_weight: the operands'
+ * absmax bits (planes == 2; NULL with planes == 3). cout <= 128; any cin (a multiple of 4 gathers 16 bytes per load).
+ * With an arithmetic rule book over the pixels of a channels-last image this gather-GEMM is also the stride-2 3x3 convolution
+ * of a SECOND stage (mmdet3d/models/backbones/second.py:49-57) and the kernel = stride transposed convolution of SECONDFPN
+ * (necks/second_fpn.py:52-69), forward and backward-data (gga_amd/strided_conv.py).
+ * stats (NULL: none) receives the per-channel sums of the output for the BatchNorm that follows
  * (ops/sparse_block.py:117-134, backbones/second.py:49-57, necks/second_fpn.py:52-69: conv -> BN -> ReLU): stats
  * [gga_sparse_conv_apply_tiles(n_rows)][2][cout] f64 = per workgroup of 128 rows the sum and the sum of squares - the
- * partials gga_bn_relu_fwd_ex takes. stats == NULL: exactly gga_sparse_conv_apply_planes. */
+ * partials gga_bn_relu_fwd_ex takes. */
 int64_t gga_sparse_conv_apply_tiles(int64_t n_rows);
 int gga_sparse_conv_apply_stats(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
                                 const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip, float* y,
@@ -443,91 +414,11 @@ int gga_sparse_conv_apply_halo(const float* x, const void* split_weight, const i
                                float* y, int64_t y_row_stride, int planes, const uint32_t* amax_x, const uint32_t* amax_weight,
                                double* stats, const float* bn_x, int64_t bn_x_row_stride, const float* bn_gamma,
                                const float* bn_beta, const float* bn_mean, const float* bn_invstd, void* stream);
-int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride, const float* grad_out, int64_t grad_out_row_stride,
-                                 const int32_t* nbr, int64_t n_rows, int kvol, int cin, int cout, float* grad_weight,
-                                 int planes, const uint32_t* amax_x, const uint32_t* amax_grad_out, void* workspace,
-                                 size_t workspace_bytes, void* stream);
-int gga_dense_conv3x3_pack_planes(const float* weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                                  int64_t stride_kx, int cin, int cout, int backward, int planes,
-                                  const uint32_t* amax_weight, void* packed, void* stream);
-int gga_dense_conv3x3_planes(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout, float* y,
-                             int64_t y_pixel_stride, int transposed, double* stats, int planes, const uint32_t* amax_x,
-                             const uint32_t* amax_weight, void* stream);
-/* gga_dense_conv3x3_planes run as the backward-data convolution that produces the gradient of z = relu(bn(bn_x)) (the
- * conv -> BatchNorm -> ReLU -> conv chains of backbones/second.py:46-63): the epilogue masks the tile with the ReLU
- * (recomputed from bn_x and gamma, beta, mean, invstd of the `cout` channels of this launch, exactly as the forward
- * pass decided it) before it is stored, and `stats` ([tiles][2][cout] f64, required) receives the per-tile sums of
- * g and g * xhat instead - the reduce pass of that BatchNorm's backward, which gga_bn_relu_bwd_partials then skips.
- * bn_x == NULL: exactly gga_dense_conv3x3_planes. */
-/* gga_dense_conv3x3_planes over several images of different sizes in ONE launch (the tower convolutions of an FPN head,
- * anchor_free_mono3d_head.py:160-250, share their weights over the levels, and the small levels alone leave most of the
- * chip idle): entry e convolves x[e] [B, heights[e], widths[e], cin] with split_weight[e] (entries that are output slices of
- * one convolution bring their own operand) into y[e] (pixel stride y_pixel_stride floats). bias (NULL: none): per entry the
- * `cout` bias values of its output channels (NULL entries: none), added in the epilogue - this is also how a single map with
- * a bias is run. tile_rows: 8, or 16 (cout 128 only: the form gga_dense_conv3x3_planes picks for maps with at least 384
- * 16-row tiles - large and small maps go into separate launches); transposed: every entry walks its map transposed (as
- * gga_dense_conv3x3_slice; split_weight packed accordingly); stats (NULL: none): per entry the f64 [tiles][2][cout]
- * BatchNorm sums of its output (gga_dense_conv3x3_stats; tiles of the entry = B * ceil(w / 32) * ceil(h / tile_rows) in its
- * tile space). At most 16 entries. */
-int gga_dense_conv3x3_levels(int n_entries, const float* const* x, const int32_t* heights, const int32_t* widths,
-                             const void* const* split_weight, int B, int cin, int cout, float* const* y, int64_t y_pixel_stride,
-                             int planes, const uint32_t* const* amax_x, const uint32_t* amax_weight, const float* const* bias,
-                             int tile_rows, int transposed, double* const* stats, void* stream);
-int gga_dense_conv3x3_bn_bwd_pays(int B, int H, int W, int cout);   /* 1: the epilogue costs less than the reduce pass (H, W of the tile space); three planes */
-int gga_dense_conv3x3_bn_bwd_pays_planes(int B, int H, int W, int cout, int planes);   /* the same for a launch of this arithmetic (two planes: always) */
-int gga_dense_conv3x3_bn_bwd(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout, float* y,
-                             int64_t y_pixel_stride, int transposed, double* stats, int planes, const uint32_t* amax_x,
-                             const uint32_t* amax_weight, const float* bn_x, int64_t bn_x_pixel_stride, const float* bn_gamma,
-                             const float* bn_beta, const float* bn_mean, const float* bn_invstd, void* stream);
-int gga_dense_wgrad3x3_planes(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
-                              float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                              int64_t stride_kx, int transposed, int planes, const uint32_t* amax_x,
-                              const uint32_t* amax_grad_y, void* workspace, size_t workspace_bytes, void* stream);
-/* The same with the absmax of an operand given per 64-channel block (amax_x[ci / 64], amax_grad_y[co / 64]) when its
- * *_per_block flag is set: dW[ci][co] only sees channel ci of x and channel co of grad_y, so on two fp16 planes a block whose
- * values lie far below the tensor's largest magnitude keeps its own 22 significant bits (the 960-channel gradient of the 15 head
- * branches: regression branches with a few object cells beside the heat-map branches).
- * One image of an operand (H * W * max(cin, cout) floats) must stay below 2 GiB: the kernel addresses a staged piece by a 32-bit
- * offset inside its image row beside a scalar row base (GGA_ERR_* otherwise). */
-int gga_dense_wgrad3x3_block_amax(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
-                                  float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                                  int64_t stride_kx, int transposed, int planes, const uint32_t* amax_x, int amax_x_per_block,
-                                  const uint32_t* amax_grad_y, int amax_grad_y_per_block, void* workspace,
-                                  size_t workspace_bytes, void* stream);
-
-/* The same with y as a 64- or 128-channel slice of a wider channels-last tensor: pixel p of the
- * result starts at y + p * y_pixel_stride (floats). A convolution with more output channels runs as
- * one call per slice (each with the weights of its slice): the backward-data of the 384 -> 64
- * shared convolution of the head (centerpoint_head.py:255-262) is three 64 -> 128 calls. */
-/* transposed != 0: the 8 x 32-pixel tiles run 32 pixels along H instead of W (maps whose width is a
- * poor multiple of 32, e.g. 124 x 108 or 62 x 54); split_weight must then be packed with the ky / kx
- * strides swapped, and stats holds gga_dense_conv3x3_tiles(B, W, H, cout) rows. Results are identical. */
-int gga_dense_conv3x3_slice(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout,
-                            float* y, int64_t y_pixel_stride, int transposed, double* stats, void* stream);
-
-/* split_weight for gga_dense_conv3x3 straight from the framework's [cout, cin, 3, 3] parameter with
- * arbitrary element strides (channels-last parameters included): size
- * gga_sparse_split_weight_bytes(9, cin, cout); backward != 0 packs the operand of the
- * backward-data convolution (a cout -> cin convolution: size ..._bytes(9, cout, cin)). */
-int gga_dense_conv3x3_pack(const float* weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
-                           int64_t stride_kx, int cin, int cout, int backward, void* packed, void* stream);
-int gga_dense_conv3x3(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout, float* y,
-                      void* stream);
-
-/* grad_weight [kvol,cin,cout] = sum_r x[nbr[k][r]]^T grad_out[r]  (zero-filled here).
- * Native fp32 MFMA with one float atomicAdd per weight and 2048-row chunk: the summation order of
- * the chunks (not the values summed) varies from run to run. */
-int gga_sparse_conv_wgrad(const float* x, const float* grad_out, const int32_t* nbr, int64_t n_rows,
-                          int kvol, int cin, int cout, float* grad_weight, void* stream);
-/* The same gradient on the bf16 planes (six partial products, as gga_sparse_conv_apply_split) and
+/* grad_weight [kvol,cin,cout] = sum_r x[nbr[k][r]]^T grad_out[r] on the operand planes (overwritten, not accumulated),
  * DETERMINISTIC: pairs are compacted in row order, every workgroup writes its partial sum to
- * workspace [chunks][kvol][CI][CO] and a second kernel adds the chunks in a fixed order in f64.
- * No atomics; about 1.7x the fp32-MFMA form at 128 channels. */
-size_t gga_sparse_conv_wgrad_workspace_bytes(int64_t n_rows, int kvol, int cin, int cout);
-int gga_sparse_conv_wgrad_split(const float* x, const float* grad_out, const int32_t* nbr, int64_t n_rows,
-                                int kvol, int cin, int cout, float* grad_weight, void* workspace,
-                                size_t workspace_bytes, void* stream);
-/* The same with x / grad_out column blocks (<= 128 wide) of wider matrices: row strides in floats.
+ * workspace [chunks][kvol][CI][CO] (gga_sparse_conv_wgrad_workspace_bytes) and a second kernel adds the chunks in a fixed
+ * order in f64. No atomics. cin, cout <= 128. x / grad_out may be column blocks of wider matrices: row strides in floats
+ * (>= cin / cout). amax_x, amax_grad_out: the operands' absmax bits (planes == 2; NULL with planes == 3).
  * Every x row a rule-book entry names must start below byte 4 GiB of x (32-bit pair offsets; the kernel TRAPS - the stream
  * reports a fault - on a row beyond it: 8 M rows of 128 floats).
  * Non-finite inputs: absent neighbours, tail pairs and (dense weight gradient) pixels outside the image are not selected to zero
@@ -535,9 +426,77 @@ int gga_sparse_conv_wgrad_split(const float* x, const float* grad_out, const int
  * the matrix instructions). With finite tensors that is 0; an Inf / NaN in the substituted element turns that padded contribution
  * into NaN, i.e. a non-finite value in x or grad_out can reach weight-gradient entries it would not reach through a select. The
  * train Runner's range guard reports non-finite operands on its guarded iterations. */
-int gga_sparse_conv_wgrad_split_strided(const float* x, int64_t x_row_stride, const float* grad_out,
-                                        int64_t grad_out_row_stride, const int32_t* nbr, int64_t n_rows, int kvol, int cin,
-                                        int cout, float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
+size_t gga_sparse_conv_wgrad_workspace_bytes(int64_t n_rows, int kvol, int cin, int cout);
+int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride, const float* grad_out, int64_t grad_out_row_stride,
+                                 const int32_t* nbr, int64_t n_rows, int kvol, int cin, int cout, float* grad_weight,
+                                 int planes, const uint32_t* amax_x, const uint32_t* amax_grad_out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* split_weight of the dense 3x3 kernels straight from the framework's [cout, cin, 3, 3] parameter with
+ * arbitrary element strides (channels-last parameters included): size
+ * gga_sparse_split_weight_bytes(9, cin, cout); backward != 0 packs the operand of the
+ * backward-data convolution (a cout -> cin convolution: size ..._bytes(9, cout, cin)). amax_weight: the weight's absmax bits
+ * (planes == 2; NULL with planes == 3). */
+int gga_dense_conv3x3_pack_planes(const float* weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
+                                  int64_t stride_kx, int cin, int cout, int backward, int planes,
+                                  const uint32_t* amax_weight, void* packed, void* stream);
+/* The dense 3x3 convolution (described above): x [B,H,W,cin], split_weight from gga_dense_conv3x3_pack_planes with the same
+ * `planes`, amax_x / amax_weight the operands' absmax bits (planes == 2; NULL with planes == 3), stats NULL or
+ * [gga_dense_conv3x3_stat_rows(..)][2][cout] f64.
+ * y may be a 64- or 128-channel slice of a wider channels-last tensor: pixel p of the
+ * result starts at y + p * y_pixel_stride (floats; cout: a dense result). A convolution with more output channels runs as
+ * one call per slice (each with the weights of its slice): the backward-data of the 384 -> 64
+ * shared convolution of the head (centerpoint_head.py:255-262) is three 64 -> 128 calls.
+ * transposed != 0: the tiles run 32 pixels along H instead of W (maps whose width is a
+ * poor multiple of 32, e.g. 124 x 108 or 62 x 54); split_weight must then be packed with the ky / kx
+ * strides swapped, and stats holds gga_dense_conv3x3_stat_rows(B, W, H, ..) rows. Results are identical.
+ * bn_x != NULL: the call is the backward-data convolution that produces the gradient of z = relu(bn(bn_x)) (the
+ * conv -> BatchNorm -> ReLU -> conv chains of backbones/second.py:46-63): the epilogue masks the tile with the ReLU
+ * (recomputed from bn_x and gamma, beta, mean, invstd of the `cout` channels of this launch, exactly as the forward
+ * pass decided it) before it is stored, and `stats` (required) receives the partial sums of
+ * g and g * xhat instead - the reduce pass of that BatchNorm's backward, which gga_bn_relu_bwd_partials then skips.
+ * gga_dense_conv3x3_bn_bwd_pays_planes: 1 when that epilogue costs less than the reduce pass it replaces for a launch of this
+ * shape (H, W of the tile space) and arithmetic (two planes: always). */
+int gga_dense_conv3x3_bn_bwd_pays_planes(int B, int H, int W, int cout, int planes);
+int gga_dense_conv3x3_bn_bwd_pays(int B, int H, int W, int cout);   /* = ..._pays_planes(.., 3) */
+int gga_dense_conv3x3_bn_bwd(const float* x, const void* split_weight, int B, int H, int W, int cin, int cout, float* y,
+                             int64_t y_pixel_stride, int transposed, double* stats, int planes, const uint32_t* amax_x,
+                             const uint32_t* amax_weight, const float* bn_x, int64_t bn_x_pixel_stride, const float* bn_gamma,
+                             const float* bn_beta, const float* bn_mean, const float* bn_invstd, void* stream);
+/* The same convolution (no BatchNorm epilogue) over several images of different sizes in ONE launch (the tower convolutions of
+ * an FPN head,
+ * anchor_free_mono3d_head.py:160-250, share their weights over the levels, and the small levels alone leave most of the
+ * chip idle): entry e convolves x[e] [B, heights[e], widths[e], cin] with split_weight[e] (entries that are output slices of
+ * one convolution bring their own operand) into y[e] (pixel stride y_pixel_stride floats). bias (NULL: none): per entry the
+ * `cout` bias values of its output channels (NULL entries: none), added in the epilogue - this is also how a single map with
+ * a bias is run. tile_rows: 8, or 16 (cout 128 only: the form gga_dense_conv3x3_bn_bwd picks for maps with at least 384
+ * 16-row tiles - large and small maps go into separate launches); transposed: every entry walks its map transposed (as
+ * in gga_dense_conv3x3_bn_bwd; split_weight packed accordingly); stats (NULL: none): per entry the f64 [tiles][2][cout]
+ * BatchNorm sums of its output (tiles of the entry = B * ceil(w / 32) * ceil(h / tile_rows) in its
+ * tile space). At most 16 entries. */
+int gga_dense_conv3x3_levels(int n_entries, const float* const* x, const int32_t* heights, const int32_t* widths,
+                             const void* const* split_weight, int B, int cin, int cout, float* const* y, int64_t y_pixel_stride,
+                             int planes, const uint32_t* const* amax_x, const uint32_t* amax_weight, const float* const* bias,
+                             int tile_rows, int transposed, double* const* stats, void* stream);
+/* Weight gradient of the dense 3x3 convolution on the operand planes, with the pixel index as the GEMM's K (transposed
+ * LDS reads): x [B,H,W,cin], grad_y [B,H,W,cout] channels-last, cin and cout multiples of 64;
+ * grad_weight is written as a [cout, cin, 3, 3] tensor with the given element strides
+ * (overwritten, not accumulated); transposed != 0 walks the maps transposed, as the forward kernel does (the same
+ * gradient up to the order of summation).
+ * Replaces the convolution-backward-weights call behind autograd
+ * for backbones/second.py:58-63 and dense_heads/centerpoint_head.py:58-68,120-121.
+ * amax_x, amax_grad_y: the operands' absmax bits (planes == 2; NULL with planes == 3) - one value per tensor, or, when the
+ * operand's *_per_block flag is set, one per 64-channel block (amax_x[ci / 64], amax_grad_y[co / 64]): dW[ci][co] only sees
+ * channel ci of x and channel co of grad_y, so on two fp16 planes a block whose
+ * values lie far below the tensor's largest magnitude keeps its own 22 significant bits (the 960-channel gradient of the 15 head
+ * branches: regression branches with a few object cells beside the heat-map branches).
+ * One image of an operand (H * W * max(cin, cout) floats) must stay below 2 GiB: the kernel addresses a staged piece by a 32-bit
+ * offset inside its image row beside a scalar row base (GGA_ERR_* otherwise). */
+size_t gga_dense_wgrad3x3_workspace_bytes(int B, int H, int W, int cin, int cout);
+int gga_dense_wgrad3x3_block_amax(const float* x, const float* grad_y, int B, int H, int W, int cin, int cout,
+                                  float* grad_weight, int64_t stride_co, int64_t stride_ci, int64_t stride_ky,
+                                  int64_t stride_kx, int transposed, int planes, const uint32_t* amax_x, int amax_x_per_block,
+                                  const uint32_t* amax_grad_y, int amax_grad_y_per_block, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a4/a5 (elementwise part). Fused training-mode BatchNorm (+ residual add)   */
@@ -550,44 +509,31 @@ int gga_sparse_conv_wgrad_split_strided(const float* x, int64_t x_row_stride, co
 /* ------------------------------------------------------------------------- */
 size_t gga_bn_relu_workspace_bytes(int64_t rows, int channels);
 size_t gga_bn_relu_mask_bytes(int64_t rows, int channels);   /* 1 bit / element ReLU sign */
-/* saved [2*channels] f32 receives mean / invstd; running stats are updated when training. */
-int gga_bn_relu_fwd(const float* x, const float* residual, const float* gamma, const float* beta,
-                    float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                    float momentum, int training, int relu, float* y, void* mask_bits, float* saved,
-                    void* workspace, size_t workspace_bytes, void* stream);
-/* batch-statistics backward: grad_x, optional grad_residual (= masked grad_y), grad_gamma/beta.
- * relu: 0 none, 1 mask_bits = the bits written by the forward, 2 mask_bits = scale_shift of
- * gga_bn_stats (mask recomputed from x). */
-int gga_bn_relu_bwd(const float* grad_y, const float* x, const void* mask_bits, const float* gamma,
-                    const float* saved, int64_t rows, int channels, int relu, float* grad_x,
-                    float* grad_residual, float* grad_gamma, float* grad_beta, void* workspace,
-                    size_t workspace_bytes, void* stream);
-/* The same with y (forward) / grad_y (backward) as a column block of a wider row-major matrix:
- * row r of the operand starts at y + r * y_row_stride (floats; a multiple of 4, >= channels; the
- * pointer 16 B aligned). The three SECONDFPN branches write their BN+ReLU output straight into
- * their channel slice of the concatenated map and read their slice of its gradient in place
- * (necks/second_fpn.py:85-91: torch.cat of the deblock outputs) - no concat copy, no split copy. */
-int gga_bn_relu_fwd_strided(const float* x, const float* residual, const float* gamma, const float* beta,
-                            float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                            float momentum, int training, int relu, float* y, int64_t y_row_stride,
-                            void* mask_bits, float* saved, void* workspace, size_t workspace_bytes, void* stream);
-int gga_bn_relu_bwd_strided(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
-                            const float* gamma, const float* saved, int64_t rows, int channels, int relu,
-                            float* grad_x, float* grad_residual, float* grad_gamma, float* grad_beta,
-                            void* workspace, size_t workspace_bytes, void* stream);
-
 /* Batch statistics only (no normalised output): saved [2*channels] = mean / invstd, scale_shift
  * [2*channels] = gamma*invstd, beta - mean*gamma*invstd; running stats updated when training. For
  * consumers that apply the affine + ReLU themselves while loading (gga_head_conv3x3_* with
  * in_scale_shift), so the normalised activation is never written. Its backward is
- * gga_bn_relu_bwd[_strided] with relu = 2 and mask_bits = scale_shift: the ReLU mask is
+ * gga_bn_relu_bwd_ex with relu = 2 and mask_bits = scale_shift: the ReLU mask is
  * recomputed as fma(x, scale, shift) > 0 instead of read from stored bits. */
-/* Supersets of the calls above with one more output: the bits of the largest finite magnitude written (y /
+int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                 int64_t rows, int channels, float eps, float momentum, int training, float* saved,
+                 float* scale_shift, void* workspace, size_t workspace_bytes, void* stream);
+/* Forward: saved [2*channels] f32 receives mean / invstd; running stats are updated when training. relu != 0 also writes
+ * mask_bits (gga_bn_relu_mask_bytes). y may be a column block of a wider row-major matrix:
+ * row r starts at y + r * y_row_stride (floats; a multiple of 4, >= channels; the
+ * pointer 16 B aligned; channels: a dense result). The three SECONDFPN branches write their BN+ReLU output straight into
+ * their channel slice of the concatenated map and read their slice of its gradient in place
+ * (necks/second_fpn.py:85-91: torch.cat of the deblock outputs) - no concat copy, no split copy.
+ * partials != NULL: training-mode statistics from per-channel sums already reduced by the producer of x: partials
+ * [n_partials][2][channels] f64 (sum, sum of squares over disjoint row sets that together cover all `rows`), e.g. the `stats`
+ * of gga_dense_conv3x3_bn_bwd or gga_sparse_conv_apply_stats; the reduce pass over x is skipped.
+ * Backward (batch statistics): grad_x, optional grad_residual (= masked grad_y), grad_gamma/beta; grad_y strided like y.
+ * relu: 0 none, 1 mask_bits = the bits written by the forward, 2 mask_bits = scale_shift of
+ * gga_bn_stats (mask recomputed from x). training = 0 is the backward of an evaluation-mode forward (running statistics,
+ * e.g. a frozen backbone with norm_eval): grad_x = gamma * invstd * g, grad_gamma / grad_beta as in training mode.
+ * amax_y / amax_grad_x (NULL: none): the bits of the largest finite magnitude written (y /
  * grad_x), max-combined into *amax (the caller zeroes it; several calls may share it) - what the two-fp16-plane
- * convolution kernels that consume the tensor derive their scale from, without a pass of their own.
- * gga_bn_relu_fwd_ex: partials != NULL = the producer's per-channel sums (as gga_bn_relu_fwd_partials).
- * gga_bn_relu_bwd_ex: training = 0 is the backward of an evaluation-mode forward (running statistics, e.g. a frozen
- * backbone with norm_eval): grad_x = gamma * invstd * g, grad_gamma / grad_beta as in training mode. */
+ * convolution kernels that consume the tensor derive their scale from, without a pass of their own. */
 int gga_bn_relu_fwd_ex(const float* x, const float* residual, const float* gamma, const float* beta,
                        float* running_mean, float* running_var, int64_t rows, int channels, float eps, float momentum,
                        int training, int relu, float* y, int64_t y_row_stride, void* mask_bits, float* saved,
@@ -621,19 +567,9 @@ int gga_gn_relu_bwd(const float* grad_y, const float* x, const float* gamma, con
                     int B, int64_t rows_per_sample, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
                     float* grad_beta, uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream);
 
-int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                 int64_t rows, int channels, float eps, float momentum, int training, float* saved,
-                 float* scale_shift, void* workspace, size_t workspace_bytes, void* stream);
-
-/* Training-mode forward / statistics with the per-channel sums already reduced by the producer of
+/* gga_bn_stats in training mode with the per-channel sums already reduced by the producer of
  * x: partials [n_partials][2][channels] f64 (sum, sum of squares over disjoint row sets that
- * together cover all `rows`), e.g. from gga_dense_conv3x3_stats. Otherwise as
- * gga_bn_relu_fwd_strided / gga_bn_stats. */
-int gga_bn_relu_fwd_partials(const float* x, const float* residual, const float* gamma, const float* beta,
-                             float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                             float momentum, int relu, float* y, int64_t y_row_stride, void* mask_bits,
-                             float* saved, const double* partials, int n_partials, void* workspace,
-                             size_t workspace_bytes, void* stream);
+ * together cover all `rows`), as for gga_bn_relu_fwd_ex. */
 int gga_bn_stats_partials(const float* gamma, const float* beta, float* running_mean, float* running_var,
                           int64_t rows, int channels, float eps, float momentum, float* saved, float* scale_shift,
                           const double* partials, int n_partials, void* stream);

@@ -26,6 +26,20 @@ def test_library_builds_and_exports_header_symbols():
     assert set(names) == set(_lib.SIGNATURES), 'python binding and header disagree'
 
 
+def test_every_bound_entry_point_has_a_caller():
+    # an entry point nothing calls is deleted, not kept as a forwarder to its successor
+    import glob
+    elsewhere = {
+        'gga_last_error', 'gga_abi_version', 'gga_timing_begin', 'gga_timing_collect',      # called inside gga_amd/_lib.py
+        'gga_dense_conv3x3_bn_bwd_pays',      # tests/test_kernels_gpu.py binds it to a local name before calling it
+    }
+    files = [f for pat in ('gga_amd/*.py', 'tests/*.py', 'bench.py', '__graft_entry__.py', 'tools/*.py')
+             for f in glob.glob(os.path.join(REPO, pat)) if not f.endswith(os.path.join('gga_amd', '_lib.py'))]
+    text = '\n'.join(open(f).read() for f in files)
+    unused = [n for n in _lib.SIGNATURES if n not in elsewhere and not re.search(r'\.' + n + r'\s*[(,)]', text)]
+    assert not unused, f'bound in _lib.SIGNATURES but called nowhere: {unused}'
+
+
 def test_abi_version_and_grid_size():
     L = _lib.lib()
     assert L.gga_abi_version() == _lib.ABI_VERSION

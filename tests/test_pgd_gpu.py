@@ -264,7 +264,7 @@ def test_wide_head_with_groupnorm_and_dcn_runs_the_hip_kernels_and_matches_the_r
     last convolution of both towers (configs/_base_/models/pgd.py towers) - against a run of the reference's PGDHead with the
     same (name-derived) weights and features (tests/golden/pgd_head_wide.npz; DCNv2 there = oracle/dcn_ref, parity unpinned):
     forward, and the gradients of a fixed linear functional of the outputs w.r.t. the features and the parameters. The
-    forward and backward must go through gga_dense_conv3x3 (tower and branch convolutions), gga_gn_relu_* and the DCN
+    forward and backward must go through gga_dense_conv3x3_* (tower and branch convolutions), gga_gn_relu_* and the DCN
     sampling kernels - counted."""
     import sys
     sys.path.insert(0, os.path.join(REPO, 'tools_dev'))

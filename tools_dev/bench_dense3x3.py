@@ -1,4 +1,4 @@
-"""Dense 3x3 bf16x9 kernel (gga_dense_conv3x3) against MIOpen's fp32 convolution: values and time
+"""Dense 3x3 bf16x9 kernel (gga_dense_conv3x3_bn_bwd) against MIOpen's fp32 convolution: values and time
 at the shapes of the BEV trunk / head branches. A 1 GiB memset runs between timed launches."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))

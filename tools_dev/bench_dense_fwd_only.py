@@ -1,4 +1,4 @@
-"""Forward time of gga_dense_conv3x3 at the two dominant shapes (1 GiB fill between launches)."""
+"""Forward time of gga_dense_conv3x3_bn_bwd at the two dominant shapes (1 GiB fill between launches)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import torch

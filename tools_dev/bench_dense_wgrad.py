@@ -1,4 +1,4 @@
-"""Time of the dense 3x3 weight-gradient kernel alone (gga_dense_wgrad3x3_planes through dense_conv._wgrad) at the
+"""Time of the dense 3x3 weight-gradient kernel alone (gga_dense_wgrad3x3_block_amax through dense_conv._wgrad) at the
 trunk's shapes, a 1 GiB fill between launches. Used with tools_dev/run_with_lib.py for kernel variants."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))

@@ -50,8 +50,8 @@ def mask_perm(m):
 
 def apply(x_rows, m, mask, perm, wp, n_rows, kvol, cin, cout):
     y = torch.empty((n_rows, cout), device=DEV)
-    rc = L.gga_sparse_conv_apply_split(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin, cout, 0, F._p(y),
-                                       F._stream())
+    rc = L.gga_sparse_conv_apply_stats(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin, cout, 0, F._p(y),
+                                       cout, 3, None, None, None, F._stream())
     _lib.check(rc, 'proto')
     return y
 
@@ -59,8 +59,8 @@ def apply(x_rows, m, mask, perm, wp, n_rows, kvol, cin, cout):
 def wgrad(x_rows, g_rows, m, n_rows, kvol, cin, cout):
     gw = torch.empty((kvol, cin, cout), device=DEV)
     ws = F._workspace('proto_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout), DEV)
-    rc = L.gga_sparse_conv_wgrad_split(F._p(x_rows), F._p(g_rows), F._p(m), n_rows, kvol, cin, cout, F._p(gw), F._p(ws), ws.numel(),
-                                       F._stream())
+    rc = L.gga_sparse_conv_wgrad_planes(F._p(x_rows), cin, F._p(g_rows), cout, F._p(m), n_rows, kvol, cin, cout, F._p(gw), 3, None, None,
+                                        F._p(ws), ws.numel(), F._stream())
     _lib.check(rc, 'proto')
     return gw
 
@@ -79,8 +79,8 @@ def conv_case(B, cin, cout, H, W, k=3, s=2, p=1):
     bmask, bperm = mask_perm(bm)
     xr = x.permute(0, 2, 3, 1).reshape(n_in, cin)
     w = conv.weight.detach()
-    wf = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), k * k, cin, cout, 0, split=True)
-    wb = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), k * k, cout, cin, 0, split=True)
+    wf = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), k * k, cin, cout, 0)
+    wb = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), k * k, cout, cin, 0)
     y = apply(xr, fm, fmask, fperm, wf, n_out, k * k, cin, cout)
     gy = torch.randn(B, cout, Ho, Wo, device=DEV).contiguous(memory_format=torch.channels_last)
     gr = gy.permute(0, 2, 3, 1).reshape(n_out, cout)
@@ -116,8 +116,8 @@ def deconv_case(B, cin, cout, H, W, s):
     bmask, bperm = mask_perm(bm)
     fmask, fperm = mask_perm(fm)
     w = dec.weight.detach()                                # [cin, cout, s, s]
-    wf = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), s * s, cin, cout, 0, split=True)
-    wb = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), s * s, cout, cin, 0, split=True)
+    wf = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), s * s, cin, cout, 0)
+    wb = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), s * s, cout, cin, 0)
     xr = x.permute(0, 2, 3, 1).reshape(n_lo, cin)
     y = apply(xr, bm, bmask, bperm, wf, n_hi, s * s, cin, cout)
     gy = torch.randn(B, cout, Ho, Wo, device=DEV).contiguous(memory_format=torch.channels_last)

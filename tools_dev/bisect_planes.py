@@ -12,7 +12,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, 'tests')]
 import test_model_gpu as T                      # noqa: E402
-from gga_amd import dense_conv, sparse          # noqa: E402
+from gga_amd import dense_conv                  # noqa: E402
 from gga_amd.cnn import to_channels_last        # noqa: E402
 
 DEV = 'cuda:0'
@@ -37,7 +37,7 @@ def groups(model, case):
     return g
 
 
-def run(case, seed, choice, default, fp32_sparse=False):
+def run(case, seed, choice, default):
     cfg, cpu_model, batch, srl, ref, ref64, ref_losses, ref64_losses = T._reference_case(case, seed)
     model = copy.deepcopy(cpu_model)
     model.pts_middle_encoder.channels_last = True
@@ -54,9 +54,8 @@ def run(case, seed, choice, default, fp32_sparse=False):
         def post(m, a, o):
             dense_conv.PLANES = stack.pop()
         hooks += [mod.register_forward_pre_hook(pre), mod.register_forward_hook(post)]
-    was, was_split = dense_conv.PLANES, sparse.SPLIT_BF16
+    was = dense_conv.PLANES
     dense_conv.PLANES = default
-    sparse.SPLIT_BF16 = not fp32_sparse
     try:
         data = dict(batch, points=[p.to(DEV) for p in batch['points']])
         with torch.no_grad():
@@ -66,7 +65,7 @@ def run(case, seed, choice, default, fp32_sparse=False):
                                               data['GGA_lidar2img'], data['GGA_init_pseudo_labels'], data['GGA_bdry_masks'],
                                               data['GGA_in_box_points'], data['img_metas'], srl=srl)
     finally:
-        dense_conv.PLANES, sparse.SPLIT_BF16 = was, was_split
+        dense_conv.PLANES = was
         for h in hooks:
             h.remove()
     rel = lambda a, b: abs(a - b) / max(abs(b), 1.0)
@@ -83,14 +82,13 @@ def main():
         T._reference_case(case, seed)
         cfg, cpu_model = T._REF_CASES[(case, seed)][:2]
         names = list(groups(cpu_model, case))
-        variants = [('all2', {}, 2, False), ('all3', {}, 3, False)]
+        variants = [('all2', {}, 2), ('all3', {}, 3)]
         if case == 'second':
-            variants.append(('all2_sparse_fp32mfma', {}, 2, True))
-            variants.append(('sparse3_rest2', {n: 3 for n in names if n.startswith('sp.')}, 2, False))
-            variants.append(('sparse2_rest3', {n: 2 for n in names if n.startswith('sp.')}, 3, False))
-        variants += [(f'only3:{n}', {n: 3}, 2, False) for n in names]
-        for tag, choice, default, f32 in variants:
-            dev, floor, vals = run(case, seed, choice, default, f32)
+            variants.append(('sparse3_rest2', {n: 3 for n in names if n.startswith('sp.')}, 2))
+            variants.append(('sparse2_rest3', {n: 2 for n in names if n.startswith('sp.')}, 3))
+        variants += [(f'only3:{n}', {n: 3}, 2) for n in names]
+        for tag, choice, default in variants:
+            dev, floor, vals = run(case, seed, choice, default)
             worst = max(dev, key=dev.get)
             fl = max(floor.values())
             print(f'{case} seed {seed} {tag:32s} worst {dev[worst]:.2e} ({worst}, value {vals[worst]:.4g}); fp32 floor {fl:.2e}; '

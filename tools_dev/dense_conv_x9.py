@@ -45,7 +45,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         w = weight.detach().permute(2, 3, 1, 0).reshape(9, cin, cout).contiguous()     # [k][ci][co]
         rb = _rulebook(B, H, W, x.device)
         y = torch.empty((B * H * W, cout), dtype=torch.float32, device=x.device)
-        S._conv_apply(xr, rb, S._pack_weight(w, 9, cin, cout, 0, split=True), B * H * W, 9, cin, cout, 0, y)
+        S._conv_apply(xr, rb, S._pack_weight(w, 9, cin, cout, 0), B * H * W, 9, cin, cout, 0, y)
         ctx.save_for_backward(x, weight)
         return y.view(B, H, W, cout).permute(0, 3, 1, 2)
 
@@ -61,7 +61,7 @@ class _Conv3x3Fn(torch.autograd.Function):
             w = weight.detach().permute(2, 3, 1, 0).reshape(9, cin, cout).contiguous()
             g = torch.empty((B * H * W, cin), dtype=torch.float32, device=x.device)
             # transposed map of a stride-1 'same' convolution = reversed offsets (as for SubM)
-            S._conv_apply(gy.permute(0, 2, 3, 1).reshape(-1, cout), rb, S._pack_weight(w, 9, cout, cin, 1, split=True),
+            S._conv_apply(gy.permute(0, 2, 3, 1).reshape(-1, cout), rb, S._pack_weight(w, 9, cout, cin, 1),
                           B * H * W, 9, cout, cin, 1, g)
             gx = g.view(B, H, W, cin).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:

@@ -93,8 +93,8 @@ for li, (lvl, C_) in enumerate(levels):
                 k2 = (torch.arange(nrow, device=DEV) // R) * (1 << 32) + (rb.mask.long() & 0xFFFFFFFF)
                 perm = torch.argsort(k2, stable=True).int()
             ms = rb.mask[perm.long()] & 0x7FFFFFF
-            t_f = timeit(lambda: L.gga_sparse_conv_apply_planes(F._p(xs), F._p(rb.nbr), F._p(wp), F._p(perm), F._p(rb.mask), nrow, 27, C_, C_, 0,
-                                                               F._p(y), C_, 2, F._p(x_amax), F._p(w_amax), F._stream()))
+            t_f = timeit(lambda: L.gga_sparse_conv_apply_stats(F._p(xs), F._p(rb.nbr), F._p(wp), F._p(perm), F._p(rb.mask), nrow, 27, C_, C_, 0,
+                                                              F._p(y), C_, 2, F._p(x_amax), F._p(w_amax), None, F._stream()))
             print(f'  {name} region {R:6d}: pairs/row {pairs:.2f} offsets per 128-row tile {unions(ms, 128):5.2f} per 256 {unions(ms, 256):5.2f} | forward {t_f:7.1f} us')
         gw = torch.empty_like(w)
         g = torch.randn(nrow, C_, device=DEV)
