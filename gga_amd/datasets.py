@@ -263,9 +263,10 @@ class KittiDataset_GGA_match(KittiDataset_GGA_train):
     whose ``evaluate`` turns the detections of a test run into KITTI annotations (``format_results`` ->
     ``bbox2result_kitti`` -> ``convert_valid_bboxes``, :330-383,458-571,685-766) and hands them to
     ``pseudo_label_matching_kitti`` together with a copy of its infos (:419-424) - the step that writes the pseudo-label
-    file of the GGA recipe. The KITTI AP evaluation that follows in the reference (``kitti_eval``, a numba CPU code of
-    mmdet3d/core/evaluation) is out of scope (evaluation is not on the path); ``evaluate`` returns the counts of
-    the matching instead."""
+    file of the GGA recipe. ``evaluate`` returns the counts of the matching; with ``kitti_ap=True`` it goes on as the
+    reference does (:425-438) and evaluates the formatted detections against the annos the matching returned with
+    ``gga_amd.kitti_eval.kitti_eval`` (bbox / BEV / 3D / AOS on this repository's kernels), adding the ``{name}/KITTI/...``
+    keys and logging the AP table. Off by default: the plain call returns exactly the three counts."""
 
     def format_results(self, outputs, pklfile_prefix=None, submission_prefix=None):
         import tempfile
@@ -288,17 +289,38 @@ class KittiDataset_GGA_match(KittiDataset_GGA_train):
         return result_files, tmp_dir
 
     def evaluate(self, results, metric=None, logger=None, pklfile_prefix=None, submission_prefix=None, show=False, out_dir=None,
-                 pipeline=None, pseudo_label_file='default', device='cuda:0'):
+                 pipeline=None, pseudo_label_file='default', device='cuda:0', kitti_ap=False):
         from .pseudo_labels import DEFAULT_OUT_FILE, pseudo_label_matching_kitti
         result_files, tmp_dir = self.format_results(results, pklfile_prefix)
         dets = result_files['pts_bbox'] if isinstance(result_files, dict) else result_files
         infos = copy.deepcopy(self.data_infos)
         out_file = DEFAULT_OUT_FILE if pseudo_label_file == 'default' else pseudo_label_file
         gt_annos = pseudo_label_matching_kitti(infos, dets, filename=out_file, device=device)
+        ap_dict = {}
+        if kitti_ap:          # kitti_dataset_GGA_match.py:425-452
+            from .kitti_eval import kitti_eval
+            if isinstance(result_files, dict):
+                for name, result_files_ in result_files.items():
+                    eval_types = ['bbox'] if 'img' in name else ['bbox', 'bev', '3d']
+                    ap_result_str, ap_dict_ = kitti_eval(gt_annos, result_files_, self.CLASSES, eval_types=eval_types, device=device)
+                    for ap_type, ap in ap_dict_.items():
+                        ap_dict[f'{name}/{ap_type}'] = float('{:.4f}'.format(ap))
+                    self._log(f'Results of {name}:\n' + ap_result_str, logger)
+            else:
+                eval_types = ['bbox'] if metric == 'img_bbox' else ['bbox', 'bev', '3d']
+                ap_result_str, ap_dict = kitti_eval(gt_annos, result_files, self.CLASSES, eval_types=eval_types, device=device)
+                self._log('\n' + ap_result_str, logger)
         if tmp_dir is not None:
             tmp_dir.cleanup()
-        return {'pseudo_labels/frames': float(len(gt_annos)), 'pseudo_labels/objects': float(sum(len(a['name']) for a in gt_annos)),
+        return {**ap_dict, 'pseudo_labels/frames': float(len(gt_annos)), 'pseudo_labels/objects': float(sum(len(a['name']) for a in gt_annos)),
                 'pseudo_labels/detections': float(sum(len(d['name']) for d in dets))}
+
+    @staticmethod
+    def _log(msg, logger):
+        if hasattr(logger, 'info'):
+            logger.info(msg)
+        else:
+            print(msg)
 
     def bbox2result_kitti(self, net_outputs, class_names, pklfile_prefix=None, submission_prefix=None):
         assert len(net_outputs) == len(self.data_infos), 'invalid list length of network outputs'

@@ -681,3 +681,94 @@ def write_kitti_tree(root, n_frames, n_points=20000, pc_range=RANGE_PP, n_obj_ra
         pickle.dump(db, f)
     json.dump(stamp, open(stamp_path, 'w'))
     return info_path, db_path
+
+
+# ---- KITTI AP evaluation (gga_amd/kitti_eval.py): seeded label / detection annos in camera coordinates
+KITTI_EVAL_NAMES = ['Car', 'Pedestrian', 'Cyclist', 'Van', 'Person_sitting']
+_KITTI_EVAL_LHW = dict(Car=(3.9, 1.56, 1.6), Pedestrian=(0.8, 1.73, 0.6), Cyclist=(1.76, 1.73, 0.6), Van=(5.0, 2.2, 1.9),
+                       Person_sitting=(0.8, 1.3, 0.6))
+
+
+def _kitti_eval_bbox(loc, dims):
+    """A plausible image box of a camera-frame object (f = 720 px): heights run from ~15 px to ~250 px over the depth range,
+    so labels fall on both sides of every MIN_HEIGHT rule."""
+    x, y, z = loc
+    l, h, w = dims
+    u, v_bottom, half = 620 + 720 * x / z, 190 + 720 * y / z, 360 * max(l, w) * 0.8 / z
+    return np.array([u - half, v_bottom - 720 * h / z, u + half, v_bottom])
+
+
+def make_kitti_eval_case(seed, n_frames, n_gt=10, n_dt=15, dt_dtype=np.float32):
+    """-> (gt_annos, dt_annos) in the KITTI anno format: float64 labels of the three classes plus Van, Person_sitting and
+    trailing DontCare boxes, with occlusion / truncation / height on both sides of every difficulty rule; detections
+    (``dt_dtype``) = jittered copies of labels across the IoU range (some flipped by pi, some of the wrong class), duplicates,
+    false positives, detections inside DontCare boxes and under the minimum height, a few exactly tied scores. About
+    ``n_gt`` labels and ``n_dt`` detections per frame; with 20 frames or more some frames have no labels or no detections
+    (never frame 0)."""
+    rng = np.random.default_rng(seed)
+    gt_annos, dt_annos = [], []
+    for f in range(n_frames):
+        n_obj = int(rng.integers(max(n_gt - 5, 1), n_gt + 3))
+        n_dc = int(rng.integers(0, 3))
+        if n_frames >= 20 and f > 0 and rng.random() < 0.05:
+            n_obj = n_dc = 0
+        names = list(rng.choice(KITTI_EVAL_NAMES, size=n_obj, p=[0.4, 0.2, 0.15, 0.15, 0.1]))
+        loc = np.stack([rng.uniform(-20, 20, n_obj), rng.uniform(1.2, 2.0, n_obj), rng.uniform(5, 60, n_obj)], 1)
+        loc[:, 0] *= loc[:, 2] / 60 + 0.2
+        dims = np.array([_KITTI_EVAL_LHW[n] for n in names]).reshape(n_obj, 3) * rng.uniform(0.85, 1.15, (n_obj, 3))
+        rot = rng.uniform(-np.pi, np.pi, n_obj)
+        bbox = np.array([_kitti_eval_bbox(loc[i], dims[i]) for i in range(n_obj)]).reshape(n_obj, 4)
+        occluded = rng.integers(0, 4, n_obj)
+        truncated = np.where(rng.random(n_obj) < 0.5, 0.0, rng.uniform(0, 0.6, n_obj))
+        alpha = rot - np.arctan2(loc[:, 0], loc[:, 2])
+        dc_bbox = np.stack([rng.uniform(0, 1000, n_dc), rng.uniform(100, 250, n_dc)], 1).reshape(n_dc, 2)
+        dc_bbox = np.concatenate([dc_bbox, dc_bbox + rng.uniform(40, 200, (n_dc, 2))], 1)
+        gt_annos.append(dict(
+            name=np.array(names + ['DontCare'] * n_dc, dtype=str), truncated=np.concatenate([truncated, -np.ones(n_dc)]),
+            occluded=np.concatenate([occluded, -np.ones(n_dc, np.int64)]), alpha=np.concatenate([alpha, -10 * np.ones(n_dc)]),
+            bbox=np.concatenate([bbox, dc_bbox], 0), dimensions=np.concatenate([dims, -np.ones((n_dc, 3))], 0),
+            location=np.concatenate([loc, -1000 * np.ones((n_dc, 3))], 0), rotation_y=np.concatenate([rot, -10 * np.ones(n_dc)])))
+
+        d_name, d_loc, d_dims, d_rot, d_bbox = [], [], [], [], []
+
+        def add(name, loc_, dims_, rot_, bbox_):
+            d_name.append(name), d_loc.append(loc_), d_dims.append(dims_), d_rot.append(rot_), d_bbox.append(bbox_)
+
+        trained = dict(Van='Car', Person_sitting='Pedestrian')
+        keep_p = min(0.85 * n_dt / max(n_gt * 1.4, 1), 0.9)
+        no_dets = n_frames >= 20 and f > 0 and rng.random() < 0.05
+        for i in range(n_obj):
+            for copy_ in range(2):                              # the second round: duplicates
+                if rng.random() > (keep_p if copy_ == 0 else 0.15):
+                    continue
+                sigma = float(rng.choice([0.02, 0.08, 0.25, 0.7]))
+                name = trained.get(names[i], names[i])
+                if rng.random() < 0.05:
+                    name = str(rng.choice(['Car', 'Pedestrian', 'Cyclist']))
+                flip = np.pi if rng.random() < 0.1 else 0.0
+                add(name, loc[i] + rng.normal(0, sigma, 3) * [1, 0.2, 1], dims[i] * (1 + rng.normal(0, 0.1 * sigma + 0.01, 3)),
+                    rot[i] + rng.normal(0, 0.3 * sigma + 0.02) + flip, bbox[i] + rng.normal(0, 20 * sigma + 0.5, 4))
+        for _ in range(int(rng.integers(0, 2 * max(n_dt - n_gt, 1)))):          # false positives, some under the minimum height
+            name = str(rng.choice(['Car', 'Pedestrian', 'Cyclist']))
+            l_ = np.array([rng.uniform(-15, 15), rng.uniform(1.2, 2.0), rng.uniform(5, 80)])
+            dm = np.array(_KITTI_EVAL_LHW[name]) * rng.uniform(0.8, 1.2, 3)
+            add(name, l_, dm, rng.uniform(-np.pi, np.pi), _kitti_eval_bbox(l_, dm))
+        for k in range(n_dc):                                  # detections inside DontCare boxes
+            if rng.random() < 0.7:
+                name = str(rng.choice(['Car', 'Pedestrian', 'Cyclist']))
+                l_ = np.array([rng.uniform(-15, 15), rng.uniform(1.2, 2.0), rng.uniform(30, 60)])
+                dm = np.array(_KITTI_EVAL_LHW[name])
+                x1, y1, x2, y2 = dc_bbox[k]
+                add(name, l_, dm, rng.uniform(-np.pi, np.pi),
+                    np.array([x1 + 0.1 * (x2 - x1), y1 + 0.05 * (y2 - y1), x2 - 0.2 * (x2 - x1), y2 - 0.1 * (y2 - y1)]))
+        n = 0 if no_dets else len(d_name)
+        score = rng.uniform(0.05, 1.0, n)
+        tie = rng.random(n) < 0.1
+        score[tie] = np.round(score[tie], 1)
+        as_dt = lambda a, shape: np.asarray(a[:n], np.float64).reshape(shape).astype(dt_dtype)
+        d_loc_, d_rot_ = as_dt(d_loc, (n, 3)), as_dt(d_rot, (n, ))
+        dt_annos.append(dict(
+            name=np.array(d_name[:n], dtype=str), truncated=np.zeros(n), occluded=np.zeros(n, np.int64),
+            alpha=(d_rot_ - np.arctan2(d_loc_[:, 0], d_loc_[:, 2])).astype(dt_dtype), bbox=as_dt(d_bbox, (n, 4)),
+            dimensions=as_dt(d_dims, (n, 3)), location=d_loc_, rotation_y=d_rot_, score=score.astype(dt_dtype)))
+    return gt_annos, dt_annos

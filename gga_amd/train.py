@@ -684,7 +684,8 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     -> the ``Runner`` after training."""
     from .loader import build_dataloader
     if validate:
-        raise NotImplementedError('evaluation hooks (KITTI AP) are out of scope: run with validate=False')
+        raise NotImplementedError('the in-training evaluation hook is out of scope: run with validate=False and evaluate the '
+                                  'checkpoint with tools/generate_pseudo_labels_gga.py --eval-options kitti_ap=True')
     dataset = dataset[0] if isinstance(dataset, (list, tuple)) else dataset
     data = cfg.data
     if 'imgs_per_gpu' in data:                    # mmdet < 2.0 spelling

@@ -771,6 +771,50 @@ int gga_image_box_match(const double* dt_boxes, const int64_t* dt_offsets, const
                         double* best_iou, double* overlaps, const int64_t* overlap_offsets, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* KITTI AP evaluation (mmdet3d/core/evaluation/kitti_utils/eval.py,         */
+/* rotate_iou.py): bbox / BEV / 3D / AOS.                                    */
+/* ------------------------------------------------------------------------- */
+/* Rotated overlaps of every detection with the ground truths of its own frame: `rotate_iou_gpu_eval` (rotate_iou.py:19-379)
+ * and, for metric 2, `d3_box_overlap_kernel` (eval.py:123-160), as `calculate_iou_partly(dt_annos, gt_annos, metric)` calls
+ * them from eval_class - only the per-frame blocks, not the part-wise (sum dt) x (sum gt) matrices. dt_boxes [n_dt,7],
+ * gt_boxes [n_gt,7] f64 = location (3), dimensions (3), rotation_y in camera coordinates as the annos hold them, concatenated
+ * over frames with device offsets dt_offsets / gt_offsets [n_frames+1]. metric 1: BEV IoU of columns (0, 2 / 3, 5 / 6), criterion
+ * -1. metric 2: BEV intersection area x height overlap over the union volume, criterion -1. The query box is the ground truth.
+ * The BEV part is float32 arithmetic on the boxes cast to float32 (the reference's kernel signature), with the operations
+ * numba types float64 carried in double (kitti_eval.hip lists them). dt_f32 / gt_f32: the annos of that side were float32,
+ * which decides the dtype of every operation of the height part as numpy / numba would. overlaps f32: frame f's
+ * [n_dt_f, n_gt_f] matrix at overlap_offsets[f] (the layout gga_image_box_match writes for metric 0); n_overlaps = its
+ * length. A frame whose offsets do not fit n_dt / n_gt / n_overlaps is not written. */
+int gga_kitti_eval_overlaps(const double* dt_boxes, const int64_t* dt_offsets, int64_t n_dt, const double* gt_boxes,
+                            const int64_t* gt_offsets, int64_t n_gt, int n_frames, int metric, int dt_f32, int gt_f32,
+                            float* overlaps, const int64_t* overlap_offsets, int64_t n_overlaps, void* stream);
+
+/* `compute_statistics_jit` (eval.py:163-281) for all frames and all combinations of one metric at once. A combination c
+ * is a (class, difficulty) pair - row combo_cd[c] of ignored_gt [n_cd, n_gt] / ignored_dt [n_cd, n_dt] (int8: 0 counted,
+ * 1 ignored, -1 other class; clean_data) - with the min overlap combo_min_overlap[c]. overlaps: the per-frame matrices
+ * at overlap_offsets (f64 when overlaps_f64, as gga_image_box_match writes them, else f32), compared in float64.
+ * dt_data [n_dt,6] f64 = bbox (4), alpha, score; gt_alpha [n_gt]; dc_boxes [n_dc,4] the DontCare boxes (used by metric 0
+ * only) with offsets dc_offsets [n_frames+1]; dt_f32: the detections' columns were float32 (decides the rounding of the
+ * detection-vs-DontCare overlap). max_dt >= the largest number of detections of one frame.
+ * compute_fp = 0: the first pass of eval_class (thresh 0): tp_det [n_combos, n_gt] i32 = for every ground truth the
+ *   index within its frame of the detection it was matched to as a true positive, else -1 (fill with -1 beforehand; the scores
+ *   of these detections are what get_thresholds sorts).
+ * compute_fp = 1: `fused_compute_statistics` (eval.py:293-340): thresholds [n_combos, 41] f64 with n_thresholds [n_combos]
+ *   valid entries each; counts [n_combos, 41, 3] i64 = tp, fp, fn and similarity [n_combos, 41] f64 (the AOS sum, when
+ *   compute_aos) summed over the frames. One lane per (frame, combination) walks the thresholds; the 64 frames of a wave are
+ *   summed by a fixed butterfly and the waves in order by a second launch, so the result has the same bits on every run.
+ * workspace: gga_kitti_eval_stats_workspace_bytes. A frame whose offsets do not fit the totals is skipped. */
+size_t gga_kitti_eval_stats_workspace_bytes(int n_frames, int n_combos, int max_dt);
+int gga_kitti_eval_stats(const void* overlaps, int overlaps_f64, const int64_t* overlap_offsets, int64_t n_overlaps,
+                         const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* dc_offsets,
+                         const double* dt_data, int64_t n_dt, const double* gt_alpha, int64_t n_gt, const double* dc_boxes,
+                         int64_t n_dc, const int8_t* ignored_gt, const int8_t* ignored_dt, int n_cd, const int32_t* combo_cd,
+                         const double* combo_min_overlap, int n_combos, int n_frames, int max_dt, int metric, int dt_f32,
+                         int compute_fp, int compute_aos, const double* thresholds, const int32_t* n_thresholds,
+                         int32_t* tp_det, int64_t* counts, double* similarity, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Offline GGA label generation primitives,             */
 /* tools/data_converter/utils_gga.py. float64, reference operation order.       */
 /* ------------------------------------------------------------------------- */

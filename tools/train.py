@@ -22,7 +22,7 @@ def main():
     ap.add_argument('--work-dir')
     ap.add_argument('--resume-from')
     ap.add_argument('--auto-resume', action='store_true')
-    ap.add_argument('--no-validate', action='store_true', help='(always on: evaluation hooks are out of scope)')
+    ap.add_argument('--no-validate', action='store_true', help='(always on: the in-training evaluation hook is out of scope; KITTI AP runs after a test run)')
     ap.add_argument('--gpu-id', type=int, default=0)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--diff-seed', action='store_true', help='a different seed per rank')

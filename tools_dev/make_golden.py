@@ -527,6 +527,187 @@ def golden_pseudo_match(ref):
     np.savez_compressed(os.path.join(OUT, 'pseudo_match.npz'), **out)
 
 
+KITTI_EVAL_CLASSES = ['Car', 'Pedestrian', 'Cyclist']
+KITTI_EVAL_GUARD = 1e-3          # no float64 overlap of case B within this of a min overlap in use
+
+
+def _kitti_eval_levels():
+    return np.unique(np.concatenate([[0.7, 0.5, 0.25], np.linspace(0.5, 0.95, 10), np.linspace(0.25, 0.7, 10)]))
+
+
+def load_reference_kitti_eval():
+    """eval.py + rotate_iou.py as plain Python: numba.jit / cuda.jit are the identity, prange is range, a cuda.local.array is a
+    float32 numpy array, and rotate_iou_gpu_eval (the kernel launch) is a double loop over devRotateIoUEval with the kernel's
+    argument order (query box first). kitti_eval_coco_style hands a bool to do_eval where eval_types belongs, which plain
+    Python refuses; the wrapper below reads it as the reference means it (all three metrics, plus AOS when set). Its
+    np.linspace(start, stop, 10.0) needs the count as an int on a current numpy."""
+    numba = sys.modules['numba']
+    numba.prange, numba.float32 = range, np.float32
+    arr = types.SimpleNamespace(array=lambda shape, dtype=None: np.zeros(shape, np.float32))
+    numba.cuda = _mod('numba.cuda', jit=_identity_decorator_factory, local=arr, shared=arr)
+    _mod('mmdet3d.core.evaluation')
+    _mod('mmdet3d.core.evaluation.kitti_utils')
+    riou = load('mmdet3d.core.evaluation.kitti_utils.rotate_iou', 'mmdet3d/core/evaluation/kitti_utils/rotate_iou.py')
+    ev = load('mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d/core/evaluation/kitti_utils/eval.py')
+    cache = {}
+
+    def rotate_iou_gpu_eval(boxes, query_boxes, criterion=-1, device_id=0):
+        boxes, query_boxes = boxes.astype(np.float32), query_boxes.astype(np.float32)
+        key = (boxes.tobytes(), query_boxes.tobytes(), criterion)
+        if key not in cache:
+            iou = np.zeros((boxes.shape[0], query_boxes.shape[0]), np.float32)
+            with np.errstate(all='ignore'):
+                for n in range(boxes.shape[0]):
+                    for k in range(query_boxes.shape[0]):
+                        iou[n, k] = riou.devRotateIoUEval(query_boxes[k], boxes[n], criterion)
+            cache[key] = iou
+        return cache[key].copy().astype(boxes.dtype)
+
+    riou.rotate_iou_gpu_eval = rotate_iou_gpu_eval
+    plain_do_eval = ev.do_eval
+
+    def do_eval(gt_annos, dt_annos, current_classes, min_overlaps, eval_types=['bbox', 'bev', '3d']):
+        if isinstance(eval_types, bool):
+            eval_types = ['bbox', 'bev', '3d'] + (['aos'] if eval_types else [])
+        return plain_do_eval(gt_annos, dt_annos, current_classes, min_overlaps, eval_types)
+
+    ev.do_eval = do_eval
+
+    class _Numpy:          # do_coco_style_eval calls np.linspace with a float count, which this numpy refuses
+        def __getattr__(self, name):
+            return getattr(np, name)
+
+        @staticmethod
+        def linspace(start, stop, num):
+            return np.linspace(start, stop, int(num))
+
+    ev.np = _Numpy()
+    return ev
+
+
+def make_kitti_overlap_case(seed=71):
+    """Case A: ragged frames of camera boxes [n,7] -> list of (dt float32, gt float64, degenerate mask [n_dt, n_gt])."""
+    rng = np.random.default_rng(seed)
+
+    def rand(n, spread):
+        y = np.where(rng.random(n) < 0.15, rng.uniform(5, 8, n), rng.uniform(1.0, 2.2, n))        # some height-disjoint
+        return np.stack([rng.uniform(0, spread, n), y, rng.uniform(0, spread, n), rng.uniform(1, 4.5, n), rng.uniform(1.4, 2.0, n),
+                         rng.uniform(0.6, 2.5, n), rng.uniform(-np.pi, np.pi, n)], 1)
+
+    A = [0, 1.5, 0, 4, 1.5, 2, 0]
+    gt_special = np.array([A, [0, 1.5, 0, 4, 1.5, 2, 0.3], [0, 1.6, 0, 8, 2, 6, 0.3], [1, 1.5, 0.5, 4, 1.5, 2, 0.3 + 2 * np.pi],
+                           [0.5, 10, 0.25, 4, 1.5, 2, 0.1], [1, 1.4, -0.5, 3, 1.5, 2, -4.0], [2.5, 1.5, 1.0, 2, 1.5, 2, 0],
+                           [-1, 1.5, 0.75, 4, 1.6, 1.5, np.pi / 2]], np.float64)
+    dt_special = np.array([A, [4, 1.5, 0, 4, 1.5, 2, 0], [0.5, 1.5, 0.25, 4, 1.5, 2, 0.3], [0, 1.5, 0, 1, 1, 0.5, 0.7],
+                           [30, 1.5, 30, 4, 1.5, 2, 1.0], [1, 1.5, 0.5, 4, 1.5, 2, 0], [0.25, 1.5, 0.25, 3.5, 1.5, 1.75, 4.0],
+                           [0.5, 1.25, -0.25, 4, 1.5, 2, -3.7]], np.float64)
+    deg = np.zeros((8, 8), bool)
+    deg[0, 0] = deg[1, 0] = True               # identical boxes; boxes sharing an edge
+    frames = [(rand(8, 6), rand(10, 6), None), (rand(0, 1), rand(0, 1), None), (rand(0, 1), rand(5, 6), None),
+              (rand(6, 6), rand(0, 1), None), (dt_special, gt_special, deg), (rand(16, 9), rand(14, 9), None)]
+    return [(d.astype(np.float32), g, np.zeros((len(d), len(g)), bool) if m is None else m) for d, g, m in frames]
+
+
+def golden_kitti_eval(ref):
+    """tests/golden/kitti_eval.npz: the reference's rotated overlaps (case A) and its kitti_eval / eval_class /
+    kitti_eval_coco_style on a seeded set of annos (case B), with the inputs. Arrays and result text only."""
+    import copy
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _kitti_eval_ref as K
+    ev = load_reference_kitti_eval()
+    out = {}
+    # ---- case A
+    frames = make_kitti_overlap_case()
+    out['A.dt_count'] = np.array([len(d) for d, _, _ in frames], np.int64)
+    out['A.gt_count'] = np.array([len(g) for _, g, _ in frames], np.int64)
+    out['A.dt'] = np.concatenate([d for d, _, _ in frames], 0)
+    out['A.gt'] = np.concatenate([g for _, g, _ in frames], 0)
+    out['A.degenerate'] = np.concatenate([m.reshape(-1) for _, _, m in frames])
+    # Where this emulation departs from numba's typing, which kitti_eval.hip follows: plain Python keeps `x / 2.0` and the
+    # area accumulator float32 (numba: float64), and in d3_box_overlap_kernel min() / max() hand back one operand unchanged, so
+    # a height overlap whose two selected operands are both the detection's float32 values is a float32 subtraction here and
+    # a float64 one under numba's type unification (and in the kernel). Each is one float32 rounding at most; the tolerance
+    # of the device test (twice A.ref_err) is what absorbs it.
+    ref_err = 0.0
+    for metric, name in ((1, 'bev'), (2, '3d')):
+        got = []
+        for d, g, m in frames:
+            if metric == 1:
+                o = ev.bev_box_overlap(d[:, [0, 2, 3, 5, 6]], g[:, [0, 2, 3, 5, 6]])
+            else:
+                o = ev.d3_box_overlap(d, g)
+            assert o.dtype == np.float32 and o.shape == (len(d), len(g))
+            o64 = K.rotated_overlaps64(d, g, metric)
+            if o.size:
+                ref_err = max(ref_err, float(np.abs(o.astype(np.float64) - o64)[~m].max(initial=0.0)))
+            got.append(o.reshape(-1))
+        out[f'A.{name}'] = np.concatenate(got)
+    out['A.ref_err'] = np.array(ref_err)
+    n_pairs = out['A.degenerate'].size
+    assert out['A.degenerate'].mean() <= 0.02, out['A.degenerate'].mean()
+    print(f'  kitti_eval[A]: {n_pairs} pairs, {int(out["A.degenerate"].sum())} degenerate; the emulated reference is at most '
+          f'{ref_err:.3e} from float64 on the others')
+
+    # ---- case B
+    gts, dts = synthetic.make_kitti_eval_case(83, 40, n_gt=9, n_dt=12)
+    levels = _kitti_eval_levels()
+    rng = np.random.default_rng(82)
+    redrawn = 0
+    for g, d in zip(gts, dts):
+        for _ in range(200):
+            ovs = [K.image_overlaps64(d['bbox'], g['bbox']), K.rotated_overlaps64(K.box7(d), K.box7(g), 1),
+                   K.rotated_overlaps64(K.box7(d), K.box7(g), 2)]
+            keep = np.array([n != 'DontCare' for n in g['name']], bool)
+            near = np.zeros(len(d['name']), bool)
+            for o in ovs:
+                near |= (np.abs(o[:, keep, None] - levels[None, None, :]) < KITTI_EVAL_GUARD).any(axis=(1, 2))
+            if not near.any():
+                break
+            for j in np.flatnonzero(near):          # re-draw the detection's position: image box and centre
+                d['bbox'][j] += rng.normal(0, 1.0, 4).astype(d['bbox'].dtype)
+                d['location'][j] += (rng.normal(0, 0.05, 3) * [1, 0.2, 1]).astype(d['location'].dtype)
+                redrawn += 1
+        else:
+            raise AssertionError('could not move every overlap away from the min overlaps')
+    # a score tie cannot change an assignment: the kernels walk detections and ground truths in the reference's order
+    # (first maximum wins in both), and get_thresholds sorts the scores, so no tie guard is needed beyond this note
+    K.pack_annos('B.gt', gts, out)
+    K.pack_annos('B.dt', dts, out)
+    result, ret_dict = ev.kitti_eval(copy.deepcopy(gts), copy.deepcopy(dts), KITTI_EVAL_CLASSES, ['bbox', 'bev', '3d'])
+    out['B.result'] = np.array(result)
+    out['B.ret_keys'] = np.array(list(ret_dict.keys()))
+    out['B.ret_values'] = np.array([ret_dict[k] for k in ret_dict], np.float64)
+    assert np.isfinite(out['B.ret_values']).all() and (out['B.ret_values'] > 1).sum() > 60, out['B.ret_values']
+    assert 'aos' in result
+    o7 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5]] * 3)
+    o5 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.5, 0.25, 0.25, 0.5, 0.25], [0.5, 0.25, 0.25, 0.5, 0.25]])
+    min_overlaps = np.stack([o7, o5], 0)[:, :, [0, 1, 2]]
+    for metric in range(3):
+        ret = ev.eval_class(copy.deepcopy(gts), copy.deepcopy(dts), [0, 1, 2], [0, 1, 2], metric, min_overlaps, compute_aos=metric == 0)
+        for k in ('recall', 'precision', 'orientation'):
+            out[f'B.eval_class.{metric}.{k}'] = ret[k]
+    mAPs = ev.do_eval(copy.deepcopy(gts), copy.deepcopy(dts), [0, 1, 2], min_overlaps, ['bbox', 'bev', '3d', 'aos'])
+    for k, m in zip(('11_bbox', '11_bev', '11_3d', '11_aos', '40_bbox', '40_bev', '40_3d', '40_aos'), mAPs):
+        out[f'B.mAP{k}'] = m
+    for c in range(3):
+        for l in range(3):
+            flags = [ev.clean_data(g, d, c, l) for g, d in zip(gts, dts)]
+            out[f'B.clean.{c}.{l}.ignored_gt'] = np.concatenate([np.array(f[1], np.int64) for f in flags])
+            out[f'B.clean.{c}.{l}.ignored_dt'] = np.concatenate([np.array(f[2], np.int64) for f in flags])
+            out[f'B.clean.{c}.{l}.num_valid_gt'] = np.array(sum(f[0] for f in flags))
+            out[f'B.clean.{c}.{l}.dc_num'] = np.array([len(f[3]) for f in flags], np.int64)
+            assert (out[f'B.clean.{c}.{l}.ignored_gt'] == 0).any() and (out[f'B.clean.{c}.{l}.ignored_gt'] == 1).any()
+    out['B.coco_result'] = np.array(ev.kitti_eval_coco_style(copy.deepcopy(gts), copy.deepcopy(dts), KITTI_EVAL_CLASSES))
+    # no value of the table may sit on a rounding edge of its format (else: another seed)
+    edge = np.abs(out['B.ret_values'] * 1e4 - np.floor(out['B.ret_values'] * 1e4) - 0.5)
+    assert edge.min() > 1e-3, edge.min()
+    np.savez_compressed(os.path.join(OUT, 'kitti_eval.npz'), **out)
+    print(f'  kitti_eval[B]: {len(gts)} frames, {sum(len(g["name"]) for g in gts)} labels, {sum(len(d["name"]) for d in dts)} '
+          f'detections ({redrawn} re-drawn); {len(ret_dict)} keys')
+    print(result)
+    print(out['B.coco_result'])
+
+
 PIPELINE_CASES = ((41, 6), (42, 5))          # (seed, frames)
 PIPELINE_OUT_KEYS = ('gt_labels_3d', 'GGA_boxes_img', 'GGA_lidar2img', 'GGA_init_pseudo_labels', 'GGA_bdry_masks',
                      'GGA_mask_valid', 'GGA_difficulty', 'GGA_num_points_in_box2d')
@@ -1385,6 +1566,7 @@ def main():
     golden_encoders(ref)
     golden_head(ref)
     golden_pseudo_match(ref)
+    golden_kitti_eval(ref)
     golden_pipeline(ref)
     golden_label_gen(ref)
     golden_rga(ref)
