@@ -187,6 +187,149 @@ class KittiDataset_GGA_train:
             data = self.prepare_train_data(self._rand_another(idx))
         return data
 
+    # ---- results of a test run -> KITTI annotations -> AP (kitti_dataset_GGA_train.py:329-566,680-761)
+    def format_results(self, outputs, pklfile_prefix=None, submission_prefix=None, device=None):
+        """``device``: where ``bbox2result_kitti`` formats (None = the host loop)."""
+        import tempfile
+        tmp_dir = None
+        if pklfile_prefix is None:
+            tmp_dir = tempfile.TemporaryDirectory()
+            pklfile_prefix = os.path.join(tmp_dir.name, 'results')
+        if not isinstance(outputs[0], dict):
+            raise NotImplementedError('2D-only results (bbox2result_kitti2d) are not produced by the GGA configs')
+        if 'pts_bbox' in outputs[0] or 'img_bbox' in outputs[0]:
+            result_files = dict()
+            for name in outputs[0]:
+                if 'img' in name:
+                    raise NotImplementedError('image-branch results are not produced by the GGA configs')
+                results_ = [out[name] for out in outputs]
+                sub = submission_prefix + name if submission_prefix is not None else None
+                result_files[name] = self.bbox2result_kitti(results_, self.CLASSES, pklfile_prefix + name, sub, device=device)
+        else:
+            result_files = self.bbox2result_kitti(outputs, self.CLASSES, pklfile_prefix, submission_prefix, device=device)
+        return result_files, tmp_dir
+
+    def evaluate(self, results, metric=None, logger=None, pklfile_prefix=None, submission_prefix=None, show=False, out_dir=None,
+                 pipeline=None, device='cuda:0'):
+        """KITTI AP of a test run against the infos' own ``annos`` (kitti_dataset_GGA_train.py:384-451) with
+        ``gga_amd.kitti_eval.kitti_eval``; the detections are formatted on ``device`` (``bbox2result_kitti``). A dict of result
+        files (``pts_bbox``) gives the keys ``{name}/{ap_type}`` rounded to four decimals, a flat list the AP dict as it comes.
+        ``show`` / ``out_dir`` (visualisation) are not part of this repository: refused."""
+        if show or out_dir:
+            raise NotImplementedError('evaluate(show=..., out_dir=...): visualisation of the results is out of scope')
+        from .kitti_eval import kitti_eval
+        result_files, tmp_dir = self.format_results(results, pklfile_prefix, device=device)
+        gt_annos = [info['annos'] for info in self.data_infos]
+        if isinstance(result_files, dict):
+            ap_dict = dict()
+            for name, result_files_ in result_files.items():
+                eval_types = ['bbox'] if 'img' in name else ['bbox', 'bev', '3d']
+                ap_result_str, ap_dict_ = kitti_eval(gt_annos, result_files_, self.CLASSES, eval_types=eval_types, device=device)
+                for ap_type, ap in ap_dict_.items():
+                    ap_dict[f'{name}/{ap_type}'] = float('{:.4f}'.format(ap))
+                self._log(f'Results of {name}:\n' + ap_result_str, logger)
+        else:
+            eval_types = ['bbox'] if metric == 'img_bbox' else ['bbox', 'bev', '3d']
+            ap_result_str, ap_dict = kitti_eval(gt_annos, result_files, self.CLASSES, eval_types=eval_types, device=device)
+            self._log('\n' + ap_result_str, logger)
+        if tmp_dir is not None:
+            tmp_dir.cleanup()
+        return ap_dict
+
+    @staticmethod
+    def _log(msg, logger):
+        if hasattr(logger, 'info'):
+            logger.info(msg)
+        else:
+            print(msg)
+
+    def bbox2result_kitti(self, net_outputs, class_names, pklfile_prefix=None, submission_prefix=None, device=None):
+        """``device=None``: the per-frame host loop below (``convert_valid_bboxes`` on CPU tensors). A device: all frames in
+        one launch of ``kitti_format.format_kitti_dets`` - the same annos to float32 rounding; ``GGA_KITTI_FORMAT=0`` in the
+        environment keeps the host loop whatever ``device`` says."""
+        assert len(net_outputs) == len(self.data_infos), 'invalid list length of network outputs'
+        if submission_prefix is not None:
+            os.makedirs(submission_prefix, exist_ok=True)
+        on_device = None
+        if device is not None:
+            from . import kitti_format
+            if kitti_format.enabled():
+                on_device = kitti_format.format_kitti_dets(net_outputs, self.data_infos, class_names, self.pcd_limit_range, device)
+        det_annos = []
+        for idx, pred_dicts in enumerate(net_outputs):
+            info = self.data_infos[idx]
+            sample_idx = info['image']['image_idx']
+            if on_device is not None:
+                anno = on_device[idx]
+                self._write_submission(anno, sample_idx, submission_prefix)
+                det_annos.append(anno)
+                continue
+            image_shape = info['image']['image_shape'][:2]
+            box_dict = self.convert_valid_bboxes(pred_dicts, info)
+            n = len(box_dict['bbox'])
+            cam, lidar = np.asarray(box_dict['box3d_camera']), np.asarray(box_dict['box3d_lidar'])
+            # KITTI label columns of the frame's valid detections, whole columns at a time: 2D box clipped to the image,
+            # observation angle alpha = rotation_y minus the azimuth of the box centre seen from the LiDAR origin
+            bbox = np.array(box_dict['bbox'], dtype=np.asarray(box_dict['bbox']).dtype).reshape(n, 4)
+            if n:
+                bbox[:, 2:] = np.minimum(bbox[:, 2:], image_shape[::-1])
+                bbox[:, :2] = np.maximum(bbox[:, :2], [0, 0])
+                anno = dict(name=np.array([class_names[int(label)] for label in box_dict['label_preds']]),
+                            truncated=np.zeros(n), occluded=np.zeros(n, dtype=np.int64),
+                            alpha=-np.arctan2(-lidar[:, 1], lidar[:, 0]) + cam[:, 6], bbox=bbox, dimensions=cam[:, 3:6],
+                            location=cam[:, :3], rotation_y=cam[:, 6], score=np.asarray(box_dict['scores']))
+            else:
+                anno = dict(name=np.array([]), truncated=np.array([]), occluded=np.array([]), alpha=np.array([]), bbox=np.zeros([0, 4]),
+                            dimensions=np.zeros([0, 3]), location=np.zeros([0, 3]), rotation_y=np.array([]), score=np.array([]))
+            self._write_submission(anno, sample_idx, submission_prefix)
+            anno['sample_idx'] = np.array([sample_idx] * len(anno['score']), dtype=np.int64)
+            det_annos.append(anno)
+        if pklfile_prefix is not None:
+            out = pklfile_prefix if pklfile_prefix.endswith(('.pkl', '.pickle')) else f'{pklfile_prefix}.pkl'
+            with open(out, 'wb') as f:
+                pickle.dump(det_annos, f)
+        return det_annos
+
+    @staticmethod
+    def _write_submission(anno, sample_idx, submission_prefix):
+        if submission_prefix is None:
+            return
+        with open(f'{submission_prefix}/{sample_idx:06d}.txt', 'w') as f:
+            bbox, loc, dims = anno['bbox'], anno['location'], anno['dimensions']          # lhw -> hwl
+            for i in range(len(bbox)):
+                print('{} -1 -1 {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f}'.format(
+                    anno['name'][i], anno['alpha'][i], bbox[i][0], bbox[i][1], bbox[i][2], bbox[i][3], dims[i][1], dims[i][2],
+                    dims[i][0], loc[i][0], loc[i][1], loc[i][2], anno['rotation_y'][i], anno['score'][i]), file=f)
+
+    def convert_valid_bboxes(self, box_dict, info):
+        from .box3d import CameraInstance3DBoxes, points_cam2img
+        box_preds, scores, labels = box_dict['boxes_3d'], box_dict['scores_3d'], box_dict['labels_3d']
+        sample_idx = info['image']['image_idx']
+        box_preds.limit_yaw(offset=0.5, period=np.pi * 2)
+        empty = dict(bbox=np.zeros([0, 4]), box3d_camera=np.zeros([0, 7]), box3d_lidar=np.zeros([0, 7]), scores=np.zeros([0]),
+                     label_preds=np.zeros([0, 4]), sample_idx=sample_idx)
+        if len(box_preds) == 0:
+            return empty
+        rect = info['calib']['R0_rect'].astype(np.float32)
+        Trv2c = info['calib']['Tr_velo_to_cam'].astype(np.float32)
+        P2 = box_preds.tensor.new_tensor(info['calib']['P2'].astype(np.float32))
+        img_shape = info['image']['image_shape']
+        cam = CameraInstance3DBoxes(lidar_boxes_to_camera(box_preds.tensor, rect @ Trv2c), box_dim=box_preds.tensor.shape[-1])
+        box_corners_in_image = points_cam2img(cam.corners, P2)
+        minxy, maxxy = torch.min(box_corners_in_image, dim=1)[0], torch.max(box_corners_in_image, dim=1)[0]
+        box_2d_preds = torch.cat([minxy, maxxy], dim=1)
+        image_shape = box_preds.tensor.new_tensor(img_shape)
+        valid_cam_inds = ((box_2d_preds[:, 0] < image_shape[1]) & (box_2d_preds[:, 1] < image_shape[0]) &
+                          (box_2d_preds[:, 2] > 0) & (box_2d_preds[:, 3] > 0))
+        limit_range = box_preds.tensor.new_tensor(self.pcd_limit_range)
+        center = box_preds.tensor[:, :3]              # ``center`` of a LiDAR box is its bottom centre (base_box3d.py:96-103)
+        valid_inds = valid_cam_inds & ((center > limit_range[:3]) & (center < limit_range[3:])).all(-1)
+        if valid_inds.sum() > 0:
+            return dict(bbox=box_2d_preds[valid_inds, :].numpy(), box3d_camera=cam.tensor[valid_inds].numpy(),
+                        box3d_lidar=box_preds.tensor[valid_inds].numpy(), scores=scores[valid_inds].numpy(),
+                        label_preds=labels[valid_inds].numpy(), sample_idx=sample_idx)
+        return empty
+
 
 def _unwrap(x):
     return getattr(x, '_data', getattr(x, 'data', x))
@@ -268,26 +411,6 @@ class KittiDataset_GGA_match(KittiDataset_GGA_train):
     ``gga_amd.kitti_eval.kitti_eval`` (bbox / BEV / 3D / AOS on this repository's kernels), adding the ``{name}/KITTI/...``
     keys and logging the AP table. Off by default: the plain call returns exactly the three counts."""
 
-    def format_results(self, outputs, pklfile_prefix=None, submission_prefix=None):
-        import tempfile
-        tmp_dir = None
-        if pklfile_prefix is None:
-            tmp_dir = tempfile.TemporaryDirectory()
-            pklfile_prefix = os.path.join(tmp_dir.name, 'results')
-        if not isinstance(outputs[0], dict):
-            raise NotImplementedError('2D-only results (bbox2result_kitti2d) are not produced by the GGA configs')
-        if 'pts_bbox' in outputs[0] or 'img_bbox' in outputs[0]:
-            result_files = dict()
-            for name in outputs[0]:
-                if 'img' in name:
-                    raise NotImplementedError('image-branch results are not produced by the GGA configs')
-                results_ = [out[name] for out in outputs]
-                sub = submission_prefix + name if submission_prefix is not None else None
-                result_files[name] = self.bbox2result_kitti(results_, self.CLASSES, pklfile_prefix + name, sub)
-        else:
-            result_files = self.bbox2result_kitti(outputs, self.CLASSES, pklfile_prefix, submission_prefix)
-        return result_files, tmp_dir
-
     def evaluate(self, results, metric=None, logger=None, pklfile_prefix=None, submission_prefix=None, show=False, out_dir=None,
                  pipeline=None, pseudo_label_file='default', device='cuda:0', kitti_ap=False):
         from .pseudo_labels import DEFAULT_OUT_FILE, pseudo_label_matching_kitti
@@ -314,79 +437,3 @@ class KittiDataset_GGA_match(KittiDataset_GGA_train):
             tmp_dir.cleanup()
         return {**ap_dict, 'pseudo_labels/frames': float(len(gt_annos)), 'pseudo_labels/objects': float(sum(len(a['name']) for a in gt_annos)),
                 'pseudo_labels/detections': float(sum(len(d['name']) for d in dets))}
-
-    @staticmethod
-    def _log(msg, logger):
-        if hasattr(logger, 'info'):
-            logger.info(msg)
-        else:
-            print(msg)
-
-    def bbox2result_kitti(self, net_outputs, class_names, pklfile_prefix=None, submission_prefix=None):
-        assert len(net_outputs) == len(self.data_infos), 'invalid list length of network outputs'
-        if submission_prefix is not None:
-            os.makedirs(submission_prefix, exist_ok=True)
-        det_annos = []
-        for idx, pred_dicts in enumerate(net_outputs):
-            info = self.data_infos[idx]
-            sample_idx = info['image']['image_idx']
-            image_shape = info['image']['image_shape'][:2]
-            box_dict = self.convert_valid_bboxes(pred_dicts, info)
-            n = len(box_dict['bbox'])
-            cam, lidar = np.asarray(box_dict['box3d_camera']), np.asarray(box_dict['box3d_lidar'])
-            # KITTI label columns of the frame's valid detections, whole columns at a time: 2D box clipped to the image,
-            # observation angle alpha = rotation_y minus the azimuth of the box centre seen from the LiDAR origin
-            bbox = np.array(box_dict['bbox'], dtype=np.asarray(box_dict['bbox']).dtype).reshape(n, 4)
-            if n:
-                bbox[:, 2:] = np.minimum(bbox[:, 2:], image_shape[::-1])
-                bbox[:, :2] = np.maximum(bbox[:, :2], [0, 0])
-                anno = dict(name=np.array([class_names[int(label)] for label in box_dict['label_preds']]),
-                            truncated=np.zeros(n), occluded=np.zeros(n, dtype=np.int64),
-                            alpha=-np.arctan2(-lidar[:, 1], lidar[:, 0]) + cam[:, 6], bbox=bbox, dimensions=cam[:, 3:6],
-                            location=cam[:, :3], rotation_y=cam[:, 6], score=np.asarray(box_dict['scores']))
-            else:
-                anno = dict(name=np.array([]), truncated=np.array([]), occluded=np.array([]), alpha=np.array([]), bbox=np.zeros([0, 4]),
-                            dimensions=np.zeros([0, 3]), location=np.zeros([0, 3]), rotation_y=np.array([]), score=np.array([]))
-            if submission_prefix is not None:
-                with open(f'{submission_prefix}/{sample_idx:06d}.txt', 'w') as f:
-                    bbox, loc, dims = anno['bbox'], anno['location'], anno['dimensions']          # lhw -> hwl
-                    for i in range(len(bbox)):
-                        print('{} -1 -1 {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f}'.format(
-                            anno['name'][i], anno['alpha'][i], bbox[i][0], bbox[i][1], bbox[i][2], bbox[i][3], dims[i][1], dims[i][2],
-                            dims[i][0], loc[i][0], loc[i][1], loc[i][2], anno['rotation_y'][i], anno['score'][i]), file=f)
-            anno['sample_idx'] = np.array([sample_idx] * len(anno['score']), dtype=np.int64)
-            det_annos.append(anno)
-        if pklfile_prefix is not None:
-            out = pklfile_prefix if pklfile_prefix.endswith(('.pkl', '.pickle')) else f'{pklfile_prefix}.pkl'
-            with open(out, 'wb') as f:
-                pickle.dump(det_annos, f)
-        return det_annos
-
-    def convert_valid_bboxes(self, box_dict, info):
-        from .box3d import CameraInstance3DBoxes, points_cam2img
-        box_preds, scores, labels = box_dict['boxes_3d'], box_dict['scores_3d'], box_dict['labels_3d']
-        sample_idx = info['image']['image_idx']
-        box_preds.limit_yaw(offset=0.5, period=np.pi * 2)
-        empty = dict(bbox=np.zeros([0, 4]), box3d_camera=np.zeros([0, 7]), box3d_lidar=np.zeros([0, 7]), scores=np.zeros([0]),
-                     label_preds=np.zeros([0, 4]), sample_idx=sample_idx)
-        if len(box_preds) == 0:
-            return empty
-        rect = info['calib']['R0_rect'].astype(np.float32)
-        Trv2c = info['calib']['Tr_velo_to_cam'].astype(np.float32)
-        P2 = box_preds.tensor.new_tensor(info['calib']['P2'].astype(np.float32))
-        img_shape = info['image']['image_shape']
-        cam = CameraInstance3DBoxes(lidar_boxes_to_camera(box_preds.tensor, rect @ Trv2c), box_dim=box_preds.tensor.shape[-1])
-        box_corners_in_image = points_cam2img(cam.corners, P2)
-        minxy, maxxy = torch.min(box_corners_in_image, dim=1)[0], torch.max(box_corners_in_image, dim=1)[0]
-        box_2d_preds = torch.cat([minxy, maxxy], dim=1)
-        image_shape = box_preds.tensor.new_tensor(img_shape)
-        valid_cam_inds = ((box_2d_preds[:, 0] < image_shape[1]) & (box_2d_preds[:, 1] < image_shape[0]) &
-                          (box_2d_preds[:, 2] > 0) & (box_2d_preds[:, 3] > 0))
-        limit_range = box_preds.tensor.new_tensor(self.pcd_limit_range)
-        center = box_preds.tensor[:, :3]              # ``center`` of a LiDAR box is its bottom centre (base_box3d.py:96-103)
-        valid_inds = valid_cam_inds & ((center > limit_range[:3]) & (center < limit_range[3:])).all(-1)
-        if valid_inds.sum() > 0:
-            return dict(bbox=box_2d_preds[valid_inds, :].numpy(), box3d_camera=cam.tensor[valid_inds].numpy(),
-                        box3d_lidar=box_preds.tensor[valid_inds].numpy(), scores=scores[valid_inds].numpy(),
-                        label_preds=labels[valid_inds].numpy(), sample_idx=sample_idx)
-        return empty

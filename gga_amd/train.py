@@ -274,6 +274,8 @@ class Runner:
                                             mc.get('cyclic_times', 1), mc.get('step_ratio_up', 0.4))
         self.iter = 0
         self.epoch = 0              # finished epochs (train_epochs / resume)
+        self.hook_msgs = {}         # mmcv's ``runner.meta['hook_msgs']``: best_score / best_ckpt of the validation hook
+        self.eval_history = []      # (epoch, dict of the values ``evaluate`` returned) per validation pass
         self.log_interval = (cfg.get('log_config') or {}).get('interval', 50)
         # Arithmetic of the matrix kernels for the train step (dense_conv.PLANES): the two-fp16-plane form, watched by
         # the range guard - armed for iteration 0 and every `range_check_interval` iterations after it; when an operand of
@@ -524,6 +526,8 @@ class Runner:
         # `step`) and whether its range guard has fallen back: resume() restores both
         meta.update(epoch=self.epoch, iter=self.iter, time=time.asctime(), gga_amd_planes=int(self.planes),
                     gga_amd_fell_back=bool(self.fell_back))
+        if self.hook_msgs:
+            meta['hook_msgs'] = dict(self.hook_msgs)
         classes = getattr(self.raw_model, 'CLASSES', None)
         if classes is not None:
             meta['CLASSES'] = classes
@@ -576,10 +580,11 @@ class Runner:
             self.planes = 3
             self.fell_back = dense_conv.FELL_BACK = True
         self._guard_next = True
+        self.hook_msgs = dict(ckpt['meta'].get('hook_msgs') or {})
         return ckpt['meta']
 
     def train_epochs(self, data_loader, max_epochs, work_dir=None, checkpoint_config=None, logger=None, to_inputs=None,
-                     after_iter=None):
+                     after_iter=None, after_epoch=None):
         """The epoch loop of the reference's ``EpochBasedRunner.run`` with the hooks the GGA configs register: sampler
         re-seeded per epoch (``DistSamplerSeedHook``), one ``step`` per loaded batch - the next batch is fetched and its
         points uploaded while this one is stepped, so its point-only front overlaps the step (``prefetch``) -, a
@@ -587,7 +592,9 @@ class Runner:
 
         ``loop_seconds`` accumulates where the loop's host time goes: ``fetch`` (waiting in ``next(loader)``: the data side
         is late), ``inputs`` (unpacking + the points' upload), ``step`` (queueing the step); ``after_iter(runner, n)`` is
-        called after every iteration (bench.py resets / reads the counters there)."""
+        called after every iteration (bench.py resets / reads the counters there). ``after_epoch(runner)`` is called when an
+        epoch has been counted, before its checkpoint is written (the validation hook: ``epoch_N.pth`` then carries the best
+        score up to and including epoch N)."""
         from .loader import PointUploader, to_step_inputs
         if to_inputs is None:
             on_gpu = self.device.type == 'cuda'
@@ -642,6 +649,8 @@ class Runner:
                     logger(f'epoch {self.epoch + 1} iter {n}/{len(data_loader)} lr {self.optimizer.param_groups[0]["lr"]:.3e} '
                            f'time {(time.time() - t0) / n:.3f}s  ' + ' '.join(f'{k}={v:.4f}' for k, v in vals.items()))
             self.epoch += 1
+            if after_epoch is not None:
+                after_epoch(self)
             last = self.epoch == max_epochs
             if out_dir and ((interval > 0 and self.epoch % interval == 0) or (save_last and last)) and _is_rank0():
                 self.save_checkpoint(out_dir, save_optimizer=ck.get('save_optimizer', True))
@@ -652,6 +661,198 @@ class Runner:
                             os.remove(old)
         return out
 
+
+
+# ---- in-training validation. The reference's train entry registers mmdet's ``EvalHook`` / ``DistEvalHook`` on ``cfg.data.val``
+# and ``cfg.evaluation`` (mmdet3d/apis/train.py:288-308 - the wiring is what the reference pins). The hooks themselves are
+# mmcv's / mmdet's (third-party, not in the tree): the behaviour below is this project's definition - restated, parity unpinned.
+EVAL_HOOK_KEYS = ('interval', 'start', 'by_epoch', 'save_best', 'rule', 'tmpdir', 'gpu_collect')
+_GREATER_KEYS, _LESS_KEYS = ('acc', 'AR', 'AP', 'mAP'), ('loss', )
+
+
+def should_evaluate(epoch, interval=1, start=None):
+    """After train epoch ``epoch`` (1-based): every ``interval`` epochs, counted from ``start`` when given."""
+    if start is None:
+        return epoch % interval == 0
+    return epoch >= start and (epoch - start) % interval == 0
+
+
+def infer_rule(key, rule=None):
+    """'greater' / 'less' for the ``save_best`` key: ``rule`` if given, else greater for a key that contains AP, mAP, AR or acc,
+    less for one that contains loss; anything else is a ValueError."""
+    if rule is not None:
+        if rule not in ('greater', 'less'):
+            raise ValueError(f"rule must be 'greater' or 'less', got {rule!r}")
+        return rule
+    if any(k in key for k in _GREATER_KEYS):
+        return 'greater'
+    if any(k in key for k in _LESS_KEYS):
+        return 'less'
+    raise ValueError(f'cannot infer the rule of save_best={key!r} (no AP / mAP / AR / acc / loss in it): give rule=')
+
+
+def evaluate_kwargs(eval_cfg):
+    """``cfg.evaluation`` without the hook's own keys and without ``pipeline`` (only ``show`` reads it): what goes to
+    ``dataset.evaluate``."""
+    return {k: v for k, v in dict(eval_cfg or {}).items() if k not in EVAL_HOOK_KEYS and k != 'pipeline'}
+
+
+class _RngState:
+    """python / numpy / torch-CPU / torch-device generator states, taken and put back around a validation pass."""
+
+    def __init__(self, device):
+        import random
+        import numpy as np
+        self.device = device if (device is not None and device.type == 'cuda') else None
+        self.py, self.np, self.cpu = random.getstate(), np.random.get_state(), torch.get_rng_state()
+        self.dev = torch.cuda.get_rng_state(self.device) if self.device is not None else None
+
+    def restore(self):
+        import random
+        import numpy as np
+        random.setstate(self.py)
+        np.random.set_state(self.np)
+        torch.set_rng_state(self.cpu)
+        if self.dev is not None:
+            torch.cuda.set_rng_state(self.dev, self.device)
+
+
+class EvalHook:
+    """Validation after train epochs (restated, parity unpinned - see above). After epoch ``e`` with
+    ``should_evaluate(e, interval, start)``: ``apis.single_gpu_test`` (``multi_gpu_test`` with ``tmpdir`` / ``gpu_collect`` when
+    ``distributed``, after the BatchNorm running statistics were broadcast from rank 0 - DDP runs with
+    ``broadcast_buffers=False``) on the runner's arithmetic, model in ``eval()`` and back in ``train()``; rank 0 then calls
+    ``dataset.evaluate(results, logger=..., **evaluate_kwargs(cfg.evaluation))``, logs the values on one line and appends
+    ``(epoch, values)`` to ``runner.eval_history``. ``save_best``: the key to watch ('auto': the first one returned; a key without its
+    ``pts_bbox/`` prefix names the one value that ends with it); on a new
+    best rank 0 writes ``best_{key, '/' -> '_'}_epoch_{e}.pth`` through ``Runner.save_checkpoint`` and removes the previous
+    best file; ``best_score`` / ``best_ckpt`` travel in the checkpoints' ``meta['hook_msgs']``. mmcv's initial evaluation when
+    a run is resumed past ``start`` is left out: the first evaluation of a resumed run is the next scheduled one.
+
+    Training is not disturbed: the generator states (python, numpy, torch CPU and device) are put back after the pass, the val
+    loader draws from a generator of its own, and nothing of the runner's step state (prefetched inputs, range-guard schedule)
+    is touched. The weight bank's operands are a function of the weights alone - a refresh the pass triggers is the one the next
+    train step would have made."""
+
+    def __init__(self, dataloader, interval=1, start=None, by_epoch=True, save_best=None, rule=None, tmpdir=None, gpu_collect=False,
+                 distributed=False, out_dir=None, logger=None, **eval_kwargs):
+        if not by_epoch:
+            raise NotImplementedError('configs/gga train with the EpochBasedRunner: by_epoch=False is not supported')
+        if int(interval) <= 0:
+            raise ValueError(f'interval must be positive, got {interval}')
+        if start is not None and start < 0:
+            raise ValueError(f'start must be None or non-negative, got {start}')
+        self.dataloader, self.interval, self.start = dataloader, int(interval), start
+        self.save_best, self.rule = save_best, None
+        if save_best is not None:
+            if not isinstance(save_best, str):
+                raise ValueError(f'save_best must be a key or "auto", got {save_best!r}')
+            if save_best != 'auto':
+                self.rule = infer_rule(save_best, rule)
+            elif rule is not None:
+                self.rule = infer_rule('', rule)
+        self.tmpdir, self.gpu_collect, self.distributed = tmpdir, gpu_collect, distributed
+        self.out_dir, self.logger = out_dir, logger
+        self.eval_kwargs = evaluate_kwargs(eval_kwargs)
+        self._remove = lambda path: os.remove(path) if os.path.isfile(path) else None
+
+    def _say(self, msg):
+        if self.logger is not None:
+            self.logger(msg)
+
+    def after_train_epoch(self, runner):
+        if not should_evaluate(runner.epoch, self.interval, self.start):
+            return None
+        from . import apis
+        model = runner.raw_model
+        rng = _RngState(runner.device)
+        if self.distributed:            # DistEvalHook._broadcast_bn_buffer: every rank tests with rank 0's running statistics
+            for m in model.modules():
+                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.track_running_stats:
+                    dist.broadcast(m.running_var, 0)
+                    dist.broadcast(m.running_mean, 0)
+        try:
+            with torch.no_grad():
+                if self.distributed:
+                    results = apis.multi_gpu_test(model, self.dataloader, self.tmpdir, self.gpu_collect, runner.device, planes=runner.planes)
+                else:
+                    results = apis.single_gpu_test(model, self.dataloader, runner.device, planes=runner.planes)
+        finally:
+            model.train()
+        values = None
+        if results is not None and _is_rank0():
+            log = self.logger
+            kwargs = dict(self.eval_kwargs)
+            if runner.device.type == 'cuda':
+                kwargs.setdefault('device', str(runner.device))
+            values = self.dataloader.dataset.evaluate(results, logger=_LoggerAdapter(log) if callable(log) else log, **kwargs)
+            self._say(f'Epoch(val) [{runner.epoch}]  ' + ', '.join(f'{k}: {v:.4f}' if isinstance(v, float) else f'{k}: {v}'
+                                                                 for k, v in values.items()))
+            runner.eval_history.append((runner.epoch, dict(values)))
+            if self.save_best is not None:
+                self.update_best(runner, values)
+        rng.restore()
+        return values
+
+    def update_best(self, runner, values):
+        """The ``save_best`` bookkeeping after one evaluation: a new best is saved (and the previous best file removed)."""
+        if not values:
+            return False
+        key = self.save_best
+        if key == 'auto':
+            key = self.save_best = next(iter(values))
+            if self.rule is None:
+                self.rule = infer_rule(key)
+        if key not in values:
+            # a detector's results come per branch (``pts_bbox``) and ``evaluate`` prefixes its keys with the branch's name: the
+            # bare key names the one value that ends with it
+            tails = [k for k in values if k.endswith('/' + key)]
+            if len(tails) != 1:
+                raise KeyError(f'save_best={key!r} is not among the evaluated values {list(values)}')
+            key = self.save_best = tails[0]
+        score = values[key]
+        best = runner.hook_msgs.get('best_score')
+        if best is not None and not (score > best if self.rule == 'greater' else score < best):
+            return False
+        out_dir = self.out_dir
+        if not out_dir:
+            raise ValueError('save_best needs a work_dir (or checkpoint_config.out_dir) to write the best checkpoint to')
+        name = 'best_{}_epoch_{}.pth'.format(key.replace('/', '_'), runner.epoch)
+        previous = runner.hook_msgs.get('best_ckpt')
+        runner.hook_msgs['best_score'] = score
+        runner.hook_msgs['best_ckpt'] = os.path.join(out_dir, name)
+        runner.save_checkpoint(out_dir, filename_tmpl=name, create_symlink=False)
+        if previous and previous != runner.hook_msgs['best_ckpt']:
+            self._remove(previous)
+        self._say(f'Now best checkpoint is saved as {name}. Best {key} is {score:0.4f} at {runner.epoch} epoch.')
+        return True
+
+
+class _LoggerAdapter:
+    """A ``logger(msg)`` callable behind the ``.info`` interface ``dataset.evaluate`` logs through."""
+
+    def __init__(self, fn):
+        self.info = fn
+
+
+def build_eval_hook(cfg, distributed, logger=None, out_dir=None):
+    """The ``validate`` branch of the reference's train entry (apis/train.py:288-308): ``cfg.data.val`` in test mode, a loader
+    with ``val_samples_per_gpu`` frames per batch, ``cfg.data.workers_per_gpu`` workers, no shuffling, sharded when
+    ``distributed``, drawing from a generator of its own; the hook gets ``cfg.evaluation``."""
+    from .loader import build_dataloader, build_dataset
+    if 'val' not in cfg.data or not cfg.data['val']:
+        raise KeyError('validate=True needs a data.val section in the config')
+    val_samples_per_gpu = cfg.data['val'].pop('samples_per_gpu', 1)
+    val_cfg = cfg.data['val']
+    val_cfg['test_mode'] = True
+    val_dataset = build_dataset(val_cfg)
+    gen = torch.Generator()
+    gen.manual_seed(int(cfg.get('seed') or 0))
+    val_loader = build_dataloader(val_dataset, val_samples_per_gpu, cfg.data['workers_per_gpu'], dist=distributed, shuffle=False,
+                                  generator=gen)
+    eval_cfg = dict(cfg.get('evaluation') or {})
+    eval_cfg['by_epoch'] = True
+    return EvalHook(val_loader, distributed=distributed, out_dir=out_dir, logger=logger, **eval_cfg)
 
 
 def _is_rank0():
@@ -680,12 +881,9 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     """``mmdet3d/apis/train.py:180-322`` for the GGA configs: loaders from ``cfg.data`` (``samples_per_gpu`` /
     ``workers_per_gpu``, sharded over the ranks when ``distributed``, seeded with ``cfg.seed``), the DDP wrap, optimizer /
     clipping / cyclic schedules (``Runner``), ``checkpoint_config``, ``resume_from`` / ``auto_resume`` / ``load_from``, then
-    ``cfg.workflow``'s train epochs. ``validate`` (the KITTI AP evaluation hook) is outside the hot path: refused loudly.
-    -> the ``Runner`` after training."""
+    ``cfg.workflow``'s train epochs. ``validate``: the evaluation hook on ``cfg.data.val`` / ``cfg.evaluation``
+    (apis/train.py:288-308; ``EvalHook``) - its results are in ``runner.eval_history``. -> the ``Runner`` after training."""
     from .loader import build_dataloader
-    if validate:
-        raise NotImplementedError('the in-training evaluation hook is out of scope: run with validate=False and evaluate the '
-                                  'checkpoint with tools/generate_pseudo_labels_gga.py --eval-options kitti_ap=True')
     dataset = dataset[0] if isinstance(dataset, (list, tuple)) else dataset
     data = cfg.data
     if 'imgs_per_gpu' in data:                    # mmdet < 2.0 spelling
@@ -703,6 +901,9 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     runner = Runner(model, cfg, max_iters=max_epochs * len(loader), distributed=distributed, device=device,
                     iters_per_epoch=len(loader))
     work_dir = cfg.get('work_dir')
+    eval_hook = None
+    if validate:
+        eval_hook = build_eval_hook(cfg, distributed, logger=logger, out_dir=(cfg.get('checkpoint_config') or {}).get('out_dir') or work_dir)
     resume_from = cfg.get('resume_from')
     if resume_from is None and cfg.get('auto_resume') and work_dir:
         resume_from = find_latest_checkpoint(work_dir)
@@ -711,5 +912,5 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     elif cfg.get('load_from'):
         runner.load_checkpoint(cfg.load_from)
     runner.train_epochs(loader, max_epochs, work_dir=work_dir, checkpoint_config=cfg.get('checkpoint_config'), logger=logger,
-                        after_iter=after_iter)
+                        after_iter=after_iter, after_epoch=eval_hook.after_train_epoch if eval_hook is not None else None)
     return runner

@@ -814,6 +814,26 @@ int gga_kitti_eval_stats(const void* overlaps, int overlaps_f64, const int64_t* 
                          int32_t* tp_det, int64_t* counts, double* similarity, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* KITTI result formatting of a whole test run in one launch: `convert_valid_bboxes` + `bbox2result_kitti`
+ * (mmdet3d/datasets/kitti_dataset_GGA_train.py:453-566,680-761) for LiDAR detections. boxes [n_dets,7] f32 (x, y, z_bottom,
+ * dx, dy, dz, yaw), scores [n_dets] f32, labels [n_dets] i64, concatenated over frames with frame_offsets [n_frames+1]. Per
+ * frame: lidar2cam [n_frames,4,4] f32 = R0_rect @ Tr_velo_to_cam (formed by the caller in float32), p2 [n_frames,4,4] f32,
+ * image_hw [n_frames,2] i32 = (height, width). limit_range_host: the six floats of pcd_limit_range (HOST pointer).
+ * Per detection, float32 in the host path's operation order: yaw limited (offset 0.5, period 2 pi), the camera box, its eight
+ * corners projected by p2, the unclipped 2D box, valid = (2D box meets the image) and (bottom centre strictly inside the
+ * range), the 2D box clipped to the image, alpha = -atan2(-y, x) + rotation_y.
+ * out_yaw [n_dets]: the limited yaw of EVERY detection in input order (the in-place side effect of limit_yaw).
+ * The valid detections of frame f are written, in their original order, to rows frame_offsets[f] ..
+ * frame_offsets[f] + valid_counts[f] of out_cols [n_dets, GGA_KITTI_FORMAT_COLS] f32 = bbox (4), dimensions (3), location (3),
+ * rotation_y, alpha, score, limited-yaw LiDAR box (7) and out_labels [n_dets] i64; the other rows are not written.
+ * valid_counts [n_frames] i32. Any number of detections per frame, 0 included; a frame whose offsets do not fit n_dets gets
+ * count 0 and nothing written. */
+#define GGA_KITTI_FORMAT_COLS 20
+int gga_kitti_format_dets(const float* boxes, const float* scores, const int64_t* labels, int64_t n_dets,
+                          const int64_t* frame_offsets, int n_frames, const float* lidar2cam, const float* p2,
+                          const int32_t* image_hw, const float* limit_range_host, float* out_cols, int64_t* out_labels,
+                          float* out_yaw, int32_t* valid_counts, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Offline GGA label generation primitives,             */
 /* tools/data_converter/utils_gga.py. float64, reference operation order.       */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python tools/train.py <config> [--work-dir D] [--resume-from F] [--auto-resume] [--seed N] [--launcher none|pytorch]`` -
+"""``python tools/train.py <config> [--work-dir D] [--resume-from F] [--auto-resume] [--validate] [--seed N] [--launcher none|pytorch]`` -
 the train entry of the reference (tools/train.py:118-263, started per GPU by tools/dist_train.sh:10-20 through
 ``torch.distributed.launch``) for one process per MI355X:
 
@@ -7,7 +7,10 @@ the train entry of the reference (tools/train.py:118-263, started per GPU by too
 
 Config keys read: ``model``, ``data.train`` (+ ``samples_per_gpu`` / ``workers_per_gpu``), ``optimizer``, ``optimizer_config``,
 ``lr_config``, ``momentum_config``, ``runner.max_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``,
-``resume_from`` / ``load_from``, ``seed``. Validation hooks are not part of the path (``--no-validate`` is the only mode)."""
+``resume_from`` / ``load_from``, ``seed``; with ``--validate`` also ``data.val`` (+ its ``samples_per_gpu``) and ``evaluation``
+(``interval``, ``start``, ``save_best``, ``rule``, ``tmpdir``, ``gpu_collect``; the rest goes to the dataset's ``evaluate``): the
+KITTI AP of the val split after the scheduled epochs (``gga_amd.train.EvalHook``). Validation is opt-in here - the reference
+validates unless ``--no-validate`` is given; without ``--validate`` this tool trains exactly as it did before the hook existed."""
 import argparse
 import os
 import sys
@@ -22,7 +25,8 @@ def main():
     ap.add_argument('--work-dir')
     ap.add_argument('--resume-from')
     ap.add_argument('--auto-resume', action='store_true')
-    ap.add_argument('--no-validate', action='store_true', help='(always on: the in-training evaluation hook is out of scope; KITTI AP runs after a test run)')
+    ap.add_argument('--validate', action='store_true', help='evaluate data.val after the epochs cfg.evaluation schedules (KITTI AP; off by default)')
+    ap.add_argument('--no-validate', action='store_true', help='do not evaluate during training (the default; accepted for the reference\'s command lines)')
     ap.add_argument('--gpu-id', type=int, default=0)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--diff-seed', action='store_true', help='a different seed per rank')
@@ -39,7 +43,11 @@ def main():
     from gga_amd.loader import build_dataset
     from gga_amd.train import init_dist, setup_multi_processes, train_detector
 
+    if args.validate and args.no_validate:
+        ap.error('--validate and --no-validate exclude each other')
     cfg = Config.fromfile(args.config)
+    if args.validate and not (cfg.get('data') or {}).get('val'):
+        ap.error(f'--validate: {args.config} has no data.val section to evaluate on')
     setup_multi_processes(cfg)
     cfg.work_dir = args.work_dir or cfg.get('work_dir') or os.path.join('./work_dirs', os.path.splitext(os.path.basename(args.config))[0])
     if args.resume_from:
@@ -81,7 +89,7 @@ def main():
     dataset = build_dataset(cfg.data['train'])
     model.CLASSES = dataset.CLASSES
     model = to_channels_last(model.to(device))
-    train_detector(model, dataset, cfg, distributed=distributed, validate=False, logger=logger, device=device)
+    train_detector(model, dataset, cfg, distributed=distributed, validate=args.validate, logger=logger, device=device)
 
 
 if __name__ == '__main__':
