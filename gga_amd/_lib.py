@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _lib = None
 
@@ -137,6 +137,9 @@ SIGNATURES = {
     'gga_kitti_eval_stats': (i32, [vp, i32, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32,
                                    i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_kitti_format_dets': (i32, [vp, vp, vp, i64, vp, i32, vp, vp, vp, C.POINTER(C.c_float * 6), vp, vp, vp, vp, vp]),
+    'gga_indoor_eval_match': (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]),
+    'gga_indoor_eval_workspace_bytes': (sz, [i64, i32]),
+    'gga_indoor_eval_assign': (i32, [vp, vp, vp, vp, i64, vp, i64, i32, C.POINTER(C.c_float * 8), i32, vp, vp, sz, vp]),
     'gga_centerpoint_detect_workspace_bytes': (sz, [i32, i32]),
     'gga_centerpoint_detect': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, C.c_float, i32, C.c_float, vp, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_points_in_boxes': (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),

@@ -32,8 +32,8 @@ def rotation_3d_in_axis_z(points, angles):
 
 
 class DepthInstance3DBoxes:
-    """The part of ``DepthInstance3DBoxes`` (core/bbox/structures/depth_box3d.py) the FCAF3D head touches: (x, y, z, dx, dy,
-    dz[, yaw]) with the origin converted to the bottom centre (0.5, 0.5, 0)."""
+    """The part of ``DepthInstance3DBoxes`` (core/bbox/structures/depth_box3d.py) the FCAF3D head, the SUN RGB-D dataset and
+    the indoor evaluation touch: (x, y, z, dx, dy, dz[, yaw]) with the origin converted to the bottom centre (0.5, 0.5, 0)."""
 
     def __init__(self, tensor, box_dim=7, with_yaw=True, origin=(0.5, 0.5, 0)):
         tensor = torch.as_tensor(tensor, dtype=torch.float32)
@@ -60,14 +60,63 @@ class DepthInstance3DBoxes:
         return gc
 
     volume = property(lambda self: self.tensor[:, 3] * self.tensor[:, 4] * self.tensor[:, 5])
+    bev = property(lambda self: self.tensor[:, [0, 1, 3, 4, 6]])
+    bottom_height = property(lambda self: self.tensor[:, 2])
+    top_height = property(lambda self: self.tensor[:, 2] + self.tensor[:, 5])
+    device = property(lambda self: self.tensor.device)
 
     def __len__(self):
         return self.tensor.shape[0]
 
-    def to(self, device):
+    def __getitem__(self, item):
+        """base_box3d.py:303-337: one box for an int, else what indexing the rows gives."""
+        t = self.tensor[item].view(1, -1) if isinstance(item, int) else self.tensor[item]
+        assert t.dim() == 2, f'Indexing on Boxes with {item} failed to return a matrix!'
+        return self._wrap(t)
+
+    def _wrap(self, tensor):
         out = object.__new__(type(self))
-        out.tensor, out.box_dim, out.with_yaw = self.tensor.to(device), self.box_dim, self.with_yaw
+        out.tensor, out.box_dim, out.with_yaw = tensor, self.box_dim, self.with_yaw
         return out
+
+    def to(self, device):
+        return self._wrap(self.tensor.to(device))
+
+    def new_box(self, data):
+        """base_box3d.py:491-508: a box object of the same kind on the same device from array-like ``data``."""
+        t = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) else data.to(self.tensor.device)
+        return type(self)(t, box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    def convert_to(self, dst, rt_mat=None):
+        """depth_box3d.py ``convert_to``: Depth boxes stay what they are; another mode needs Box3DMode, which is not here."""
+        if dst is not None and dst not in ('Depth', 'DEPTH', 2) and getattr(dst, 'name', None) != 'DEPTH' and dst is not type(self):
+            raise NotImplementedError(f'DepthInstance3DBoxes.convert_to({dst!r}): only the Depth mode is supported')
+        return self
+
+    @classmethod
+    def height_overlaps(cls, boxes1, boxes2, mode='iou'):
+        top = torch.min(boxes1.top_height.view(-1, 1), boxes2.top_height.view(1, -1))
+        bottom = torch.max(boxes1.bottom_height.view(-1, 1), boxes2.bottom_height.view(1, -1))
+        return torch.clamp(top - bottom, min=0)
+
+    @classmethod
+    def overlaps(cls, boxes1, boxes2, mode='iou'):
+        """3D IoU / IoF of two box sets (base_box3d.py:437-489), the BEV part on the HIP rotated-IoU kernel."""
+        assert type(boxes1) == type(boxes2), f'"boxes1" and "boxes2" should be in the same type, got {type(boxes1)} and {type(boxes2)}.'
+        assert mode in ['iou', 'iof']
+        rows, cols = len(boxes1), len(boxes2)
+        if rows * cols == 0:
+            return boxes1.tensor.new(rows, cols)
+        overlaps_h = cls.height_overlaps(boxes1, boxes2)
+        iou2d = ops.box_iou_rotated(boxes1.bev, boxes2.bev)
+        areas1 = (boxes1.bev[:, 2] * boxes1.bev[:, 3]).unsqueeze(1).expand(rows, cols)
+        areas2 = (boxes2.bev[:, 2] * boxes2.bev[:, 3]).unsqueeze(0).expand(rows, cols)
+        overlaps_bev = iou2d * (areas1 + areas2) / (1 + iou2d)
+        overlaps_3d = overlaps_bev.to(boxes1.device) * overlaps_h
+        volume1, volume2 = boxes1.volume.view(-1, 1), boxes2.volume.view(1, -1)
+        if mode == 'iou':
+            return overlaps_3d / torch.clamp(volume1 + volume2 - overlaps_3d, min=1e-8)
+        return overlaps_3d / torch.clamp(volume1, min=1e-8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- losses

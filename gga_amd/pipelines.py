@@ -34,7 +34,7 @@ import torch
 from scipy.spatial.distance import cdist, pdist, squareform
 
 from .box3d import LiDARInstance3DBoxes
-from .points import BasePoints, LiDARPoints
+from .points import BasePoints, DepthPoints, LiDARPoints
 from .registry import OBJECTSAMPLERS, PIPELINES, build_from_cfg
 
 
@@ -91,18 +91,21 @@ class Compose:
 @PIPELINES.register_module()
 class LoadPointsFromFile:
     """transforms: mmdet3d/datasets/pipelines/loading.py LoadPointsFromFile for local ``.bin`` files
-    (float32 rows of ``load_dim`` values) — what the database sampler's ``points_loader`` needs."""
+    (float32 rows of ``load_dim`` values) — what the database sampler's ``points_loader`` and the SUN RGB-D pipelines
+    (``coord_type='DEPTH'``, six columns: x, y, z, r, g, b) need."""
 
     def __init__(self, coord_type='LIDAR', load_dim=6, use_dim=[0, 1, 2], shift_height=False, use_color=False,
                  file_client_args=dict(backend='disk')):
-        assert coord_type == 'LIDAR' and not shift_height and not use_color
+        assert coord_type in ('LIDAR', 'DEPTH') and not shift_height and not use_color
+        self.coord_type = coord_type
         self.load_dim = load_dim
         self.use_dim = list(range(use_dim)) if isinstance(use_dim, int) else list(use_dim)
         assert max(self.use_dim) < load_dim
 
     def __call__(self, results):
         pts = np.fromfile(results['pts_filename'], dtype=np.float32).reshape(-1, self.load_dim)[:, self.use_dim]
-        results['points'] = LiDARPoints(pts, points_dim=pts.shape[-1], attribute_dims=None)
+        points_class = DepthPoints if self.coord_type == 'DEPTH' else LiDARPoints
+        results['points'] = points_class(pts, points_dim=pts.shape[-1], attribute_dims=None)
         return results
 
 
@@ -534,6 +537,51 @@ class RandomFlip3D:
 
 
 @PIPELINES.register_module()
+class PointSample:
+    """transforms_3d.py:1024-1121: ``num_points`` points drawn from the scene - with replacement when it has fewer (or
+    ``replace``), else without; with ``sample_range`` the points farther than that are kept first. The draws from ``np.random``
+    come in the reference's order: ``choice`` of the far points when there are too many, ``choice`` of the rest, ``shuffle``."""
+
+    def __init__(self, num_points, sample_range=None, replace=False):
+        self.num_points, self.sample_range, self.replace = num_points, sample_range, replace
+
+    def _points_random_sampling(self, points, num_samples, sample_range=None, replace=False, return_choices=False):
+        if not replace:
+            replace = points.shape[0] < num_samples
+        point_range = range(len(points))
+        if sample_range is not None and not replace:
+            dist = np.linalg.norm(points.tensor.numpy(), axis=1)
+            far_inds, near_inds = np.where(dist >= sample_range)[0], np.where(dist < sample_range)[0]
+            if len(far_inds) > num_samples:
+                far_inds = np.random.choice(far_inds, num_samples, replace=False)
+            point_range = near_inds
+            num_samples -= len(far_inds)
+        choices = np.random.choice(point_range, num_samples, replace=replace)
+        if sample_range is not None and not replace:
+            choices = np.concatenate((far_inds, choices))
+            np.random.shuffle(choices)
+        return (points[choices], choices) if return_choices else points[choices]
+
+    def __call__(self, d):
+        d['points'], choices = self._points_random_sampling(d['points'], self.num_points, self.sample_range, self.replace,
+                                                            return_choices=True)
+        for k in ('pts_instance_mask', 'pts_semantic_mask'):
+            if d.get(k) is not None:
+                d[k] = d[k][choices]
+        return d
+
+
+@PIPELINES.register_module()
+class IndoorPointSample(PointSample):
+    """transforms_3d.py:1133-1146: the deprecated name of ``PointSample``."""
+
+    def __init__(self, *args, **kwargs):
+        import warnings
+        warnings.warn('IndoorPointSample is deprecated in favor of PointSample')
+        super().__init__(*args, **kwargs)
+
+
+@PIPELINES.register_module()
 class MultiScaleFlipAug3D:
     """Test-time augmentation wrapper: the inner transforms run once per (image scale, point scale, flip) combination on a deep
     copy of the sample, and the results are regrouped key by key into lists - one entry per combination (exactly one for the
@@ -579,8 +627,8 @@ class DefaultFormatBundle3D:
             if 'gt_labels_3d' in d:
                 d['gt_labels_3d'] = DC(to_tensor(d['gt_labels_3d']))
             if 'gt_bboxes_3d' in d:
-                b = d['gt_bboxes_3d']
-                d['gt_bboxes_3d'] = DC(b, cpu_only=True) if isinstance(b, LiDARInstance3DBoxes) else DC(to_tensor(b))
+                b = d['gt_bboxes_3d']          # a box structure (LiDAR or Depth) travels as it is, an array as a tensor
+                d['gt_bboxes_3d'] = DC(b, cpu_only=True) if hasattr(b, 'tensor') else DC(to_tensor(b))
         return d
 
 

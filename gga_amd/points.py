@@ -1,4 +1,4 @@
-"""``LiDARPoints`` — the slice of the reference's point structure the GGA train pipeline touches
+"""``LiDARPoints`` / ``DepthPoints`` — the slice of the reference's point structure the GGA train pipeline touches
 (mmdet3d/core/points/base_points.py:11-440, lidar_points.py): ``tensor [N, points_dim]``,
 ``coord``, ``in_range_3d`` (strict inequalities, :203-225), ``shuffle`` (``torch.randperm``,
 :135-143), ``cat`` (:356-377), indexing, ``new_point``."""
@@ -83,6 +83,14 @@ class BasePoints:
 
 
 class LiDARPoints(BasePoints):
+    def __init__(self, tensor, points_dim=3, attribute_dims=None):
+        super().__init__(tensor, points_dim=points_dim, attribute_dims=attribute_dims)
+        self.rotation_axis = 2
+
+
+class DepthPoints(BasePoints):
+    """depth_points.py: points in depth coordinates (indoor scenes); rotation about z like the LiDAR points."""
+
     def __init__(self, tensor, points_dim=3, attribute_dims=None):
         super().__init__(tensor, points_dim=points_dim, attribute_dims=attribute_dims)
         self.rotation_axis = 2

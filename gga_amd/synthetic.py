@@ -558,6 +558,87 @@ def make_indoor_batch(batch_size, start=0, rank=0, device=None, n_points=50000, 
     return out
 
 
+def write_sunrgbd_tree(root, n_frames, seed=5100, n_points=2000, n_obj_range=(0, 9), empty_frames=(1, )):
+    """Writes what ``SUNRGBDDataset`` reads (reference: tools/data_converter/sunrgbd_data_utils.py ``get_infos``) for
+    ``n_frames`` synthetic rooms under ``root`` - the analogue of ``write_kitti_tree``:
+
+        points/%06d.bin                         [n_points,6] f32: x, y, z (depth coordinates, metres), r, g, b in [0, 1]
+        sunrgbd_infos_train.pkl / _val.pkl      the info list: point_cloud, image, pts_path, calib (K, Rt), annos
+
+    ``annos``: ``gt_num``, ``name``, ``class``, ``gt_boxes_upright_depth`` [k,7] (gravity centre, sizes, yaw), ``location``,
+    ``dimensions`` (half sizes), ``rotation_y``, ``index``, ``bbox`` [k,4]; a frame without objects has ``gt_num = 0`` only, as
+    the converter leaves it. The frames listed in ``empty_frames`` have no objects. Both pickles hold the same frames.
+    Deterministic in ``seed``. -> (train info path, val info path)."""
+    import os
+    import pickle
+    os.makedirs(os.path.join(root, 'points'), exist_ok=True)
+    names = np.array(INDOOR_CLASSES)
+    infos = []
+    for i in range(n_frames):
+        rng = np.random.default_rng(seed + i)
+        n_obj = 0 if i in empty_frames else int(rng.integers(max(n_obj_range[0], 1), n_obj_range[1] + 1))
+        size = rng.uniform([0.4, 0.4, 0.4], [2.0, 1.6, 1.2], (n_obj, 3))
+        ctr = np.concatenate([rng.uniform(-2.0, 2.0, (n_obj, 2)), size[:, 2:] / 2 + rng.uniform(0, 0.3, (n_obj, 1))], 1)
+        yaw = rng.uniform(-np.pi / 2, np.pi / 2, (n_obj, 1))
+        labels = rng.integers(0, len(INDOOR_CLASSES), n_obj)
+        n_bg = n_points // 2 if n_obj else n_points
+        pts = [np.concatenate([rng.uniform(-2.5, 2.5, (n_bg, 2)), rng.normal(0, 0.004, (n_bg, 1))], 1)]
+        for k in range(n_obj):
+            n_k = (n_points - n_bg) // n_obj if k < n_obj - 1 else n_points - n_bg - (n_points - n_bg) // n_obj * (n_obj - 1)
+            u = rng.uniform(-0.5, 0.5, (n_k, 3)) * size[k]
+            c, s_ = np.cos(yaw[k, 0]), np.sin(yaw[k, 0])
+            pts.append(np.stack([u[:, 0] * c - u[:, 1] * s_ + ctr[k, 0], u[:, 0] * s_ + u[:, 1] * c + ctr[k, 1], u[:, 2] + ctr[k, 2]], 1))
+        xyz = np.concatenate(pts)
+        cloud = np.concatenate([xyz, rng.uniform(0, 1, (len(xyz), 3))], 1).astype(np.float32)
+        cloud[rng.permutation(len(cloud))].tofile(os.path.join(root, 'points', f'{i:06d}.bin'))
+        annos = dict(gt_num=n_obj)
+        if n_obj:
+            boxes = np.concatenate([ctr, size, yaw], 1)
+            annos.update(name=names[labels], **{'class': labels.astype(np.int64)}, gt_boxes_upright_depth=boxes, location=ctr,
+                         dimensions=size / 2, rotation_y=yaw[:, 0], index=np.arange(n_obj, dtype=np.int32),
+                         bbox=np.concatenate([rng.uniform(0, 300, (n_obj, 2)), rng.uniform(320, 500, (n_obj, 2))], 1))
+        infos.append(dict(point_cloud=dict(num_features=6, lidar_idx=i), pts_path=f'points/{i:06d}.bin',
+                          image=dict(image_idx=i, image_shape=np.array([530, 730], np.int32), image_path=f'image/{i:06d}.jpg'),
+                          calib=dict(K=np.array([[529.5, 0, 365.0], [0, 529.5, 265.0], [0, 0, 1]], np.float32), Rt=np.eye(3, dtype=np.float32)),
+                          annos=annos))
+    paths = tuple(os.path.join(root, f'sunrgbd_infos_{split}.pkl') for split in ('train', 'val'))
+    for path in paths:
+        with open(path, 'wb') as f:
+            pickle.dump(infos, f)
+    return paths
+
+
+def make_indoor_eval_case(seed, n_frames, n_classes=10, gt_range=(0, 9), dt_range=(0, 40)):
+    """Seeded SUN RGB-D-shaped ground truths and detections for ``indoor_eval``: per frame ``gt_range`` boxes of random classes
+    and ``dt_range`` detections - most of them a jittered copy of a ground truth of the frame with its class (so every IoU level
+    occurs), the rest free boxes. -> (gt_annos, dt_annos as arrays: list of dict(boxes [k,7] f32 bottom-centre, scores [k] f32,
+    labels [k] i64))."""
+    rng = np.random.default_rng(seed)
+    gts, dts = [], []
+    for _ in range(n_frames):
+        k = int(rng.integers(gt_range[0], gt_range[1] + 1))
+        size = rng.uniform([0.4, 0.4, 0.4], [2.0, 1.6, 1.2], (k, 3))
+        ctr = np.concatenate([rng.uniform(-2.5, 2.5, (k, 2)), size[:, 2:] / 2 + rng.uniform(0, 0.3, (k, 1))], 1)
+        box = np.concatenate([ctr, size, rng.uniform(-np.pi / 2, np.pi / 2, (k, 1))], 1).astype(np.float32)
+        cls = rng.integers(0, n_classes, k).astype(np.int64)
+        gts.append(dict(gt_num=k, gt_boxes_upright_depth=box, **{'class': cls}) if k else dict(gt_num=0))
+        m = int(rng.integers(dt_range[0], dt_range[1] + 1))
+        src = rng.integers(0, max(k, 1), m)
+        near = (rng.random(m) < 0.7) & (k > 0)
+        free_size = rng.uniform([0.4, 0.4, 0.4], [2.0, 1.6, 1.2], (m, 3))
+        free = np.concatenate([rng.uniform(-2.5, 2.5, (m, 2)), rng.uniform(0, 0.3, (m, 1)), free_size, rng.uniform(-np.pi / 2, np.pi / 2, (m, 1))], 1)
+        det = free.copy()
+        if k:
+            bottom = box[src].astype(np.float64)
+            bottom[:, 2] -= bottom[:, 5] / 2
+            jitter = rng.normal(0, 1, (m, 7)) * np.array([0.15, 0.15, 0.05, 0.1, 0.1, 0.05, 0.15]) * rng.uniform(0.1, 2.0, (m, 1))
+            det[near] = (bottom + jitter)[near]
+        det[:, 3:6] = np.maximum(det[:, 3:6], 0.1)
+        labels = np.where(near, cls[src] if k else 0, rng.integers(0, n_classes, m)).astype(np.int64)
+        dts.append(dict(boxes=det.astype(np.float32), scores=rng.uniform(0.01, 1.0, m).astype(np.float32), labels=labels))
+    return gts, dts
+
+
 # ---------------------------------------------------------------------------
 # An on-disk KITTI tree in the layout the GGA train job reads (loader-fed bench / tests)
 # ---------------------------------------------------------------------------

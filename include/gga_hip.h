@@ -835,6 +835,35 @@ int gga_kitti_format_dets(const float* boxes, const float* scores, const int64_t
                           float* out_yaw, int32_t* valid_counts, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Indoor mAP / mAR evaluation (mmdet3d/core/evaluation/indoor_eval.py).       */
+/* ------------------------------------------------------------------------- */
+/* Detections and ground truths are sorted by the caller into (class, frame) segments, segment = class * n_frames + frame,
+ * with device offsets det_offsets / gt_offsets [n_segments+1]; a segment may be empty on either side. Boxes [n,7] f32 =
+ * (x, y, z_bottom, dx, dy, dz, yaw), the DepthInstance3DBoxes tensor with origin (0.5, 0.5, 0).
+ * gga_indoor_eval_match: for every detection iou_max [n_det] f32 = the largest 3D IoU (BaseInstance3DBoxes.overlaps, mode
+ * 'iou', float32: rotated BEV IoU -> BEV overlap iou2d * (a1 + a2) / (1 + iou2d), times the height overlap, over
+ * max(v1 + v2 - overlap, 1e-8)) over the ground truths of its segment and jmax [n_det] i32 = the index of that ground truth
+ * within the segment: the first one that reaches the maximum (eval_det_cls, `if iou > iou_max`). A segment without ground
+ * truths gives -inf and -1. One thread per detection. */
+int gga_indoor_eval_match(const float* det_boxes, const int64_t* det_offsets, int64_t n_det, const float* gt_boxes,
+                          const int64_t* gt_offsets, int64_t n_gt, int n_segments, float* iou_max, int32_t* jmax, void* stream);
+
+/* The TP / FP marking of eval_det_cls for n_thresholds <= GGA_INDOOR_EVAL_MAX_THRESHOLDS IoU thresholds (thresholds_host:
+ * HOST pointer to 8 floats) at once. det_pos [n_det] i32: the position of each detection in the output order - class-major,
+ * within a class by descending score (its class's first position + its rank in the class); positions are distinct. A
+ * detection is a true positive at threshold t when iou_max > t and it has the smallest position among the detections of
+ * its segment with the same jmax and iou_max > t; it is a false positive otherwise (a detection whose best ground truth is
+ * taken does not fall back to another). tp [n_thresholds, n_det] u8, indexed by det_pos: 1 = TP, 0 = FP. One atomicMin per
+ * (threshold, detection) and a compare pass: the result does not depend on scheduling.
+ * workspace: gga_indoor_eval_workspace_bytes. */
+#define GGA_INDOOR_EVAL_MAX_THRESHOLDS 8
+size_t gga_indoor_eval_workspace_bytes(int64_t n_gt, int n_thresholds);
+int gga_indoor_eval_assign(const float* iou_max, const int32_t* jmax, const int32_t* det_pos, const int64_t* det_offsets,
+                           int64_t n_det, const int64_t* gt_offsets, int64_t n_gt, int n_segments,
+                           const float* thresholds_host, int n_thresholds, uint8_t* tp, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Offline GGA label generation primitives,             */
 /* tools/data_converter/utils_gga.py. float64, reference operation order.       */
 /* ------------------------------------------------------------------------- */

@@ -9,7 +9,7 @@ Config keys read: ``model``, ``data.train`` (+ ``samples_per_gpu`` / ``workers_p
 ``lr_config``, ``momentum_config``, ``runner.max_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``,
 ``resume_from`` / ``load_from``, ``seed``; with ``--validate`` also ``data.val`` (+ its ``samples_per_gpu``) and ``evaluation``
 (``interval``, ``start``, ``save_best``, ``rule``, ``tmpdir``, ``gpu_collect``; the rest goes to the dataset's ``evaluate``): the
-KITTI AP of the val split after the scheduled epochs (``gga_amd.train.EvalHook``). Validation is opt-in here - the reference
+KITTI AP (for ``SUNRGBDDataset`` the indoor mAP / mAR) of the val split after the scheduled epochs (``gga_amd.train.EvalHook``). Validation is opt-in here - the reference
 validates unless ``--no-validate`` is given; without ``--validate`` this tool trains exactly as it did before the hook existed."""
 import argparse
 import os

@@ -708,6 +708,180 @@ def golden_kitti_eval(ref):
     print(out['B.coco_result'])
 
 
+INDOOR_EVAL_ABSENT, INDOOR_EVAL_GT_ONLY = 7, 9          # case B: a class nobody has, a class with ground truths only
+
+
+def load_reference_indoor_eval(ref):
+    """indoor_eval.py with the reference's real DepthInstance3DBoxes (base_box3d.py / depth_box3d.py / box_3d_mode.py loaded by
+    path). mmcv.ops.box_iou_rotated is a float32 emulation of the polygon clip: this repository's host restatement
+    (gga_amd.indoor_eval.rotated_iou32) - not independent evidence for the IoU values, which is why every pair is also computed
+    in float64 on the separate clip of tests/_kitti_eval_ref.py; the flags and tables that come out are the reference's own
+    code. print_log prints; terminaltables' AsciiTable is a stand-in that keeps the rows."""
+    from gga_amd.indoor_eval import rotated_iou32
+
+    def box_iou_rotated(b1, b2, mode='iou', aligned=False):
+        n, m = len(b1), len(b2)
+        a = b1.detach().numpy().astype(np.float32)[:, None, :].repeat(m, 1).reshape(-1, 5)
+        b = b2.detach().numpy().astype(np.float32)[None, :, :].repeat(n, 0).reshape(-1, 5)
+        return torch.from_numpy(rotated_iou32(a, b).reshape(n, m))
+
+    ops = sys.modules['mmcv.ops']
+    ops.box_iou_rotated, ops.points_in_boxes_all, ops.points_in_boxes_part = box_iou_rotated, None, None
+    _mod('mmdet3d.core.points')
+    bp = load('mmdet3d.core.points.base_points', 'mmdet3d/core/points/base_points.py')
+    sys.modules['mmdet3d.core.points'].BasePoints = bp.BasePoints
+    st = 'mmdet3d.core.bbox.structures.'
+    load(st + 'base_box3d', 'mmdet3d/core/bbox/structures/base_box3d.py')
+    for name in ('cam_box3d', 'lidar_box3d', 'depth_box3d', 'box_3d_mode'):
+        load(st + name, f'mmdet3d/core/bbox/structures/{name}.py')
+    utils = sys.modules.get('mmcv.utils') or _mod('mmcv.utils')
+    utils.print_log = lambda msg, logger=None: print(msg)
+
+    class AsciiTable:
+        def __init__(self, rows):
+            self.rows, self.inner_footing_row_border = rows, False
+
+        @property
+        def table(self):
+            return '\n'.join(' | '.join(map(str, r)) for r in self.rows)
+    _mod('terminaltables', AsciiTable=AsciiTable)
+    _mod('mmdet3d.core.evaluation')
+    ie = load('mmdet3d.core.evaluation.indoor_eval', 'mmdet3d/core/evaluation/indoor_eval.py')
+    return ie, sys.modules[st + 'depth_box3d'].DepthInstance3DBoxes, sys.modules[st + 'box_3d_mode'].Box3DMode
+
+
+def make_indoor_overlap_case(seed=91):
+    """Case A: aligned (detection, ground truth) pairs of Depth boxes (bottom centre, non-zero yaw) -> (det [n,7] f32, gt [n,7]
+    f32, degenerate [n]): identical boxes and boxes sharing an edge first (degenerate: the clip's answer hangs on the last bit),
+    then nested, disjoint, height-disjoint, and jittered copies at every IoU level."""
+    rng = np.random.default_rng(seed)
+    n = 296
+    size = rng.uniform([0.4, 0.4, 0.4], [2.0, 1.6, 1.2], (n, 3))
+    gt = np.concatenate([rng.uniform(-2.5, 2.5, (n, 2)), rng.uniform(0, 0.3, (n, 1)), size, rng.uniform(-np.pi, np.pi, (n, 1))], 1)
+    gt[:, 6] = np.where(np.abs(gt[:, 6]) < 0.05, 0.3, gt[:, 6])
+    det = gt + rng.normal(0, 1, (n, 7)) * np.array([0.15, 0.15, 0.05, 0.1, 0.1, 0.05, 0.15]) * rng.uniform(0.05, 3.0, (n, 1))
+    det[:, 3:6] = np.maximum(det[:, 3:6], 0.1)
+    far = rng.random(n) < 0.1
+    det[far, :2] += 6.0
+    A = np.array([0.5, -0.25, 0.1, 2.0, 1.0, 0.8, 0.4])
+    c, s_ = np.cos(0.4), np.sin(0.4)
+    special_gt = np.stack([A, A, A, A, A])
+    special_dt = np.stack([A,                                                               # identical
+                           A + [2.0 * c, 2.0 * s_, 0, 0, 0, 0, 0],                           # shares the short edge
+                           A * [1, 1, 1, 0.5, 0.5, 0.5, 1] + [0, 0, 0.1, 0, 0, 0, 0.2],       # nested
+                           A + [5.0, 0, 0, 0, 0, 0, 0.7],                                    # disjoint in the plane
+                           A + [0.1, 0, 2.0, 0, 0, 0, -0.3]])                                # disjoint in height
+    deg = np.zeros(n + 5, bool)
+    deg[:2] = True
+    return np.concatenate([special_dt, det]).astype(np.float32), np.concatenate([special_gt, gt]).astype(np.float32), deg
+
+
+def make_indoor_eval_cases(seed=92):
+    """Cases B and C (array form, see synthetic.make_indoor_eval_case) with the conditions the tests rely on enforced by
+    re-drawing: distinct scores; every detection's best float64 IoU at least MARGIN away from both thresholds and from its
+    runner-up. A best IoU of exactly 0 (the detection meets none of its ground truths) has only exact zeros behind it: such a
+    detection is a false positive whichever ground truth is named, and it is not part of the runner-up condition; a best IoU
+    between 0 and MARGIN is re-drawn."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _indoor_eval_ref as R
+    gts, dts = synthetic.make_indoor_eval_case(seed, 12)
+    rng = np.random.default_rng(seed + 1)
+    gts[3] = dict(gt_num=0)                                                           # a frame without ground truths
+    dts[5] = dict(boxes=np.zeros((0, 7), np.float32), scores=np.zeros(0, np.float32), labels=np.zeros(0, np.int64))   # ... without detections
+    others = [c for c in range(10) if c not in (INDOOR_EVAL_ABSENT, INDOOR_EVAL_GT_ONLY)]
+    for g in gts:
+        if g['gt_num']:
+            g['class'] = np.where(g['class'] == INDOOR_EVAL_ABSENT, others[0], g['class'])
+    for d in dts:
+        swap = np.isin(d['labels'], (INDOOR_EVAL_ABSENT, INDOOR_EVAL_GT_ONLY))
+        d['labels'] = np.where(swap, rng.choice(others, len(swap)), d['labels']).astype(np.int64)
+    gts[0]['class'][-1] = INDOOR_EVAL_GT_ONLY
+    # two detections of frame 0 on the same ground truth, both well above 0.5: the lower-scored one must become a false positive
+    target = R.bottom_centre(gts[0]['gt_boxes_upright_depth'])[0]
+    twins = np.stack([target + [0.02, 0.01, 0, 0, 0, 0, 0.01], target + [-0.03, 0.02, 0.01, 0.02, 0, 0, -0.02]]).astype(np.float32)
+    dts[0] = dict(boxes=np.concatenate([dts[0]['boxes'], twins]), scores=np.concatenate([dts[0]['scores'], [0.9312, 0.9287]]).astype(np.float32),
+                  labels=np.concatenate([dts[0]['labels'], [gts[0]['class'][0]] * 2]).astype(np.int64))
+    redrawn = 0
+    for _ in range(200):
+        scores = np.concatenate([d['scores'] for d in dts])
+        stats = R.best_two64(gts, dts)
+        bad, k = [], 0
+        for f, d in enumerate(dts):
+            for i in range(len(d['labels'])):
+                best, _, second = stats[k]
+                near = any(abs(best - t) < R.MARGIN for t in R.THRESHOLDS) or (best - second < R.MARGIN and best > 0) or 0 < best < R.MARGIN
+                if near or (scores == d['scores'][i]).sum() > 1:
+                    bad.append((f, i))
+                k += 1
+        if not bad:
+            break
+        for f, i in bad:
+            dts[f]['boxes'][i, :2] += rng.normal(0, 0.03, 2).astype(np.float32)
+            dts[f]['scores'][i] = np.float32(rng.uniform(0.01, 1.0))
+            redrawn += 1
+    else:
+        raise AssertionError('could not move every best IoU away from the thresholds and its runner-up')
+    extra = [(2, 2), (8, 3)]                                                           # case C: (frame, detections of the absent class)
+    dts_c = [dict(d) for d in dts]
+    for f, m in extra:
+        size = rng.uniform(0.4, 1.5, (m, 3))
+        box = np.concatenate([rng.uniform(-2, 2, (m, 2)), rng.uniform(0, 0.2, (m, 1)), size, rng.uniform(-1, 1, (m, 1))], 1).astype(np.float32)
+        dts_c[f] = dict(boxes=np.concatenate([dts[f]['boxes'], box]), scores=np.concatenate([dts[f]['scores'], rng.uniform(0.011, 0.99, m)]).astype(np.float32),
+                        labels=np.concatenate([dts[f]['labels'], [INDOOR_EVAL_ABSENT] * m]).astype(np.int64))
+    assert len(np.unique(np.concatenate([d['scores'] for d in dts_c]))) == sum(len(d['scores']) for d in dts_c)
+    return gts, dts, dts_c, redrawn
+
+
+def golden_indoor_eval(ref):
+    """tests/golden/indoor_eval.npz: the reference's ``BaseInstance3DBoxes.overlaps`` on aligned pairs (case A) and its
+    ``indoor_eval`` - ret_dict, recall and precision arrays - on seeded frames (cases B and C), with the inputs. Arrays only."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _indoor_eval_ref as R
+    ie, Boxes, Box3DMode = load_reference_indoor_eval(ref)
+    out = {}
+    # ---- case A
+    det, gt, deg = make_indoor_overlap_case()
+    iou32 = np.concatenate([Boxes.overlaps(Boxes(torch.from_numpy(det[i:i + 64])), Boxes(torch.from_numpy(gt[i:i + 64]))).numpy().diagonal()
+                            for i in range(0, len(det), 64)]).astype(np.float32)
+    iou64 = np.array([R.iou3d64(d, g) for d, g in zip(det, gt)])
+    ref_err = float(np.abs(iou32.astype(np.float64) - iou64)[~deg].max())
+    assert R.MARGIN >= 100 * ref_err, ref_err
+    assert (iou64 == 0).sum() >= 3 and (iou64 > 0.5).sum() > 40 and ((iou64 > 0.05) & (iou64 < 0.25)).sum() > 20
+    out.update({'A.det': det, 'A.gt': gt, 'A.degenerate': deg, 'A.iou32': iou32, 'A.iou64': iou64, 'A.ref_err': np.array(ref_err)})
+    print(f'  indoor_eval[A]: {len(det)} pairs, {int(deg.sum())} degenerate; the emulated reference is at most {ref_err:.3e} from float64 '
+          f'on the others ({abs(iou32[deg].astype(np.float64) - iou64[deg]).max():.3e} on the degenerate ones)')
+    # ---- cases B and C
+    gts, dts, dts_c, redrawn = make_indoor_eval_cases()
+    label2cat = dict(enumerate(synthetic.INDOOR_CLASSES))
+    plain = ie.eval_map_recall
+    for case, d in (('B', dts), ('C', dts_c)):
+        kept = {}
+
+        def spy(pred, gt_, ovthresh=None):
+            kept['ret'] = plain(pred, gt_, ovthresh)
+            return kept['ret']
+        ie.eval_map_recall = spy
+        with np.errstate(all='ignore'):
+            ret = ie.indoor_eval([dict(g) for g in gts], R.as_results(d, Boxes), list(R.THRESHOLDS), label2cat, box_type_3d=Boxes,
+                                 box_mode_3d=Box3DMode.DEPTH)
+        R.pack_case(case, gts, d, out)
+        out[f'{case}.ret_keys'] = np.array(list(ret.keys()))
+        out[f'{case}.ret_values'] = np.array([ret[k] for k in ret], np.float64)
+        rec, prec, ap = kept['ret']
+        out[f'{case}.labels'] = np.array(list(rec[0].keys()), np.int64)
+        for t in range(len(R.THRESHOLDS)):
+            for label in rec[t]:
+                out[f'{case}.rec.{t}.{label}'] = np.asarray(rec[t][label], np.float64)
+                out[f'{case}.prec.{t}.{label}'] = np.asarray(prec[t][label], np.float64)
+        nan = np.isnan(out[f'{case}.ret_values'])
+        assert nan.any() == (case == 'C'), (case, ret)
+        print(f'  indoor_eval[{case}]: {len(gts)} frames, {sum(g["gt_num"] for g in gts)} ground truths, {sum(len(x["labels"]) for x in d)} '
+              f'detections ({redrawn} re-drawn), {len(ret)} keys, {int(nan.sum())} NaN; mAP_0.25 {ret["mAP_0.25"]:.4f}, mAP_0.50 {ret["mAP_0.50"]:.4f}')
+    ie.eval_map_recall = plain
+    assert out['B.ret_values'][list(out['B.ret_keys']).index(f'{label2cat[INDOOR_EVAL_GT_ONLY]}_AP_0.25')] == 0
+    np.savez_compressed(os.path.join(OUT, 'indoor_eval.npz'), **out)
+
+
 PIPELINE_CASES = ((41, 6), (42, 5))          # (seed, frames)
 PIPELINE_OUT_KEYS = ('gt_labels_3d', 'GGA_boxes_img', 'GGA_lidar2img', 'GGA_init_pseudo_labels', 'GGA_bdry_masks',
                      'GGA_mask_valid', 'GGA_difficulty', 'GGA_num_points_in_box2d')
@@ -1567,6 +1741,7 @@ def main():
     golden_head(ref)
     golden_pseudo_match(ref)
     golden_kitti_eval(ref)
+    golden_indoor_eval(ref)
     golden_pipeline(ref)
     golden_label_gen(ref)
     golden_rga(ref)
