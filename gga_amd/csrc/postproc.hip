@@ -12,6 +12,16 @@
 // by the reference's own known-answer tests (tests/test_utils/test_nms.py:82-120,
 // tests/test_utils/test_box3d.py:1122-1187,1683-1790).
 //
+// Pinned beyond those by tests/test_postproc_edges_gpu.py against float64 references (tests/_geometry_ref.py):
+//   face rule   the top and bottom faces belong to a box, the four side faces do not; of several boxes holding a point
+//               points_in_boxes_part names the first; a NaN coordinate or box field is inside nothing
+//   tie order   equal scores are processed in input order (ops.nms_rotated / nms_bev / circle_nms sort stably; the
+//               kernels below take the sorted order as given), so the kept set is the same on every call
+//   IoU         identical, re-parametrised, near-parallel, nested, touching, thin and degenerate pairs, |yaw| up to
+//               6 pi + 1, centres out to 600 m (the label offset of ops.nms_rotated); boxes that only touch stay at 0
+//   sizes       the scan beyond its first register word per lane (n > 4096, max_keep cutting there), n > 32768 refused
+//               before anything is launched; points_in_boxes_all beyond one tile of 256 boxes
+//
 // NMS runs fully on the device (mmcv copies the N x N bit mask to the host for the greedy scan):
 //   nms_mask_kernel   64x64 IoU blocks -> bit mask rows (only the upper triangle)
 //   nms_scan_kernel   one wavefront walks the score-sorted boxes, the "removed" bit set lives in
@@ -164,7 +174,7 @@ extern "C" int gga_nms_rotated_sorted(const float* boxes_sorted, int n, float io
 // box = (x, y, z_bottom, dx, dy, dz, yaw). mmcv's check_pt_in_box3d.
 __device__ __forceinline__ bool pt_in_box3d(float px, float py, float pz, const float* b) {
     const float cz = b[2] + b[5] * 0.5f;
-    if (fabsf(pz - cz) > b[5] * 0.5f) return false;
+    if (!(fabsf(pz - cz) <= b[5] * 0.5f)) return false;     // (a NaN z or dz is inside nothing)
     const float sx = px - b[0], sy = py - b[1];
     const float c = cosf(-b[6]), s = sinf(-b[6]);
     const float lx = sx * c - sy * s, ly = sx * s + sy * c;
@@ -215,7 +225,7 @@ __global__ __launch_bounds__(256) void points_in_boxes_all_kernel(const float* _
             const int p = e / tn, t = e - p * tn;
             const float* pt = pts + ((int64_t)b * M + p0 + p) * 3;
             const float* d = sb[t];
-            bool in = !(fabsf(pt[2] - d[2]) > d[5]);
+            bool in = fabsf(pt[2] - d[2]) <= d[5];
             const float sx = pt[0] - d[0], sy = pt[1] - d[1];
             const float lx = sx * d[6] - sy * d[7], ly = sx * d[7] + sy * d[6];
             in = in & (lx > -d[3]) & (lx < d[3]) & (ly > -d[4]) & (ly < d[4]);
@@ -227,10 +237,9 @@ __global__ __launch_bounds__(256) void points_in_boxes_all_kernel(const float* _
 extern "C" int gga_points_in_boxes(const float* points, const float* boxes, int B, int M, int T, int all, int32_t* out,
                                    void* stream) {
     GGA_REQUIRE(B >= 1 && M >= 0 && T >= 0, "gga_points_in_boxes: bad sizes");
-    if (M == 0) return GGA_OK;
+    if (M == 0 || (all && T == 0)) return GGA_OK;         // nothing to write (an empty [B, M, 0] output has no address)
     GGA_REQUIRE(points && out && (T == 0 || boxes), "gga_points_in_boxes: null pointer argument");
     if (all) {
-        if (T == 0) return GGA_OK;
         hipLaunchKernelGGL(points_in_boxes_all_kernel, dim3((M + PIB_PTS - 1) / PIB_PTS, B), dim3(256), 0,
                            (hipStream_t)stream, points, boxes, M, T, out);
         GGA_CHECK_LAUNCH("points_in_boxes_all_kernel");

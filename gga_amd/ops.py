@@ -46,7 +46,7 @@ def nms_rotated(dets, scores, iou_threshold, labels=None, max_keep=0):
         span = boxes[:, :2].abs().max() + boxes[:, 2:4].max() + 1
         boxes = boxes.clone()
         boxes[:, :2] += labels.to(boxes)[:, None] * span * 2
-    scores_sorted, order = scores.sort(0, descending=True)
+    order = torch.sort(scores, dim=0, descending=True, stable=True)[1]      # ties keep their input order
     boxes_sorted = boxes.index_select(0, order).contiguous()
     n = boxes_sorted.shape[0]
     L = _lib.lib()
@@ -82,7 +82,7 @@ def circle_nms(dets, thresh, post_max_size=83):
 
 def nms_bev(boxes, scores, thresh, pre_max_size=None, post_max_size=None):
     assert boxes.size(1) == 5, 'Input boxes shape should be [N, 5]'
-    order = scores.sort(0, descending=True)[1]
+    order = torch.sort(scores, dim=0, descending=True, stable=True)[1]      # ties keep their input order
     if pre_max_size is not None:
         order = order[:pre_max_size]
     boxes = boxes[order].contiguous()

@@ -417,10 +417,11 @@ int gga_oracle_nms_rotated_sorted(const float* boxes, int n, float thr, int64_t*
     return nk;
 }
 
-/* mmcv check_pt_in_box3d: box = (x, y, z_bottom, dx, dy, dz, yaw) */
+/* mmcv check_pt_in_box3d: box = (x, y, z_bottom, dx, dy, dz, yaw). One deliberate departure from mmcv: its z test,
+ * fabsf(z - cz) > dz / 2 -> outside, lets a NaN z or dz pass; here (and in the product kernels) NaN is inside nothing. */
 static int pt_in_box(const float* p, const float* b) {
     float cz = b[2] + b[5] * 0.5f;
-    if (fabsf(p[2] - cz) > b[5] * 0.5f) return 0;
+    if (!(fabsf(p[2] - cz) <= b[5] * 0.5f)) return 0;
     float sx = p[0] - b[0], sy = p[1] - b[1];
     float c = cosf(-b[6]), s = sinf(-b[6]);
     float lx = sx * c - sy * s, ly = sx * s + sy * c;
