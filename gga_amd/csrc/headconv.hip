@@ -9,11 +9,10 @@
 // 0.38 ms wgrad per conv on a 219 MB input = 0.6 TB/s; a lane-per-pixel VALU kernel over an LDS
 // halo tile: 0.165 / 0.147 ms, bound by LDS reads). Swapping the roles makes them GEMMs with
 // N = 9 taps x COUT <= 32 and the convolution a shifted sum of the result (see the kernels).
-// Three generations live in this file: round 1 (one tile per workgroup, described next), round 2 (persistent, rows parked
-// in LDS: headconv_fwd_kernel / headconv_wgrad_kernel - kept for maps beyond the 32-bit tile offsets of the newer ones and
-// for the A/B, GGA_HEADCONV_PARKED) and round 3, the shipped ones (headconv_fwd16_kernel / headconv_wgrad16_kernel: operand
-// straight from the load into v_mfma_f32_16x16x4_f32, every load a tile ahead with counted waits; 0.091 -> 0.056-0.063 ms
-// forward, 0.100 -> 0.047-0.055 ms weight gradient at 16 x 248 x 216: EXPERIMENTS.md 6c).
+// headconv_fwd16_kernel / headconv_wgrad16_kernel: persistent workgroups, the operand straight from the global load into
+// v_mfma_f32_16x16x4_f32, every load requested a tile ahead with counted waits (0.056-0.063 ms forward, 0.047-0.055 ms
+// weight gradient at 16 x 248 x 216). The forms before them (one tile per workgroup; rows parked in LDS) and the
+// measurements that led from one to the next: EXPERIMENTS.md 6b / 6c.
 // Backward-data is never materialised on the train path: the gradient w.r.t. the (never stored)
 // normalised activation is recomputed from the 1-4 channel grad_y inside the BatchNorm backward of
 // the branch (headtail_bwd_kernel below).
@@ -24,166 +23,26 @@
 
 // Forward on the matrix cores, with the roles swapped so that the tiny output width is not the
 // GEMM's N: Z[p][n] = sum_ci x[p][ci] * w[co][ci][off] for n = off*COUT + co (9*COUT <= 32 columns,
-// one 32-wide tile) is a [pixels x 64] x [64 x 32] product on v_mfma_f32_32x32x2_f32, and the
+// one or two 16-wide tiles) is a [pixels x 64] x [64 x 32] product on v_mfma_f32_16x16x4_f32, and the
 // convolution is the 9-tap shifted sum y[p][co] = bias + sum_off Z[p + off][off*COUT + co].
 //   x: [B, H, W, 64] (channels-last memory of a [B,64,H,W] tensor); w: [cout][64][3][3]; y: [B, cout, H, W]
-// A 512-thread workgroup owns 8 x 32 output pixels; its 10 x 34 halo pixels are dealt to the 8
-// waves in groups of 32. Lane (r = lane%32, h = lane/32) loads channels 32h..32h+31 of pixel r of
-// its group straight from global memory (128 contiguous bytes, no LDS staging of x) and keeps the
-// weights of column r for the same channels in registers, so K is walked in the order
-// (32h + s) on both operands. Z goes to LDS (pixel stride 33 floats), then one thread per
-// (output pixel, channel) adds its nine taps. Each input pixel is read once per tile
-// (halo 1.33x), 32 MFMAs per 32 pixels.
-// (That was the round-1 forward kernel. Cycle stamps per workgroup at
-// 16 x 248 x 216 had shown ~25 k of its ~60 k cycles waiting for the first pixel group's rows, ~20 k for the second group's -
-// which only three of the eight waves have -, 2 k of matrix products per group and 1-8 k of epilogue.)
-#define HM_TR 8
-#define HM_TW 32
-#define HM_HR (HM_TR + 2)
-#define HM_HW (HM_TW + 2)
-#define HM_NPIX (HM_HR * HM_HW)
-#define HM_NGRP ((HM_NPIX + 31) / 32)
-#define HM_ZS 33
-
-// Round 2 (headconv_fwd_kernel): the kernel is PERSISTENT and keeps one pixel group's rows in flight per wave at all times. A workgroup owns
-// 13 x 32 output pixels; its 15 x 34 = 510 halo pixels are exactly 16 groups of 32, two per wave. A wave walks the stream
-// of its groups (tile after tile): park the rows that arrived (whole pixel rows, lane l = 16-byte piece l of four rows per
-// load instruction, optional input affine + ReLU on the lane's four fixed channels) in its own LDS region, read them back
-// pixel-per-lane (lane (r, h): channels 32h .. 32h+31 of pixel r; 272-byte rows are conflict-free both ways), REQUEST THE
-// NEXT GROUP (possibly of the next tile), multiply, write the Z block. After a tile's second group: barrier, nine-tap sums,
-// barrier. The region holds the parked rows first and the wave's two Z blocks after (8704 B), so a workgroup needs 70 KB
-// and 119 registers: two per CU. The one-tile-per-workgroup form had every workgroup of a round load (25 k of its 60 k
-// cycles, 12 us under a full memory pipe), then multiply, with the pipe idle meanwhile: 141-150 us per call with cold
-// caches against 114-118 us now (104 -> 77 us with the input resident in the MALL); tools_dev/bench_headconv_cold.py.
-#define HP_TR 13
-#define HP_HR (HP_TR + 2)
-#define HP_NPIX (HP_HR * HM_HW)                        // 510
-#define HP_NGRP 16
-#define HM_SROW 272                                    // bytes per parked pixel row (256 + 16)
-#define HM_WREG (32 * HM_SROW)                         // per-wave LDS region: 8704 B >= two Z blocks of 32 x 33 floats
-
-template <int COUT>
-__global__ __launch_bounds__(512, 2) void headconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          const float* __restrict__ bias, int B, int H, int W,
-                                                          int tiles_x, int tiles_y, int n_tiles, int cout_total, int co_base,
-                                                          const float* __restrict__ in_ss, int64_t xs, float* __restrict__ y) {
-    typedef float acc16 __attribute__((ext_vector_type(16)));
-    static_assert(2 * 32 * HM_ZS * 4 <= HM_WREG && (HP_NPIX + 31) / 32 == HP_NGRP, "tile geometry");
-    __shared__ __attribute__((aligned(16))) unsigned char reg[8 * HM_WREG];
-    const int per_img = tiles_x * tiles_y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    unsigned char* mine = reg + wave * HM_WREG;
-
-    // B operand: column n = r -> (off, co); zero columns beyond 9*COUT. Built once per workgroup as wl[channel][32 columns]
-    // in LDS and read per MFMA (lane (r, h) of k-step s: wl[32h + s][r], conflict-free): 32 registers less per lane than
-    // holding the column, which is what lets two 512-thread workgroups share a CU
-    __shared__ float wl[HC_CIN * 32];
-    for (int i = threadIdx.x; i < HC_CIN * 32; i += 512) {
-        const int c = i >> 5, n = i & 31;
-        const bool used = n < 9 * COUT;
-        const int off = used ? n / COUT : 0, co = used ? n - off * COUT : 0;
-        wl[i] = used ? w[((int64_t)(co_base + co) * HC_CIN + c) * 9 + off] : 0.0f;
-    }
-    __syncthreads();
-    const float* wcol = wl + (32 * h) * 32 + r;
-    // the lane's piece of a pixel row: channels 4 * (lane % 16) .. +3, fixed for every load
-    const int piece = lane & 15, prow_ = lane >> 4;                    // 4 pixel rows per load instruction
-    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sf = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (in_ss) {
-        sc = *reinterpret_cast<const float4*>(in_ss + 4 * piece);
-        sf = *reinterpret_cast<const float4*>(in_ss + HC_CIN + 4 * piece);
-    }
-    float4 ld[8];
-#define HM_FETCH_(P) (*reinterpret_cast<const float4*>(P))
-    // request the rows of group G of tile T (8 loads in flight per lane), zero outside the image / the halo
-#define HM_LOAD(T, G) {                                                                                               \
-        const int tb_ = (T) / per_img, trem_ = (T) - tb_ * per_img;                                                   \
-        const int ty0_ = (trem_ / tiles_x) * HP_TR, tx0_ = (trem_ % tiles_x) * HM_TW;                                 \
-        int pv_ = prow_;                                                                                              \
-        asm volatile("" : "+v"(pv_));      /* keep the 16 row positions from being hoisted out of the tile loop (32 registers) */ \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                               \
-            const int hp = (G) * 32 + 4 * i + pv_;                                                                    \
-            const int hr = hp / HM_HW, hx = hp - hr * HM_HW;                                                          \
-            const int iy = ty0_ + hr - 1, ix = tx0_ + hx - 1;                                                         \
-            const bool ok = hp < HP_NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;                 \
-            float4 v = ok ? HM_FETCH_(x + (((int64_t)tb_ * H + iy) * W + ix) * xs + 4 * piece)                        \
-                          : make_float4(0.f, 0.f, 0.f, 0.f);                                                          \
-            if (ok && in_ss) {                           /* input = relu(x * scale + shift); zero padding stays zero */ \
-                v.x = fmaxf(fmaf(v.x, sc.x, sf.x), 0.0f); v.y = fmaxf(fmaf(v.y, sc.y, sf.y), 0.0f);                   \
-                v.z = fmaxf(fmaf(v.z, sc.z, sf.z), 0.0f); v.w = fmaxf(fmaf(v.w, sc.w, sf.w), 0.0f);                   \
-            }                                                                                                         \
-            ld[i] = v; } }
-    // park the group in the wave's region, read it back pixel-per-lane (a wave is in lockstep: no barrier, the LDS
-    // counter orders the write before the read)
-#define HM_PARK(XA) {                                                                                                 \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) *reinterpret_cast<float4*>(mine + (4 * i + prow_) * HM_SROW + piece * 16) = ld[i]; \
-        _Pragma("unroll") for (int q = 0; q < 8; ++q) XA[q] = *reinterpret_cast<const float4*>(mine + r * HM_SROW + h * 128 + q * 16); }
-#define HM_MMA(XA, ACC) {                                                                                             \
-        _Pragma("unroll") for (int i = 0; i < 16; ++i) ACC[i] = 0.0f;                                                 \
-        _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                               \
-            ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(XA[q].x, wcol[(4 * q + 0) * 32], ACC, 0, 0, 0);                \
-            ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(XA[q].y, wcol[(4 * q + 1) * 32], ACC, 0, 0, 0);                \
-            ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(XA[q].z, wcol[(4 * q + 2) * 32], ACC, 0, 0, 0);                \
-            ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(XA[q].w, wcol[(4 * q + 3) * 32], ACC, 0, 0, 0);                \
-        } }
-    // D layout of 32x32x2: register v of lane l holds row (v/4)*8 + (l/32)*4 + v%4, column l%32
-#define HM_ZOUT(U, ACC) { float* zg = reinterpret_cast<float*>(mine) + (U) * 32 * HM_ZS + r;                          \
-        _Pragma("unroll") for (int v = 0; v < 16; ++v) zg[((v >> 2) * 8 + h * 4 + (v & 3)) * HM_ZS] = ACC[v]; }
-    int tile = blockIdx.x;
-    if (tile >= n_tiles) return;
-    HM_LOAD(tile, wave)
-    for (; tile < n_tiles; tile += gridDim.x) {
-        const int b = tile / per_img;
-        const int rem = tile - b * per_img;
-        const int y0 = (rem / tiles_x) * HP_TR, x0 = (rem % tiles_x) * HM_TW;
-        float4 xa[8];
-        acc16 acc, acc2;
-        HM_PARK(xa)
-        HM_LOAD(tile, wave + 8)                           // in flight while the first group multiplies
-        HM_MMA(xa, acc)
-        HM_PARK(xa)                                       // the region is free for the Z blocks from here on
-        if (tile + (int)gridDim.x < n_tiles) { HM_LOAD(tile + (int)gridDim.x, wave) }     // across the barriers and the epilogue
-        HM_ZOUT(0, acc)
-        HM_MMA(xa, acc2)
-        HM_ZOUT(1, acc2)
-        __syncthreads();
-        for (int i = threadIdx.x; i < HP_TR * HM_TW * COUT; i += 512) {
-            const int co = i / (HP_TR * HM_TW), pid = i - co * (HP_TR * HM_TW);
-            const int ty = pid / HM_TW, tx = pid - ty * HM_TW;
-            const int oy = y0 + ty, ox = x0 + tx;
-            if (oy >= H || ox >= W) continue;
-            float s = bias ? bias[co_base + co] : 0.0f;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int hp = (ty + ky) * HM_HW + tx + kx;           // halo pixel -> group g = hp / 32, kept by wave g % 8
-                    const int g = hp >> 5;
-                    s += reinterpret_cast<const float*>(reg + (g & 7) * HM_WREG)[((g >> 3) * 32 + (hp & 31)) * HM_ZS + (ky * 3 + kx) * COUT + co];
-                }
-            y[(((int64_t)b * cout_total + co_base + co) * H + oy) * W + ox] = s;
-        }
-        __syncthreads();                                  // the regions are parked into again
-    }
-#undef HM_LOAD
-#undef HM_PARK
-#undef HM_MMA
-#undef HM_ZOUT
-#undef HM_FETCH_
-}
-
-// Round 3: the forward kernel without the LDS parking step. Cycle ablations of the parked form at 16 x 248 x 216 out of a
-// 960-channel tensor (tools_dev/exp_headconv.py: 91 us as shipped, 69 without the matrix products, 59 without the global
-// reads, 31 with neither) had shown its three parts running one after another, not side by side: a wave waited for its
-// group, parked it, multiplied, and only one group per wave was ever in flight. Here the operand comes straight from the
-// load: v_mfma_f32_16x16x4_f32 wants A[i][k] from lane (i = lane % 16, k = lane / 16), so lane (i, hq) loads the float4
+// The kernel is persistent (two 512-thread workgroups per CU walk the tiles). A tile is 13 x 32 output pixels; its
+// 15 x 34 = 510 halo pixels are exactly 16 groups of 32, two per wave. The operand comes straight from the load:
+// v_mfma_f32_16x16x4_f32 wants A[i][k] from lane (i = lane % 16, k = lane / 16), so lane (i, hq) loads the float4
 // at channels 16j + 4hq .. +3 of pixel i (16 pixel rows x 64 contiguous bytes per instruction, j = 0..3) and feeds its
 // four floats to four k-steps whose B rows are the channels (16j + 4hq' + e), hq' = 0..3 - any channel order serves as
 // long as both operands use it. No LDS round trip, no register copy, the address of every halo slot is a per-lane constant
 // plus the tile's origin, and BOTH pixel groups of the next tile are requested a whole tile ahead (16 loads in flight per
-// lane). Z is kept compactly (9 * COUT columns, odd stride) for the whole tile; a one-channel branch needs one 16-column
-// product instead of two.
+// lane; the waits are counted, see HQ_LOAD). Z is kept compactly (9 * COUT columns, odd stride) for the whole tile, then
+// one thread per output pixel adds its nine taps; a one-channel branch needs one 16-column product instead of two.
+#define HM_TW 32                                       // forward tile: HP_TR x HM_TW output pixels, halo HP_HR x HM_HW
+#define HM_HW (HM_TW + 2)
+#define HP_TR 13
+#define HP_HR (HP_TR + 2)
+#define HP_NPIX (HP_HR * HM_HW)                        // 510
+#define HP_NGRP 16
+static_assert((HP_NPIX + 31) / 32 == HP_NGRP, "tile geometry");
+
 template <int COUT, bool AFF>
 __global__ __launch_bounds__(512, 4) void headconv_fwd16_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, int B, int H, int W,
@@ -325,138 +184,17 @@ __global__ __launch_bounds__(512, 4) void headconv_fwd16_kernel(const float* __r
 }
 
 // dW[co][ci][off] = sum_p x[p+off][ci] * dy[co][p]; dbias[co] = sum_p dy[co][p], on the matrix
-// cores with the same role swap: per tile, D[ci][n] += sum_q x[q][ci] * G[q][n] over the halo
-// pixels q, where G[q][off*COUT + co] = dy[co][q - off] if q - off is an output pixel of the
-// tile (zero otherwise) - a [64 x halo] x [halo x 32] product, K = pixels. Lane (m, h) feeds
-// x[q_h][m] / x[q_h][32 + m] (one coalesced 128 B row segment per half wave, each input element
-// read exactly once per tile, no LDS staging) and G[q_h][m] (read from the tile's dy, staged in
-// LDS with a zero border so the shifted read needs no branch). Persistent 512-thread
-// workgroups (4 per CU: the loads of one hide behind the MFMAs of the others - 60 VGPRs with the
-// K loop unrolled by 11; measured 0.136 ms at 2 per CU, 0.120 ms at 4) walk the tiles; the 8 waves split K (44 halo pixels each) and keep their partial D
-// in accumulators across tiles; one fixed-order fold per workgroup at the end, then
-// headconv_wgrad_final_kernel adds the workgroups (no atomics).
-#define HW_PR (HM_HR + 2)
-#define HW_PC (HM_HW + 2)
-#define HW_KW ((HM_NGRP * 32) / 8)      // halo pixels per wave (44)
-#ifndef HW_UNROLL
-#define HW_UNROLL 11
-#endif
-#ifndef HW_MINW
-#define HW_MINW 8
-#endif
-
-template <int COUT>
-__global__ __launch_bounds__(512, HW_MINW) void headconv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                            int B, int H, int W, int tiles_x, int tiles_y,
-                                                            int64_t n_tiles, int cout_total, int co_base,
-                                                            const float* __restrict__ in_ss, int64_t xs,
-                                                            float* __restrict__ partials) {
-    typedef float acc16 __attribute__((ext_vector_type(16)));
-    __shared__ float gds[2][COUT * HW_PR * HW_PC];
-    __shared__ float red[HC_CIN * 33];
-    __shared__ float bred[8][HC_MAXCO];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = lane & 31, h = lane >> 5;
-    const bool used = m < 9 * COUT;
-    const int off = used ? m / COUT : 0, co = used ? m - off * COUT : 0;
-    const int ky = off / 3, kx = off - ky * 3;
-    const int gbase = co * HW_PR * HW_PC + (2 - ky) * HW_PC + (2 - kx);
-    const float usedf = used ? 1.0f : 0.0f;
-    // optional input affine + ReLU (the lane's two channels are fixed)
-    const float sc0 = in_ss ? in_ss[m] : 1.0f, sc1 = in_ss ? in_ss[32 + m] : 1.0f;
-    const float sf0 = in_ss ? in_ss[HC_CIN + m] : 0.0f, sf1 = in_ss ? in_ss[HC_CIN + 32 + m] : 0.0f;
-    const float lo = in_ss ? 0.0f : -INFINITY;
-    for (int i = threadIdx.x; i < 2 * COUT * HW_PR * HW_PC; i += 512) (&gds[0][0])[i] = 0.0f;    // borders stay zero
-    // (the zeroes must have landed before anyone stages the first tile into the same words: without this barrier a wave that
-    // was held up in the loop above could wipe values another wave had already staged - seen once in ~2000 steps, and only with
-    // a second stream's kernels sharing the CU: one tile's dy partly zeroed, 3e-3 of the branch's weight gradient)
-    __syncthreads();
-    acc16 acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
-    float bs = 0.0f;                     // this thread's share of sum(dy) for channel (threadIdx.x >> 8) (+2 on odd passes)
-    float bs2 = 0.0f;
-    const int per_img = tiles_x * tiles_y;
-    int it = 0;
-    for (int64_t ti = blockIdx.x; ti < n_tiles; ti += gridDim.x, ++it) {
-        const int b = (int)(ti / per_img);
-        const int rem = (int)(ti - (int64_t)b * per_img);
-        const int y0 = (rem / tiles_x) * HM_TR, x0 = (rem % tiles_x) * HM_TW;
-        float* g = gds[it & 1];
-        // stage dy of the tile (zero outside the image): thread -> (channel, pixel), at most 2 passes
-#pragma unroll
-        for (int pass = 0; pass < (COUT + 1) / 2; ++pass) {
-            const int i = threadIdx.x + 512 * pass;
-            const int ci = i >> 8, pid = i & 255;
-            if (ci < COUT) {
-                const int ty = pid >> 5, tx = pid & 31;
-                const int oy = y0 + ty, ox = x0 + tx;
-                const float v = (oy < H && ox < W) ? dy[(((int64_t)b * cout_total + co_base + ci) * H + oy) * W + ox] : 0.0f;
-                g[ci * HW_PR * HW_PC + (ty + 2) * HW_PC + tx + 2] = v;
-                if (pass == 0) bs += v; else bs2 += v;
-            }
-        }
-        __syncthreads();      // tile `it` staged; every wave is done with tile it-1, so the other buffer is free
-#pragma unroll HW_UNROLL
-        for (int s = 0; s < HW_KW / 2; ++s) {
-            const int q = HW_KW * wave + 2 * s + h;
-            const bool inh = q < HM_NPIX;
-            const int hr = inh ? q / HM_HW : 0, hx = inh ? q - hr * HM_HW : 0;
-            const int iy = y0 + hr - 1, ix = x0 + hx - 1;
-            const bool ok = inh && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-            const float* xp = x + (((int64_t)b * H + (ok ? iy : 0)) * W + (ok ? ix : 0)) * xs + m;
-            const float mk = ok ? 1.0f : 0.0f;
-            const float x0_ = xp[0], x1_ = xp[32];
-            const float a0 = fmaxf(fmaf(x0_, sc0, sf0), lo) * mk, a1 = fmaxf(fmaf(x1_, sc1, sf1), lo) * mk;
-            const float gv = g[gbase + hr * HW_PC + hx] * usedf;
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, gv, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, gv, acc1, 0, 0, 0);
-        }
-    }
-    // fixed-order fold of the 8 waves' partial D[ci][n] (register v of lane l: row (v/4)*8 + (l/32)*4 + v%4, column l%32)
-    for (int wv = 0; wv < 8; ++wv) {
-        __syncthreads();
-        if (wave == wv) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = (v >> 2) * 8 + h * 4 + (v & 3);
-                float* r0 = red + row * 33 + m;
-                float* r1 = red + (32 + row) * 33 + m;
-                *r0 = (wv ? *r0 : 0.0f) + acc0[v];
-                *r1 = (wv ? *r1 : 0.0f) + acc1[v];
-            }
-        }
-    }
-    // bias sums: threads 0..255 hold channel 0 (pass 0) and 2 (pass 1), threads 256..511 channels 1 and 3
-    {
-        const float t0 = wave_sum(bs), t1 = wave_sum(bs2);
-        if (lane == 0) { bred[wave][0] = t0; bred[wave][1] = t1; }
-    }
-    __syncthreads();
-    const int row_len = cout_total * HC_CIN * 9 + cout_total;
-    float* out = partials + (int64_t)blockIdx.x * row_len;
-    for (int i = threadIdx.x; i < 9 * COUT * HC_CIN; i += 512) {
-        const int ci = i & 63, n = i >> 6;
-        const int o = n / COUT, c = n - o * COUT;
-        out[((int64_t)(co_base + c) * HC_CIN + ci) * 9 + o] = red[ci * 33 + n];
-    }
-    if (threadIdx.x < COUT) {
-        const int c = threadIdx.x;                       // channel c: waves (c&1)*4 .. +3, pass c>>1
-        const int w0 = (c & 1) * 4, ps = c >> 1;
-        out[cout_total * HC_CIN * 9 + co_base + c] = (bred[w0][ps] + bred[w0 + 1][ps]) + (bred[w0 + 2][ps] + bred[w0 + 3][ps]);
-    }
-}
-
-// Round 3: the weight gradient over INPUT tiles. The kernel above walks the halo pixels of an output tile (every input element
-// read 1.33 times) and feeds the matrix cores from 4-byte loads behind ~25 address instructions per pixel pair; with neither
-// its loads nor its products it still took 55 of its 100 us (tools_dev/exp_headconv.py). Here a workgroup owns 8 x 32 INPUT
+// cores with the same role swap: the output is D[ci][n] for n = off*COUT + co, K = pixels. A workgroup owns 8 x 32 INPUT
 // pixels - disjoint tiles, every element of x read exactly once - and the shifted operand is taken from the tile of dy with a
-// one-pixel border instead (a few KB): dW[co][ci][off] = sum_q x[q][ci] * dy[co][q - (off - 1)] over the tile's own pixels q.
+// one-pixel border (a few KB, staged in LDS, zero outside the image so the shifted read needs no branch):
+// dW[co][ci][off] = sum_q x[q][ci] * dy[co][q - (off - 1)] over the tile's own pixels q.
 // v_mfma_f32_16x16x4_f32 with A[i][k] = x[pixel q0 + k][channel 4i + e] for e = 0..3: lane (i, k) loads ONE float4 (its
 // pixel's channels 4i .. 4i+3; a 16-lane group reads the pixel's 256 contiguous bytes, four pixels per instruction) and
 // feeds its four floats to four products whose D rows are the channels 4i + e; B[k][n] = dy of column n = off * COUT + co at
 // pixel q0 + k shifted by the tap, one LDS read with an immediate offset. A wave owns one row of the tile (8 steps of 4
 // pixels); every float4 is requested a whole tile ahead and every lane always loads (counted waits, see the forward kernel).
+// The persistent 512-thread workgroups keep their partial D in accumulators across tiles; one fixed-order fold per
+// workgroup at the end, then headconv_wgrad_final_kernel adds the workgroups (no atomics).
 #define HG_TR 8
 #define HG_TW 32
 #define HG_PR (HG_TR + 2)
@@ -540,7 +278,9 @@ __global__ __launch_bounds__(512, 4) void headconv_wgrad16_kernel(const float* _
         } }
     int tile = blockIdx.x;
     const int stride = gridDim.x;
-    __syncthreads();                                      // the zeroes have landed (see the race note in the kernel above)
+    // (the zeroes must have landed before anyone stages the first tile into the same words: without this barrier a wave that
+    // was held up in the zeroing loop could wipe values another wave had already staged)
+    __syncthreads();
     HG_GLOAD(tile, tile < n_tiles)
 #pragma unroll
     for (int s = 0; s < 8; ++s) HG_XLOAD(tile, tile < n_tiles, s)
@@ -626,9 +366,7 @@ __global__ __launch_bounds__(256) void headconv_wgrad_final_kernel(const float* 
     else if (dbias) dbias[i - n_w] = (float)s;
 }
 
-#ifndef HC_WGRAD_BLOCKS
-#define HC_WGRAD_BLOCKS 1024
-#endif
+#define HC_BLOCKS 512                    // persistent launches: two workgroups per CU
 
 static int headconv_check(const char* fn, int B, int H, int W, int cin, int cout) {
     GGA_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad sizes", fn);
@@ -639,12 +377,24 @@ static int headconv_check(const char* fn, int B, int H, int W, int cin, int cout
 }
 
 extern "C" size_t gga_head_conv3x3_workspace_bytes(int cout) {
-    return (size_t)HC_WGRAD_BLOCKS * ((size_t)cout * HC_CIN * 9 + cout) * sizeof(float);
+    return (size_t)HC_BLOCKS * ((size_t)cout * HC_CIN * 9 + cout) * sizeof(float);
 }
 
 static int headconv_stride(const char* fn, const void* x, int64_t xs) {
     GGA_REQUIRE(xs >= HC_CIN && xs % 4 == 0 && ((uintptr_t)x & 15) == 0,
                 "%s: pixel stride %lld must be a multiple of 4 floats >= %d and the base 16-byte aligned", fn, (long long)xs, HC_CIN);
+    return GGA_OK;
+}
+
+// Map sizes the conv entry points accept. Both kernels take an int tile count and keep per-lane 32-bit element offsets within
+// a tile of `rows` input rows, so rows * W * pixel stride must stay below 2^31. The forward also packs its halo coordinates
+// into 16 bits, hence H, W < 16384; the weight gradient (8-bit tile-local coordinates) has no such need and is held to the
+// same bound only so that both directions of a convolution accept the same maps.
+static int headconv_limits(const char* fn, int H, int W, int64_t xs, int rows, int64_t n_tiles) {
+    GGA_REQUIRE(H < 16384 && W < 16384, "%s: height and width must be below 16384 (got H=%d W=%d)", fn, H, W);
+    GGA_REQUIRE((int64_t)rows * W * xs < 2147483647ll,
+                "%s: %d * W * pixel stride must be below 2^31 elements (got W=%d, pixel stride %lld)", fn, rows, W, (long long)xs);
+    GGA_REQUIRE(n_tiles < 2147483647ll, "%s: too many tiles (%lld)", fn, (long long)n_tiles);
     return GGA_OK;
 }
 
@@ -656,23 +406,19 @@ extern "C" int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, cons
     if (int rc = headconv_stride("gga_head_conv3x3_fwd", x, x_pixel_stride)) return rc;
     const int tx = (W + HM_TW - 1) / HM_TW, ty = (H + HP_TR - 1) / HP_TR;
     const int64_t n_tiles = (int64_t)B * tx * ty;
-    GGA_REQUIRE(n_tiles < 2147483647ll, "gga_head_conv3x3_fwd: too many tiles");
-    static const bool parked_env = getenv("GGA_HEADCONV_PARKED") && (atoi(getenv("GGA_HEADCONV_PARKED")) & 1) != 0;   // A/B: the round-2 kernel (1: forward, 2: weight gradient, 3: both)
-    // (the round-3 kernel keeps per-lane 32-bit element offsets within a tile and 16-bit halo coordinates: larger maps take the other one)
-    const bool parked = parked_env || !(16ll * W * x_pixel_stride < 2147483647ll && H < 16384 && W < 16384);
-    const dim3 grid((unsigned)(n_tiles < 512 ? n_tiles : 512)), block(512);       // persistent: two workgroups per CU
+    if (int rc = headconv_limits("gga_head_conv3x3_fwd", H, W, x_pixel_stride, HP_HR + 1, n_tiles)) return rc;      // (halo rows -1 .. 13: offsets span up to 16 rows)
+    const dim3 grid((unsigned)(n_tiles < HC_BLOCKS ? n_tiles : HC_BLOCKS)), block(512);
 #define HC_G(CO, BASE, AF) hipLaunchKernelGGL((headconv_fwd16_kernel<CO, AF>), grid, block, 0, stream, x, weight, bias, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, y)
-#define HC_F(CO, BASE) { if (parked) hipLaunchKernelGGL(headconv_fwd_kernel<CO>, grid, block, 0, stream, x, weight, bias, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, y); \
-                         else if (in_scale_shift) HC_G(CO, BASE, true); else HC_G(CO, BASE, false); }
+#define HC_F(CO, BASE) { if (in_scale_shift) HC_G(CO, BASE, true); else HC_G(CO, BASE, false); }
     switch (cout) {
         case 1: HC_F(1, 0); break;
         case 2: HC_F(2, 0); break;
         case 3: HC_F(3, 0); break;
-        default: HC_F(2, 0); HC_F(2, 2); break;      // 9*4 columns do not fit one 32-wide tile
+        default: HC_F(2, 0); HC_F(2, 2); break;      // 9*4 columns do not fit two 16-wide tiles
     }
 #undef HC_F
 #undef HC_G
-    GGA_CHECK_LAUNCH("headconv_fwd_kernel");
+    GGA_CHECK_LAUNCH("headconv_fwd16_kernel");
     return GGA_OK;
 }
 
@@ -683,21 +429,17 @@ extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, co
     if (int rc = headconv_check("gga_head_conv3x3_wgrad", B, H, W, cin, cout)) return rc;
     if (int rc = headconv_stride("gga_head_conv3x3_wgrad", x, x_pixel_stride)) return rc;
     GGA_REQUIRE(x && grad_y && grad_weight && workspace, "gga_head_conv3x3_wgrad: null pointer argument");
+    const int tx = (W + HG_TW - 1) / HG_TW, ty = (H + HG_TR - 1) / HG_TR;
+    const int64_t n_tiles = (int64_t)B * tx * ty;
+    if (int rc = headconv_limits("gga_head_conv3x3_wgrad", H, W, x_pixel_stride, HG_TR, n_tiles)) return rc;
     if (workspace_bytes < gga_head_conv3x3_workspace_bytes(cout)) {
         gga_set_error("gga_head_conv3x3_wgrad: workspace too small");
         return GGA_ERR_WORKSPACE;
     }
-    static const bool parked_env = getenv("GGA_HEADCONV_PARKED") && (atoi(getenv("GGA_HEADCONV_PARKED")) & 2) != 0;   // A/B: the round-2 kernel
-    const int tx = (W + HM_TW - 1) / HM_TW, ty = (H + HM_TR - 1) / HM_TR;          // (both kernels: tiles of 8 x 32)
-    const int64_t n_tiles = (int64_t)B * tx * ty;
-    // (the round-3 kernel keeps per-lane 32-bit element offsets within a tile and an int tile count: larger maps take the other one)
-    const bool parked = parked_env || !(n_tiles < 2147483647ll && 8ll * W * x_pixel_stride < 2147483647ll);
-    const int cap = parked ? HC_WGRAD_BLOCKS : 512;                               // persistent: two workgroups per CU
-    const int nb = (int)(n_tiles < cap ? n_tiles : cap);
+    const int nb = (int)(n_tiles < HC_BLOCKS ? n_tiles : HC_BLOCKS);
     float* partials = (float*)workspace;
-#define HC_W(CO, BASE) { if (parked) hipLaunchKernelGGL(headconv_wgrad_kernel<CO>, dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, partials); \
-                         else if (in_scale_shift) hipLaunchKernelGGL((headconv_wgrad16_kernel<CO, true>), dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, partials); \
-                         else hipLaunchKernelGGL((headconv_wgrad16_kernel<CO, false>), dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, partials); }
+#define HC_G(CO, BASE, AF) hipLaunchKernelGGL((headconv_wgrad16_kernel<CO, AF>), dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, partials)
+#define HC_W(CO, BASE) { if (in_scale_shift) HC_G(CO, BASE, true); else HC_G(CO, BASE, false); }
     switch (cout) {
         case 1: HC_W(1, 0); break;
         case 2: HC_W(2, 0); break;
@@ -705,7 +447,8 @@ extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, co
         default: HC_W(2, 0); HC_W(2, 2); break;
     }
 #undef HC_W
-    GGA_CHECK_LAUNCH("headconv_wgrad_kernel");
+#undef HC_G
+    GGA_CHECK_LAUNCH("headconv_wgrad16_kernel");
     const int n_w = cout * HC_CIN * 9;
     hipLaunchKernelGGL(headconv_wgrad_final_kernel, dim3((n_w + cout + 3) / 4), dim3(256), 0, stream, partials, nb, n_w,
                        cout, grad_weight, grad_bias);

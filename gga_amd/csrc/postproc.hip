@@ -367,50 +367,6 @@ extern "C" int gga_circle_nms_sorted(const float* xy_sorted, int n, double thres
 // Output: frame b's detections compacted at out_*[b, 0 .. count[b]).
 #define CPD_THREADS 256
 #define CPD_K 128
-// rotated_inter_area / rotated_iou with the boxes' cos / sin handed in (computed once per candidate instead of once per pair:
-// the same float operations on the same values, so the overlap is bit-identical to rotated_iou's)
-__device__ __forceinline__ void rect_corners_cs(const float* b, float c, float s, float sx, float sy, P2 out[4]) {
-    const float hw = b[2] * 0.5f, hh = b[3] * 0.5f;
-    const float cx = b[0] - sx, cy = b[1] - sy;
-    const float dx[4] = { -hw, hw, hw, -hw }, dy[4] = { -hh, -hh, hh, hh };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { out[i].x = cx + dx[i] * c - dy[i] * s; out[i].y = cy + dx[i] * s + dy[i] * c; }
-}
-
-__device__ float rotated_iou_cs(const float* b1, float c1, float s1, const float* b2, float c2, float s2) {
-    const float a1 = b1[2] * b1[3], a2 = b2[2] * b2[3];
-    if (a1 < 1e-14f || a2 < 1e-14f) return 0.0f;
-    const float sx = (b1[0] + b2[0]) * 0.5f, sy = (b1[1] + b2[1]) * 0.5f;
-    P2 poly[10], tmp[10], q[4];
-    rect_corners_cs(b1, c1, s1, sx, sy, poly);
-    rect_corners_cs(b2, c2, s2, sx, sy, q);
-    int n = 4;
-    for (int e = 0; e < 4 && n > 0; ++e) {
-        const P2 a = q[e], bq = q[(e + 1) & 3];
-        const P2 ed = { bq.x - a.x, bq.y - a.y };
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            const P2 p = poly[i], r = poly[(i + 1) % n];
-            const float dp = cross2(ed, P2{ p.x - a.x, p.y - a.y });
-            const float dr = cross2(ed, P2{ r.x - a.x, r.y - a.y });
-            if (dp >= 0.0f) tmp[m++] = p;
-            if ((dp >= 0.0f) != (dr >= 0.0f)) {
-                const float t = dp / (dp - dr);
-                tmp[m++] = P2{ p.x + t * (r.x - p.x), p.y + t * (r.y - p.y) };
-            }
-        }
-        n = m;
-        for (int i = 0; i < n; ++i) poly[i] = tmp[i];
-    }
-    float inter = 0.0f;
-    if (n >= 3) {
-        float area = 0.0f;
-        for (int i = 0; i < n; ++i) area += cross2(poly[i], poly[(i + 1) % n]);
-        inter = fabsf(area) * 0.5f;
-    }
-    return inter / (a1 + a2 - inter);
-}
-
 // One 256-thread workgroup per (frame, task): steps 1-5 of the list above; the survivors go to the task's own segment
 // out_*[b, t * K ...] with their number in seg_count[b, t]. Thread pair (i, i + 128) shares candidate i's row of the overlap
 // mask: each takes half of the later candidates (the row's work falls with i, the split keeps the long rows short).
@@ -465,7 +421,7 @@ __global__ __launch_bounds__(CPD_THREADS) void centerpoint_detect_kernel(const f
         const int mid = i + 1 + (n - i - 1) / 2;
         const int j0 = half ? mid : i + 1, j1 = half ? n : mid;
         for (int j = j0; j < j1; ++j)
-            if (rotated_iou_cs(me, mc, ms, nb + j * 5, ncs[j * 2], ncs[j * 2 + 1]) > nms_thr) { if (j < 64) m0 |= 1ull << j; else m1 |= 1ull << (j - 64); }
+            if (rotated_iou_rot(me, mc, ms, nb + j * 5, ncs[j * 2], ncs[j * 2 + 1], 0) > nms_thr) { if (j < 64) m0 |= 1ull << j; else m1 |= 1ull << (j - 64); }
         mask[i][half][0] = m0; mask[i][half][1] = m1;
     }
     __syncthreads();

@@ -586,10 +586,16 @@ int gga_bn_stats_partials_cols(const float* gamma, const float* beta, float* run
  * a wider one (x_pixel_stride floats between pixels, 64 when dense); weight [cout,64,3,3];
  * y [B,cout,H,W] NCHW-contiguous. in_scale_shift (optional, [2*64]): the convolution input is
  * relu(x * scale + shift) per channel, applied while loading - the BatchNorm + ReLU of the
- * branch's ConvModule (centerpoint_head.py:58-68) fused into its consumer. */
+ * branch's ConvModule (centerpoint_head.py:58-68) fused into its consumer.
+ * Map size: H and W below 16384 and 16 * W * x_pixel_stride below 2^31 elements (the kernel keeps 16-bit halo
+ * coordinates and 32-bit element offsets within a tile); a larger map returns GGA_ERR_INVALID_ARG before anything is
+ * launched. */
 int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
                          const float* bias, int B, int H, int W, int cin, int cout, float* y, void* stream);
-/* grad_weight [cout,64,3,3] and grad_bias [cout] (optional) from grad_y [B,cout,H,W] */
+/* grad_weight [cout,64,3,3] and grad_bias [cout] (optional) from grad_y [B,cout,H,W]. Map size: H and W below 16384
+ * (the forward's bound, kept on this side so that both directions accept the same maps) and 8 * W * x_pixel_stride
+ * below 2^31 elements, else GGA_ERR_INVALID_ARG before anything is launched. workspace:
+ * gga_head_conv3x3_workspace_bytes(cout), the partial sums of the at most 512 workgroups of the launch. */
 size_t gga_head_conv3x3_workspace_bytes(int cout);
 int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* grad_y,
                            int B, int H, int W, int cin, int cout, float* grad_weight, float* grad_bias,

@@ -579,6 +579,59 @@ def test_head_output_conv_on_column_blocks_of_large_maps(shape):
             assert float((db.double() - br.grad).abs().max() / br.grad.abs().max()) < 2e-5, (cout, aff)
 
 
+def test_head_output_conv_refuses_maps_beyond_its_32_bit_offsets():
+    """A map at the width limit (W = 16384) is refused with an error that names the limit, before anything is launched: the
+    output / the workspace keep their sentinel. Inputs are allocated at the full size, so every address a launch could touch
+    would be in bounds. Just below, the accepted side of the limit (W = 64) is checked against float64 at the tolerances of
+    the test above. The weight gradient's stride product (8 * W * pixel stride < 2^31) would need a 2 GB input to reach
+    through a real pixel stride: it is covered by reading the GGA_REQUIRE in headconv.hip, not by a run."""
+    from gga_amd import _lib
+    L = _lib.lib()
+    torch.manual_seed(5)
+    w = torch.randn(1, 64, 3, 3, device=DEV) * 0.05
+    b = torch.randn(1, device=DEV)
+    ws = torch.empty(L.gga_head_conv3x3_workspace_bytes(1), dtype=torch.uint8, device=DEV)
+
+    def fwd(x, y):
+        B, H, W = x.shape[:3]
+        return L.gga_head_conv3x3_fwd(F._p(x), 64, None, F._p(w), F._p(b), B, H, W, 64, 1, F._p(y), F._stream())
+
+    def wgrad(x, gy, dw, db):
+        B, H, W = x.shape[:3]
+        return L.gga_head_conv3x3_wgrad(F._p(x), 64, None, F._p(gy), B, H, W, 64, 1, F._p(dw), F._p(db), ws.data_ptr(), ws.numel(),
+                                        F._stream())
+
+    # control: W = 64 at H = 2
+    x = torch.randn(1, 2, 64, 64, device=DEV)
+    y = torch.full((1, 1, 2, 64), float('nan'), device=DEV)
+    assert fwd(x, y) == 0
+    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double(), wr, br, padding=1)
+    assert float((y.double() - ref).abs().max() / ref.abs().max()) < 2e-6
+    gy = torch.randn(1, 1, 2, 64, device=DEV)
+    dw, db = torch.full_like(w, float('nan')), torch.full_like(b, float('nan'))
+    assert wgrad(x, gy, dw, db) == 0
+    ref.backward(gy.double())
+    assert float((dw.double() - wr.grad).abs().max() / wr.grad.abs().max()) < 2e-6
+    assert float((db.double() - br.grad).abs().max() / br.grad.abs().max()) < 2e-5
+    # forward at the limit
+    W = 16384
+    x = torch.zeros(1, 2, W, 64, device=DEV)
+    y = torch.full((1, 1, 2, W), -7.0, device=DEV)
+    with pytest.raises(RuntimeError, match=r'width must be below 16384 \(got H=2 W=16384\)'):
+        _lib.check(fwd(x, y), 'gga_head_conv3x3_fwd')
+    torch.cuda.synchronize()
+    assert bool((y == -7.0).all())
+    # weight gradient at the limit (H = 1)
+    x, gy = x[:, :1], torch.zeros(1, 1, 1, W, device=DEV)
+    dw, db = torch.full_like(w, -7.0), torch.full_like(b, -7.0)
+    ws.fill_(0x5a)
+    with pytest.raises(RuntimeError, match=r'width must be below 16384 \(got H=1 W=16384\)'):
+        _lib.check(wgrad(x, gy, dw, db), 'gga_head_conv3x3_wgrad')
+    torch.cuda.synchronize()
+    assert bool((ws == 0x5a).all()) and bool((dw == -7.0).all()) and bool((db == -7.0).all())
+
+
 @pytest.mark.parametrize('cout', [1, 2, 3, 4])
 def test_bn_relu_head_conv_fused_vs_torch(cout):
     """Tail of a head branch: conv(relu(bn(x))) with the normalised activation never stored."""

@@ -1,5 +1,5 @@
 // Stand-alone timing of the head output conv kernels at the train-step shape, with a 1 GiB memset
-// between launches so nothing is served from L2/MALL.  hipcc -O3 --offload-arch=gfx950 [-DHW_UNROLL=..]
+// between launches so nothing is served from L2/MALL.  hipcc -O3 --offload-arch=gfx950
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
