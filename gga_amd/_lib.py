@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _lib = None
 
@@ -113,6 +113,9 @@ SIGNATURES = {
     'gga_head_conv3x3_workspace_bytes': (sz, [i32]),
     'gga_head_conv3x3_wgrad': (i32, [vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'gga_head_tail_bwd': (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]),
+    'gga_head_tile_activity': (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    'gga_head_branch_bwd_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'gga_head_branch_bwd': (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp, sz, vp]),
     'gga_heatmap_splat': (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp]),
     'gga_focal_loss_workspace_bytes': (sz, [i64]),
     'gga_focal_loss_fwd': (i32, [vp, vp, i64, f32, f32, f32, vp, vp, sz, vp]),

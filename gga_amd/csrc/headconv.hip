@@ -195,17 +195,71 @@ __global__ __launch_bounds__(512, 4) void headconv_fwd16_kernel(const float* __r
 // pixels); every float4 is requested a whole tile ahead and every lane always loads (counted waits, see the forward kernel).
 // The persistent 512-thread workgroups keep their partial D in accumulators across tiles; one fixed-order fold per
 // workgroup at the end, then headconv_wgrad_final_kernel adds the workgroups (no atomics).
+// MAP: the walk skips the tiles the activity map below calls inactive (see there); MAP = false is the dense walk.
 #define HG_TR 8
 #define HG_TW 32
 #define HG_PR (HG_TR + 2)
 #define HG_PC (HG_TW + 2)
 #define HG_GP (HG_PR * HG_PC)                             // 340 staged dy values per channel
 
-template <int COUT, bool AFF>
+// Tile activity (backward of a branch whose grad_y is almost everywhere zero - the regression outputs receive a gradient only
+// at the cells of live objects, head_loss.hip gather_pred_bwd_kernel): one byte per 8 x 32 tile, non-zero when any BIT of any
+// grad_y value of any channel is set inside the tile or within one pixel around it (clipped to the image; -0.0, NaN and Inf
+// count as set). Every value the weight gradient and the tail kernels stage for an inactive tile is +0, so the tile adds +0
+// to every sum they keep: they may leave it out without changing a bit of their results. One wavefront per tile.
+__global__ __launch_bounds__(256) void head_tile_activity_kernel(const float* __restrict__ gy, int cout, int H, int W, int tiles_x,
+                                                                 int tiles_y, int64_t n_tiles, uint8_t* __restrict__ act) {
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int per_img = tiles_x * tiles_y;
+    const int b = (int)(t / per_img), rem = (int)(t - (int64_t)b * per_img);
+    const int y0 = (rem / tiles_x) * HG_TR, x0 = (rem % tiles_x) * HG_TW;
+    const int ya = max(y0 - 1, 0), yb = min(y0 + HG_TR, H - 1), xa = max(x0 - 1, 0), xb = min(x0 + HG_TW, W - 1);
+    const int nc = xb - xa + 1, per_ch = (yb - ya + 1) * nc;
+    uint32_t bits = 0;
+    for (int i = lane; i < cout * per_ch; i += 64) {
+        const int c = i / per_ch, q = i - c * per_ch;
+        const int r = q / nc, col = q - r * nc;
+        bits |= __float_as_uint(gy[(((int64_t)b * cout + c) * H + ya + r) * W + xa + col]);
+    }
+    const bool any = __ballot(bits != 0) != 0;
+    if (lane == 0) act[t] = any ? 1 : 0;
+}
+
+// The tiles first, first + stride, ... of a persistent workgroup, restricted to the active ones and in the same order: the
+// activity bytes of 64 of them are fetched with one load per lane and kept as a wave-uniform bit mask, so a step costs a
+// few scalar instructions and memory is touched once per 64 owned tiles (every wave computes the same mask).
+struct HeadTileWalk {
+    const uint8_t* act;
+    int64_t base, stride, n_tiles;
+    unsigned long long mask;
+    __device__ __forceinline__ unsigned long long window(int64_t from) const {
+        const int64_t t = from + (int64_t)(threadIdx.x & 63) * stride;
+        return __ballot(t < n_tiles && act[t] != 0);
+    }
+    __device__ __forceinline__ HeadTileWalk(const uint8_t* a, int64_t first, int64_t s, int64_t n) : act(a), base(first), stride(s), n_tiles(n) {
+        mask = window(base);
+    }
+    // the next active tile, n_tiles when there is none
+    __device__ __forceinline__ int64_t next() {
+        while (mask == 0) {
+            if (base + 64 * stride >= n_tiles) return n_tiles;
+            base += 64 * stride;
+            mask = window(base);
+        }
+        const int k = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        return base + k * stride;
+    }
+};
+
+template <int COUT, bool AFF, bool MAP>
 __global__ __launch_bounds__(512, 4) void headconv_wgrad16_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               int B, int H, int W, int tiles_x, int tiles_y, int n_tiles,
                                                               int cout_total, int co_base, const float* __restrict__ in_ss,
-                                                              int64_t xs, float* __restrict__ partials) {
+                                                              int64_t xs, const uint8_t* __restrict__ act,
+                                                              float* __restrict__ partials) {
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef float f2 __attribute__((ext_vector_type(2)));
     constexpr int NT = COUT == 1 ? 1 : 2;                // 16-column tiles of the result
@@ -276,8 +330,22 @@ __global__ __launch_bounds__(512, 4) void headconv_wgrad16_kernel(const float* _
             const int hr = (gq[e] >> 8) & 255, hx = gq[e] & 255;                                                      \
             if (hr >= 1 && hr <= HG_TR && hx >= 1 && hx <= HG_TW) bsum[e] += greg[e];     /* the tile's own pixels */  \
         } }
-    int tile = blockIdx.x;
+    // MAP: the workgroup still owns the tiles blockIdx.x, + gridDim.x, ... and visits the active ones among them in that order
+    // (see head_tile_activity_kernel) - every accumulator sees the dense walk's additions without the +0 ones, and a workgroup
+    // without an active tile writes all-zero partials. The LDS buffer parity counts visited tiles.
+    HeadTileWalk walk(MAP ? act : nullptr, MAP ? (int64_t)blockIdx.x : (int64_t)n_tiles, gridDim.x, n_tiles);
+    int tile = MAP ? (int)walk.next() : blockIdx.x;
     const int stride = gridDim.x;
+    if (MAP && tile >= n_tiles) {                         // (uniform, before any barrier) nothing to add: the zero row right away
+        float* out = partials + (int64_t)blockIdx.x * (cout_total * HC_CIN * 9 + cout_total);
+        for (int i = tid; i < 9 * COUT * HC_CIN; i += 512) {
+            const int ci = i & 63, nn = i >> 6;
+            const int o = nn / COUT, c = nn - o * COUT;
+            out[((int64_t)(co_base + c) * HC_CIN + ci) * 9 + o] = 0.0f;
+        }
+        if (tid < COUT) out[cout_total * HC_CIN * 9 + co_base + tid] = 0.0f;
+        return;
+    }
     // (the zeroes must have landed before anyone stages the first tile into the same words: without this barrier a wave that
     // was held up in the zeroing loop could wipe values another wave had already staged)
     __syncthreads();
@@ -285,9 +353,9 @@ __global__ __launch_bounds__(512, 4) void headconv_wgrad16_kernel(const float* _
 #pragma unroll
     for (int s = 0; s < 8; ++s) HG_XLOAD(tile, tile < n_tiles, s)
     HG_GSTORE(gds[0])
-    for (int it = 0; tile < n_tiles; tile += stride, ++it) {
+    for (int it = 0, nxt; tile < n_tiles; tile = nxt, ++it) {
         __syncthreads();          // tile `it` staged; every wave is done with tile it-1, so the other buffer is free
-        const int nxt = tile + stride;
+        nxt = MAP ? (int)walk.next() : tile + stride;
         const bool live = nxt < n_tiles;
         HG_GLOAD(nxt, live)
         const float* g = gds[it & 1];
@@ -422,24 +490,25 @@ extern "C" int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, cons
     return GGA_OK;
 }
 
-extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* grad_y,
-                                      int B, int H, int W, int cin, int cout, float* grad_weight, float* grad_bias,
-                                      void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = headconv_check("gga_head_conv3x3_wgrad", B, H, W, cin, cout)) return rc;
-    if (int rc = headconv_stride("gga_head_conv3x3_wgrad", x, x_pixel_stride)) return rc;
-    GGA_REQUIRE(x && grad_y && grad_weight && workspace, "gga_head_conv3x3_wgrad: null pointer argument");
+// tile_act: nullptr = walk every tile, else the map of head_tile_activity_kernel (one map serves both launches of cout = 4)
+static int headconv_wgrad_run(const char* fn, const float* x, int64_t x_pixel_stride, const float* in_scale_shift,
+                              const float* grad_y, int B, int H, int W, int cin, int cout, float* grad_weight, float* grad_bias,
+                              void* workspace, size_t workspace_bytes, const uint8_t* tile_act, hipStream_t stream) {
+    if (int rc = headconv_check(fn, B, H, W, cin, cout)) return rc;
+    if (int rc = headconv_stride(fn, x, x_pixel_stride)) return rc;
+    GGA_REQUIRE(x && grad_y && grad_weight && workspace, "%s: null pointer argument", fn);
     const int tx = (W + HG_TW - 1) / HG_TW, ty = (H + HG_TR - 1) / HG_TR;
     const int64_t n_tiles = (int64_t)B * tx * ty;
-    if (int rc = headconv_limits("gga_head_conv3x3_wgrad", H, W, x_pixel_stride, HG_TR, n_tiles)) return rc;
+    if (int rc = headconv_limits(fn, H, W, x_pixel_stride, HG_TR, n_tiles)) return rc;
     if (workspace_bytes < gga_head_conv3x3_workspace_bytes(cout)) {
-        gga_set_error("gga_head_conv3x3_wgrad: workspace too small");
+        gga_set_error("%s: workspace too small", fn);
         return GGA_ERR_WORKSPACE;
     }
     const int nb = (int)(n_tiles < HC_BLOCKS ? n_tiles : HC_BLOCKS);
     float* partials = (float*)workspace;
-#define HC_G(CO, BASE, AF) hipLaunchKernelGGL((headconv_wgrad16_kernel<CO, AF>), dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, partials)
-#define HC_W(CO, BASE) { if (in_scale_shift) HC_G(CO, BASE, true); else HC_G(CO, BASE, false); }
+#define HC_G(CO, BASE, AF, MP) hipLaunchKernelGGL((headconv_wgrad16_kernel<CO, AF, MP>), dim3(nb), dim3(512), 0, stream, x, grad_y, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, tile_act, partials)
+#define HC_A(CO, BASE, AF) { if (tile_act) HC_G(CO, BASE, AF, true); else HC_G(CO, BASE, AF, false); }
+#define HC_W(CO, BASE) { if (in_scale_shift) HC_A(CO, BASE, true) else HC_A(CO, BASE, false) }
     switch (cout) {
         case 1: HC_W(1, 0); break;
         case 2: HC_W(2, 0); break;
@@ -447,6 +516,7 @@ extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, co
         default: HC_W(2, 0); HC_W(2, 2); break;
     }
 #undef HC_W
+#undef HC_A
 #undef HC_G
     GGA_CHECK_LAUNCH("headconv_wgrad16_kernel");
     const int n_w = cout * HC_CIN * 9;
@@ -454,6 +524,13 @@ extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, co
                        cout, grad_weight, grad_bias);
     GGA_CHECK_LAUNCH("headconv_wgrad_final_kernel");
     return GGA_OK;
+}
+
+extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* grad_y,
+                                      int B, int H, int W, int cin, int cout, float* grad_weight, float* grad_bias,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return headconv_wgrad_run("gga_head_conv3x3_wgrad", x, x_pixel_stride, in_scale_shift, grad_y, B, H, W, cin, cout, grad_weight,
+                              grad_bias, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
 
@@ -469,23 +546,40 @@ extern "C" int gga_head_conv3x3_wgrad(const float* x, int64_t x_pixel_stride, co
 //   4cg..4cg+3 - its 36*COUT weights live in registers - and walks the pixels pg, pg + 16, ... of the tile,
 //   reading x as one float4 (16 lanes = the 256 contiguous bytes of a pixel).
 //   partial sums: [block][2][64] f64, the layout of bn_reduce_kernel, folded by gga_bn_bwd_finalize.
+//   MAP (gga_head_branch_bwd): with the tile activity map of head_tile_activity_kernel the sums pass visits only the tiles whose
+//   staged grad_y holds a set bit - the others rebuild dh = +0 and add +0 - and the apply pass, which has to write all of dx,
+//   skips the staging and the 36*COUT multiply-adds per pixel on the others. Same ownership of tiles by workgroups, same order:
+//   the results equal the dense walk's bit for bit (finite x). A regression branch's grad_y lives on a few object cells, so
+//   its sums pass reads a few of the 3472 tiles of x instead of 219 MB. MAP = false (gga_head_tail_bwd) is the dense walk.
 #define HT_TR 8
 #define HT_TW 32
 #define HT_HR (HT_TR + 2)
 #define HT_HW (HT_TW + 2)
 #define HT_MAX_BLOCKS 2048           // = BN_MAX_BLOCKS: the partials fit the BatchNorm workspace
 
-template <int COUT, bool APPLY>
+template <int COUT, bool APPLY, bool MAP>
 __global__ __launch_bounds__(256, COUT >= 4 ? 1 : 2) void headtail_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                           const float* __restrict__ w, const float* __restrict__ ss,
                                                           const float* __restrict__ saved, const float* __restrict__ coef,
                                                           int B, int H, int W, int tiles_x, int tiles_y, int64_t n_tiles,
-                                                          int64_t xs, int64_t dxs, double* __restrict__ partials,
-                                                          float* __restrict__ dx, uint32_t* __restrict__ amax) {
+                                                          int64_t xs, int64_t dxs, const uint8_t* __restrict__ act,
+                                                          double* __restrict__ partials, float* __restrict__ dx,
+                                                          uint32_t* __restrict__ amax) {
     uint32_t am = 0;                                     // largest finite |dx| written (apply pass)
     __shared__ float gs[2][COUT * HT_HR * HT_HW];
     __shared__ double red[APPLY ? 1 : 256][8];
     const int tid = threadIdx.x, cg = tid & 15, pg = tid >> 4;
+    // MAP (see head_tile_activity_kernel): the sums pass visits only the active tiles among the workgroup's own, in the same
+    // order - an inactive tile adds +0 to both sums - and a workgroup that owns none writes its zero row before it loads
+    // anything else. The apply pass visits every tile (dx is dense) but for an inactive one neither stages grad_y nor rebuilds
+    // dh: it evaluates the same expression with +0 in its place. The LDS buffer parity counts visits.
+    if (MAP && !APPLY) {
+        HeadTileWalk probe(act, blockIdx.x, gridDim.x, n_tiles);
+        if (probe.next() >= n_tiles) {
+            if (tid < 2 * HC_CIN) partials[(int64_t)blockIdx.x * 2 * HC_CIN + tid] = 0.0;
+            return;
+        }
+    }
     // w[co][ci][tap] -> wr[tap][co][j] for the thread's four channels
     typedef float f2 __attribute__((ext_vector_type(2)));
     f2 wr[9][COUT][2];                                   // (register pairs: channels (0, 1) and (2, 3) of the thread)
@@ -549,22 +643,69 @@ __global__ __launch_bounds__(256, COUT >= 4 ? 1 : 2) void headtail_bwd_kernel(co
                                         : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    int64_t ti = blockIdx.x;
+    // the value of one element from its rebuilt dh (or +0): the two sums, or dx
+    auto finish = [&](float gj, float xa, int j, float& o, float* f0, float* f1) {
+        const float xh = (xa - mean[j]) * inv[j];
+        if (APPLY) o = kk[j] * (gj - mg[j] - xh * mgx[j]);
+        else { f0[j] += gj; f1[j] += gj * xh; }
+    };
+    auto store_dx = [&](int b, int oy, int ox, const float* o) {
+#ifndef HT_NO_NT
+        { typedef float ht_v4f __attribute__((ext_vector_type(4))); const ht_v4f t_ = {o[0], o[1], o[2], o[3]};
+          __builtin_nontemporal_store(t_, reinterpret_cast<ht_v4f*>(dx + (((int64_t)b * H + oy) * W + ox) * dxs + 4 * cg)); }
+#else
+        *reinterpret_cast<float4*>(dx + (((int64_t)b * H + oy) * W + ox) * dxs + 4 * cg) = make_float4(o[0], o[1], o[2], o[3]);
+#endif
+        if (amax) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) am = gga_amax_of(o[j], am);
+        }
+    };
+    HeadTileWalk walk(MAP ? act : nullptr, MAP ? (int64_t)blockIdx.x : n_tiles, gridDim.x, n_tiles);
+    int64_t ti = (MAP && !APPLY) ? walk.next() : (int64_t)blockIdx.x;
+    bool on = true, on_n = true;                         // apply pass with a map: is this tile / the next one active
+    if (MAP && APPLY) on = walk.mask & 1;
     int b = 0, y0 = 0, x0 = 0;
     if (ti < n_tiles) {
         coords(ti, b, y0, x0);
-        load_g(b, y0, x0);
+        if (on) load_g(b, y0, x0);
         load_x(b, y0, x0, 0);
-        store_g(gs[0]);
+        if (on) store_g(gs[0]);
     }
     __syncthreads();
     for (int it = 0; ti < n_tiles; ++it) {
-        const int64_t tn = ti + gridDim.x;
+        const int64_t tn = (MAP && !APPLY) ? walk.next() : ti + gridDim.x;
         const bool more = tn < n_tiles;
+        if (MAP && APPLY) {                              // bit (it + 1) % 64 of the window of the workgroup's tiles 64k .. 64k + 63
+            const int k = (it + 1) & 63;
+            if (k == 0) walk.mask = walk.window(tn);
+            on_n = more && ((walk.mask >> k) & 1);
+        }
         int bn = 0, y0n = 0, x0n = 0;
-        if (more) { coords(tn, bn, y0n, x0n); load_g(bn, y0n, x0n); }
+        if (more) { coords(tn, bn, y0n, x0n); if (on_n) load_g(bn, y0n, x0n); }
         const float* g = gs[it & 1];
         float f0[4] = {0, 0, 0, 0}, f1[4] = {0, 0, 0, 0};
+        if (MAP && APPLY && !on) {
+#pragma unroll 1
+            for (int u0 = 0; u0 < (HT_TR * HT_TW) / 16; u0 += 4) {
+                float4 xv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) xv[u] = nxt[u];
+                if (u0 + 4 < (HT_TR * HT_TW) / 16) load_x(b, y0, x0, u0 + 4);
+                else if (more) load_x(bn, y0n, x0n, 0);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int p = pg + 16 * (u0 + u);
+                    const int oy = y0 + (p >> 5), ox = x0 + (p & 31);
+                    if (oy >= H || ox >= W) continue;
+                    const float xa[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
+                    float o[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) finish(0.0f, xa[j], j, o[j], f0, f1);
+                    store_dx(b, oy, ox, o);
+                }
+            }
+        } else {
 #pragma unroll 1
         for (int u0 = 0; u0 < (HT_TR * HT_TW) / 16; u0 += 4) {
             float4 xv[4];
@@ -604,34 +745,19 @@ __global__ __launch_bounds__(256, COUT >= 4 ? 1 : 2) void headtail_bwd_kernel(co
                     const float xa[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
                     float o[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float gj = fmaf(xa[j], sc[j], sf[j]) > 0.0f ? dh[j] : 0.0f;
-                        const float xh = (xa[j] - mean[j]) * inv[j];
-                        if (APPLY) o[j] = kk[j] * (gj - mg[j] - xh * mgx[j]);
-                        else { f0[j] += gj; f1[j] += gj * xh; }
-                    }
-                    if (APPLY) {
-#ifndef HT_NO_NT
-                        { typedef float ht_v4f __attribute__((ext_vector_type(4))); const ht_v4f t_ = {o[0], o[1], o[2], o[3]};
-                          __builtin_nontemporal_store(t_, reinterpret_cast<ht_v4f*>(dx + (((int64_t)b * H + oy) * W + ox) * dxs + 4 * cg)); }
-#else
-                        *reinterpret_cast<float4*>(dx + (((int64_t)b * H + oy) * W + ox) * dxs + 4 * cg) = make_float4(o[0], o[1], o[2], o[3]);
-#endif
-                        if (amax) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) am = gga_amax_of(o[j], am);
-                        }
-                    }
+                    for (int j = 0; j < 4; ++j) finish(fmaf(xa[j], sc[j], sf[j]) > 0.0f ? dh[j] : 0.0f, xa[j], j, o[j], f0, f1);
+                    if (APPLY) store_dx(b, oy, ox, o);
                 }
             }
+        }
         }
         if (!APPLY) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) { s0[j] += f0[j]; s1[j] += f1[j]; }      // 16 elements per f32 run
         }
-        if (more) store_g(gs[(it + 1) & 1]);     // last read of that buffer: tile it-1, before the previous barrier
+        if (more && on_n) store_g(gs[(it + 1) & 1]);     // last read of that buffer: tile it-1, before the previous barrier
         __syncthreads();
-        ti = tn; b = bn; y0 = y0n; x0 = x0n;
+        ti = tn; b = bn; y0 = y0n; x0 = x0n; on = on_n;
     }
     if (APPLY && amax) gga_amax_commit(am, amax);
     if (!APPLY) {
@@ -650,18 +776,18 @@ __global__ __launch_bounds__(256, COUT >= 4 ? 1 : 2) void headtail_bwd_kernel(co
     }
 }
 
-extern "C" int gga_head_tail_bwd(const float* grad_y, const float* x, int64_t x_pixel_stride, const float* scale_shift,
-                                 const float* gamma, const float* saved, const float* weight, int B, int H, int W, int cin,
-                                 int cout, float* grad_x, int64_t grad_x_pixel_stride, float* grad_gamma, float* grad_beta,
-                                 uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = headconv_check("gga_head_tail_bwd", B, H, W, cin, cout)) return rc;
-    if (int rc = headconv_stride("gga_head_tail_bwd", x, x_pixel_stride)) return rc;
-    if (int rc = headconv_stride("gga_head_tail_bwd", grad_x, grad_x_pixel_stride)) return rc;
-    GGA_REQUIRE(grad_y && x && scale_shift && saved && weight && grad_x && workspace, "gga_head_tail_bwd: null pointer argument");
+static int headtail_bwd_run(const char* fn, const float* grad_y, const float* x, int64_t x_pixel_stride, const float* scale_shift,
+                            const float* gamma, const float* saved, const float* weight, int B, int H, int W, int cin,
+                            int cout, float* grad_x, int64_t grad_x_pixel_stride, float* grad_gamma, float* grad_beta,
+                            uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, const uint8_t* tile_act,
+                            hipStream_t stream) {
+    if (int rc = headconv_check(fn, B, H, W, cin, cout)) return rc;
+    if (int rc = headconv_stride(fn, x, x_pixel_stride)) return rc;
+    if (int rc = headconv_stride(fn, grad_x, grad_x_pixel_stride)) return rc;
+    GGA_REQUIRE(grad_y && x && scale_shift && saved && weight && grad_x && workspace, "%s: null pointer argument", fn);
     const int64_t rows = (int64_t)B * H * W;
     if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, HC_CIN)) {
-        gga_set_error("gga_head_tail_bwd: workspace %zu B < required %zu B", workspace_bytes, gga_bn_relu_workspace_bytes(rows, HC_CIN));
+        gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes, gga_bn_relu_workspace_bytes(rows, HC_CIN));
         return GGA_ERR_WORKSPACE;
     }
     const int tx = (W + HT_TW - 1) / HT_TW, ty = (H + HT_TR - 1) / HT_TR;
@@ -669,7 +795,8 @@ extern "C" int gga_head_tail_bwd(const float* grad_y, const float* x, int64_t x_
     const int nb = (int)(n_tiles < HT_MAX_BLOCKS ? n_tiles : HT_MAX_BLOCKS);     // (512 .. 2048 workgroups measured: no difference beyond noise)
     double* partials = (double*)workspace;
     float* coef = nullptr;
-#define HT_GO(CO, AP) hipLaunchKernelGGL((headtail_bwd_kernel<CO, AP>), dim3(nb), dim3(256), 0, stream, grad_y, x, weight, scale_shift, saved, coef, B, H, W, tx, ty, n_tiles, x_pixel_stride, grad_x_pixel_stride, partials, grad_x, amax_grad_x)
+#define HT_GM(CO, AP, MP) hipLaunchKernelGGL((headtail_bwd_kernel<CO, AP, MP>), dim3(nb), dim3(256), 0, stream, grad_y, x, weight, scale_shift, saved, coef, B, H, W, tx, ty, n_tiles, x_pixel_stride, grad_x_pixel_stride, tile_act, partials, grad_x, amax_grad_x)
+#define HT_GO(CO, AP) { if (tile_act) HT_GM(CO, AP, true); else HT_GM(CO, AP, false); }
 #define HT_SW(AP) switch (cout) { case 1: HT_GO(1, AP); break; case 2: HT_GO(2, AP); break; case 3: HT_GO(3, AP); break; default: HT_GO(4, AP); break; }
     HT_SW(false)
     GGA_CHECK_LAUNCH("headtail_bwd_kernel<reduce>");
@@ -678,5 +805,74 @@ extern "C" int gga_head_tail_bwd(const float* grad_y, const float* x, int64_t x_
     GGA_CHECK_LAUNCH("headtail_bwd_kernel<apply>");
 #undef HT_SW
 #undef HT_GO
+#undef HT_GM
     return GGA_OK;
+}
+
+extern "C" int gga_head_tail_bwd(const float* grad_y, const float* x, int64_t x_pixel_stride, const float* scale_shift,
+                                 const float* gamma, const float* saved, const float* weight, int B, int H, int W, int cin,
+                                 int cout, float* grad_x, int64_t grad_x_pixel_stride, float* grad_gamma, float* grad_beta,
+                                 uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream) {
+    return headtail_bwd_run("gga_head_tail_bwd", grad_y, x, x_pixel_stride, scale_shift, gamma, saved, weight, B, H, W, cin, cout,
+                            grad_x, grad_x_pixel_stride, grad_gamma, grad_beta, amax_grad_x, workspace, workspace_bytes, nullptr,
+                            (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------ backward of one branch on its active tiles
+static_assert(HT_TR == HG_TR && HT_TW == HG_TW, "the weight gradient and the tail kernels share one tile numbering and one activity map");
+
+static int head_tile_activity_run(const char* fn, const float* grad_y, int B, int H, int W, int cout, uint8_t* tile_act,
+                                  hipStream_t stream) {
+    GGA_REQUIRE(B >= 1 && H >= 1 && W >= 1 && cout >= 1 && cout <= HC_MAXCO, "%s: bad sizes", fn);
+    GGA_REQUIRE(grad_y && tile_act, "%s: null pointer argument", fn);
+    const int tx = (W + HG_TW - 1) / HG_TW, ty = (H + HG_TR - 1) / HG_TR;
+    const int64_t n_tiles = (int64_t)B * tx * ty;
+    GGA_REQUIRE(n_tiles < 2147483647ll, "%s: too many tiles (%lld)", fn, (long long)n_tiles);
+    hipLaunchKernelGGL(head_tile_activity_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, grad_y, cout, H, W,
+                       tx, ty, n_tiles, tile_act);
+    GGA_CHECK_LAUNCH("head_tile_activity_kernel");
+    return GGA_OK;
+}
+
+static int64_t head_tile_count(int B, int H, int W) {
+    return (int64_t)B * ((W + HG_TW - 1) / HG_TW) * ((H + HG_TR - 1) / HG_TR);
+}
+
+extern "C" int gga_head_tile_activity(const float* grad_y, int B, int H, int W, int cout, uint8_t* tile_active, void* stream) {
+    return head_tile_activity_run("gga_head_tile_activity", grad_y, B, H, W, cout, tile_active, (hipStream_t)stream);
+}
+
+// workspace of gga_head_branch_bwd: [weight-gradient partials][BatchNorm partials + coefficients][activity map]
+static size_t hb_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+extern "C" size_t gga_head_branch_bwd_workspace_bytes(int B, int H, int W, int cout) {
+    return hb_align(gga_head_conv3x3_workspace_bytes(cout)) + hb_align(gga_bn_relu_workspace_bytes((int64_t)B * H * W, HC_CIN)) +
+           hb_align((size_t)head_tile_count(B, H, W));
+}
+
+extern "C" int gga_head_branch_bwd(const float* grad_y, const float* x, int64_t x_pixel_stride, const float* scale_shift,
+                                   const float* gamma, const float* saved, const float* weight, int B, int H, int W, int cin,
+                                   int cout, float* grad_weight, float* grad_bias, float* grad_x, int64_t grad_x_pixel_stride,
+                                   float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x, int sparse_grad_y,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_head_branch_bwd";
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = headconv_check(fn, B, H, W, cin, cout)) return rc;
+    GGA_REQUIRE(workspace, "%s: null pointer argument", fn);
+    if (workspace_bytes < gga_head_branch_bwd_workspace_bytes(B, H, W, cout)) {
+        gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes, gga_head_branch_bwd_workspace_bytes(B, H, W, cout));
+        return GGA_ERR_WORKSPACE;
+    }
+    const size_t wg_bytes = hb_align(gga_head_conv3x3_workspace_bytes(cout));
+    const size_t bn_bytes = hb_align(gga_bn_relu_workspace_bytes((int64_t)B * H * W, HC_CIN));
+    char* ws = (char*)workspace;
+    // (a gradient the caller knows to be dense - a heat-map branch's - takes the dense walk: the map would call every tile
+    // active, and building and reading it costs 15-20 us of a 190 us branch)
+    uint8_t* tile_act = sparse_grad_y ? (uint8_t*)(ws + wg_bytes + bn_bytes) : nullptr;
+    if (tile_act)
+        if (int rc = head_tile_activity_run(fn, grad_y, B, H, W, cout, tile_act, stream)) return rc;
+    if (int rc = headconv_wgrad_run(fn, x, x_pixel_stride, scale_shift, grad_y, B, H, W, cin, cout, grad_weight, grad_bias, ws,
+                                    wg_bytes, tile_act, stream)) return rc;
+    return headtail_bwd_run(fn, grad_y, x, x_pixel_stride, scale_shift, gamma, saved, weight, B, H, W, cin, cout, grad_x,
+                            grad_x_pixel_stride, grad_gamma, grad_beta, amax_grad_x, ws + wg_bytes, bn_bytes, tile_act, stream);
 }

@@ -78,7 +78,8 @@ class SeparateHead(nn.Module):
             for m in mods[:-2] if fuse else mods[:-1]:
                 y = m(y)
             if fuse:      # norm + ReLU of the last ConvModule applied inside the output conv's loads
-                out[head] = F.bn_relu_head_conv3x3(dense_conv.conv2d(y, last.conv, bn_follows=last.norm.training), last.norm, mods[-1])
+                out[head] = F.bn_relu_head_conv3x3(dense_conv.conv2d(y, last.conv, bn_follows=last.norm.training), last.norm, mods[-1],
+                                                   sparse_grad=head != 'heatmap')
             else:
                 out[head] = F.head_conv3x3(y, mods[-1])     # 1-3 channel output conv: HBM-bound HIP kernel
         return out
@@ -172,7 +173,10 @@ class CenterHead_GGA(nn.Module):
                     branches.append((mods[0].conv, mods[0].norm, mods[1]))
                     keys.append((ti, head))
         n_all = sum(len(getattr(task, 'heads', ())) for task in self.task_heads)
-        outs = F.head_branches(x, branches) if branches and len(branches) == n_all and self.training else None
+        # (the regression outputs are read through gather_pred at object cells only: their gradient is zero almost everywhere;
+        # the heat-map's, from the focal loss, is dense)
+        outs = (F.head_branches(x, branches, sparse_grad=[head != 'heatmap' for _, head in keys])
+                if branches and len(branches) == n_all and self.training else None)
         if outs is None:
             return [task(x) for task in self.task_heads]
         ret = [dict() for _ in self.task_heads]

@@ -988,7 +988,8 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
     grad_y in registers (gga_head_tail_bwd: no backward-data tensor)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, weight, bias, eps, momentum, training, partials=None):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, weight, bias, eps, momentum, training, partials=None,
+                sparse_grad=True):
         L = _lib.lib()
         B, C, H, W = x.shape
         rows, cout = B * H * W, weight.shape[0]
@@ -1008,7 +1009,7 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
         check(L.gga_head_conv3x3_fwd(_p(x), C, _p(ss), _p(w), _p(bias), B, H, W, C, cout, _p(y), _stream()),
               'gga_head_conv3x3_fwd')
         ctx.save_for_backward(x, gamma, saved, ss, w)
-        ctx.has_bias = bias is not None
+        ctx.has_bias, ctx.sparse_grad = bias is not None, bool(sparse_grad)
         return y
 
     @staticmethod
@@ -1021,25 +1022,26 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
         dev = x.device
         gw = torch.empty_like(w)
         gb = torch.empty(cout, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        ws = _workspace('headconv', L.gga_head_conv3x3_workspace_bytes(cout), dev)
-        check(L.gga_head_conv3x3_wgrad(_p(x), C, _p(ss), _p(gy), B, H, W, C, cout, _p(gw), _p(gb), _p(ws), ws.numel(),
-                                       _stream()), 'gga_head_conv3x3_wgrad')
-        # BatchNorm + ReLU backward with the conv's input gradient rebuilt from gy on the fly (never stored)
+        # the weight gradient, then BatchNorm + ReLU backward with the conv's input gradient rebuilt from gy on the fly (never
+        # stored); both on the tiles of gy that hold anything
         gx = torch.empty_like(x)
         gg = torch.empty(C, dtype=torch.float32, device=dev)
         gbeta = torch.empty(C, dtype=torch.float32, device=dev)
-        wsb = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
+        ws = _workspace('headbranch', L.gga_head_branch_bwd_workspace_bytes(B, H, W, cout), dev)
         from . import dense_conv
         amax = dense_conv.new_amax(dev)
-        check(L.gga_head_tail_bwd(_p(gy), _p(x), C, _p(ss), _p(gamma), _p(saved), _p(w), B, H, W, C, cout, _p(gx), C, _p(gg), _p(gbeta),
-                                  _p(amax), _p(wsb), wsb.numel(), _stream()), 'gga_head_tail_bwd')
+        check(L.gga_head_branch_bwd(_p(gy), _p(x), C, _p(ss), _p(gamma), _p(saved), _p(w), B, H, W, C, cout, _p(gw), _p(gb), _p(gx), C,
+                                    _p(gg), _p(gbeta), _p(amax), int(ctx.sparse_grad), _p(ws), ws.numel(), _stream()),
+              'gga_head_branch_bwd')
         dense_conv.set_amax(gx, amax)
-        return gx, gg, gbeta, None, None, gw, gb, None, None, None, None
+        return gx, gg, gbeta, None, None, gw, gb, None, None, None, None, None
 
 
-def bn_relu_head_conv3x3(x, bn, conv):
+def bn_relu_head_conv3x3(x, bn, conv, sparse_grad=True):
     """``conv(relu(bn(x)))`` (tail of a SeparateHead branch: the ConvModule's norm + activation
-    and the output conv), fused when both halves qualify for their HIP kernels in training mode."""
+    and the output conv), fused when both halves qualify for their HIP kernels in training mode.
+    ``sparse_grad``: a hint for the backward, never a change of its result - False when the output's gradient is
+    known to be dense (a heat-map), see ``gga_head_branch_bwd``."""
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32) else None
     ok = (rc is not None and x.dim() == 4 and x.shape[1] == 64 and bn.affine and bn.track_running_stats
           and bn.momentum is not None and bn.training and torch.is_grad_enabled() and conv.out_channels <= 4
@@ -1050,7 +1052,7 @@ def bn_relu_head_conv3x3(x, bn, conv):
     count_batch(bn)
     partials = bn_partials_of(x)
     return _BnReluHeadConv3x3.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.weight, conv.bias,
-                                    float(bn.eps), float(bn.momentum), True, partials)
+                                    float(bn.eps), float(bn.momentum), True, partials, sparse_grad)
 
 
 _BRANCH_STREAMS = {}
@@ -1074,8 +1076,10 @@ class _HeadBranches(torch.autograd.Function):
 
     Forward: per branch the bf16x6 convolution writes its 64 channels (and their BatchNorm sums) into a column
     block of ONE [B, 64n, H, W] channels-last buffer, the statistics are folded, and the output conv normalises
-    while it loads. Backward: per branch the output conv's weight gradient and ``gga_head_tail_bwd``, which
-    writes the gradient w.r.t. the branch's column block of a second [B, 64n, H, W] buffer; then ONE
+    while it loads. Backward: per branch ``gga_head_branch_bwd`` - the output conv's weight gradient and the tail's
+    BatchNorm backward, both on the tiles of the branch's output gradient that hold anything (the regression branches
+    receive one at a few object cells only) - which writes the gradient w.r.t. the branch's column block of a second
+    [B, 64n, H, W] buffer; then ONE
     backward-data convolution 64n -> 64 and ONE weight-gradient call over all branches - where one node per
     branch left autograd n - 1 full-size additions of the shared map's gradient."""
 
@@ -1112,7 +1116,7 @@ class _HeadBranches(torch.autograd.Function):
         for st_ in streams[1:]:
             st_.wait_stream(streams[0])
         for i in range(n):
-            eps, momentum = cfg[i]
+            eps, momentum = cfg[i][:2]
             stats, col = all_stats[i]
             tiles = int(stats.shape[0])
             with torch.cuda.stream(streams[i % len(streams)]):
@@ -1125,6 +1129,7 @@ class _HeadBranches(torch.autograd.Function):
             streams[0].wait_stream(st_)
         ctx.save_for_backward(x, Y, *w1, *gam, *w2, *saved_all, *ss_all)
         ctx.n, ctx.has_bias, ctx.x_amax = n, [b is not None for b in b2], x_amax
+        ctx.sparse_grad = [int(c[2]) for c in cfg]
         ctx.bn_src = dense_conv.bn_source(x, C) if dense_conv.BN_BWD_FUSED else None     # x = relu(bn(shared conv))
         return tuple(outs)
 
@@ -1159,14 +1164,11 @@ class _HeadBranches(torch.autograd.Function):
         for i in range(n):
             cout = w2[i].shape[0]
             with torch.cuda.stream(streams[i % len(streams)]):
-                ws = _workspace('headconv', L.gga_head_conv3x3_workspace_bytes(cout), dev)       # (scratch buffers are per stream)
-                wsb = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
-                check(L.gga_head_conv3x3_wgrad(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(gyc[i]), B, H, W, C, cout, _p(gw2[i]),
-                                               _p(gb2[i]), _p(ws), ws.numel(), _stream()), 'gga_head_conv3x3_wgrad')
-                check(L.gga_head_tail_bwd(_p(gyc[i]), Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(gam[i]), _p(saved_all[i]), _p(w2c[i]),
-                                          B, H, W, C, cout, G.data_ptr() + 4 * C * i, tot, _p(ggam[i]), _p(gbet[i]),
-                                          _p(g_blocks[i:i + 1] if g_blocks is not None else None), _p(wsb), wsb.numel(),
-                                          _stream()), 'gga_head_tail_bwd')
+                ws = _workspace('headbranch', L.gga_head_branch_bwd_workspace_bytes(B, H, W, cout), dev)       # (scratch buffers are per stream)
+                check(L.gga_head_branch_bwd(_p(gyc[i]), Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(gam[i]), _p(saved_all[i]),
+                                            _p(w2c[i]), B, H, W, C, cout, _p(gw2[i]), _p(gb2[i]), G.data_ptr() + 4 * C * i, tot,
+                                            _p(ggam[i]), _p(gbet[i]), _p(g_blocks[i:i + 1] if g_blocks is not None else None),
+                                            ctx.sparse_grad[i], _p(ws), ws.numel(), _stream()), 'gga_head_branch_bwd')
         for st_ in streams[1:]:
             streams[0].wait_stream(st_)
         wcat = [w.detach() for w in w1]            # stands for the [64n, 64, 3, 3] concatenation (weight bank: never made)
@@ -1178,9 +1180,11 @@ class _HeadBranches(torch.autograd.Function):
         return (gx, None, None, *gw1, *ggam, *gbet, *none, *none, *gw2, *gb2)
 
 
-def head_branches(x, branches):
+def head_branches(x, branches, sparse_grad=None):
     """Outputs of the head branches ``[(conv1, bn, conv2), ...]`` that all read ``x`` (see _HeadBranches), or
-    None when a branch does not qualify for the fused kernels (the caller then runs them one by one)."""
+    None when a branch does not qualify for the fused kernels (the caller then runs them one by one).
+    ``sparse_grad``: per branch, False where the output's gradient is known to be dense (a heat-map) - a hint for
+    ``gga_head_branch_bwd``, never a change of the result; default: every branch may be sparse."""
     from . import dense_conv
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) else None
     if rc is None or x.shape[1] != 64 or not torch.is_grad_enabled() or not dense_conv.ENABLED or not dense_conv.WGRAD:
@@ -1196,7 +1200,9 @@ def head_branches(x, branches):
     for _, bn, _ in branches:
         count_batch(bn)
     n = len(branches)
-    cfg = tuple((float(bn.eps), float(bn.momentum)) for _, bn, _ in branches)
+    sparse = [True] * n if sparse_grad is None else [bool(s) for s in sparse_grad]
+    assert len(sparse) == n
+    cfg = tuple((float(bn.eps), float(bn.momentum), s) for (_, bn, _), s in zip(branches, sparse))
     cols = ([c1.weight for c1, _, _ in branches], [bn.weight for _, bn, _ in branches], [bn.bias for _, bn, _ in branches],
             [bn.running_mean for _, bn, _ in branches], [bn.running_var for _, bn, _ in branches],
             [c2.weight for _, _, c2 in branches], [c2.bias for _, _, c2 in branches])

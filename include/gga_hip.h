@@ -613,6 +613,28 @@ int gga_head_tail_bwd(const float* grad_y, const float* x, int64_t x_pixel_strid
                       float* grad_x, int64_t grad_x_pixel_stride, float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which 8 x 32 tiles of a branch's output gradient hold anything: tile_active[(b * tiles_y + ty) * tiles_x + tx]
+ * (tiles_x = ceil(W / 32), tiles_y = ceil(H / 8), one byte each) is 1 when any bit of any value of any of the cout
+ * channels of grad_y [B,cout,H,W] is set inside the tile or within one pixel around it (clipped to the image; -0.0, NaN
+ * and Inf count as set), else 0. The regression branches of a CenterHead receive a gradient only at the cells of live
+ * objects (F.gather_pred), so nearly all of their tiles are inactive. */
+int gga_head_tile_activity(const float* grad_y, int B, int H, int W, int cout, uint8_t* tile_active, void* stream);
+
+/* Backward of one head branch = gga_head_conv3x3_wgrad (with in_scale_shift = scale_shift) followed by
+ * gga_head_tail_bwd, same arguments and bit-identical results for finite x, on the active tiles of grad_y: the
+ * weight gradient and the BatchNorm-backward sums visit only those (an inactive tile contributes exactly +0 to every
+ * sum), and the pass that writes grad_x skips the rebuild of the conv's input gradient on the others.
+ * sparse_grad_y: a hint, never a change of the result - 0 for a gradient known to be dense (a heat-map branch's): no map
+ * is built and every tile is visited, exactly the two calls above; non-zero otherwise (a dense gradient then costs the
+ * map on top: measured +15-20 us per branch at 16 x 248 x 216).
+ * workspace: gga_head_branch_bwd_workspace_bytes(B, H, W, cout), used by this stream alone until the call's work is done. */
+size_t gga_head_branch_bwd_workspace_bytes(int B, int H, int W, int cout);
+int gga_head_branch_bwd(const float* grad_y, const float* x, int64_t x_pixel_stride, const float* scale_shift,
+                        const float* gamma, const float* saved, const float* weight, int B, int H, int W, int cin, int cout,
+                        float* grad_weight, float* grad_bias, float* grad_x, int64_t grad_x_pixel_stride, float* grad_gamma,
+                        float* grad_beta, uint32_t* amax_grad_x, int sparse_grad_y, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* a6/a7. Heat-map target splat on the device.                                */
 /* Replaces the per-object numpy gaussian + H2D copy + torch.max(out=) of     */
