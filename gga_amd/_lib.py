@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _lib = None
 
@@ -50,6 +50,16 @@ SIGNATURES = {
                                        vp, vp, vp, vp, vp, sz, vp]),
     'gga_hard_voxelize_prepared': (i32, [vp, i32, C.POINTER(C.c_int64), vp, i32, C.POINTER(VoxelParams),
                                           vp, vp, vp, vp, vp, sz, vp]),
+    'gga_dynamic_voxelize': (i32, [vp, i32, C.POINTER(C.c_int64), vp, i32, C.POINTER(VoxelParams), vp, vp, vp]),
+    'gga_dynamic_voxel_map_workspace_bytes': (sz, [i64]),
+    'gga_dynamic_voxel_map': (i32, [vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'gga_dynamic_scatter_chunk': (i32, []),
+    'gga_dynamic_scatter_workspace_bytes': (sz, [i64, i32]),
+    'gga_dynamic_scatter_fwd': (i32, [vp, i32, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, sz, vp]),
+    'gga_dynamic_scatter_bwd': (i32, [vp, i32, i64, vp, vp, vp, i64, i32, vp, vp]),
+    'gga_dynamic_pfn_workspace_bytes': (sz, [i64]),
+    'gga_dynamic_pfn_fwd': (i32, [vp, vp, i64, vp, vp, vp, vp, i64, C.POINTER(PfnParams)] + [vp] * 10 + [sz, vp]),
+    'gga_dynamic_pfn_bwd': (i32, [vp, vp, i64, vp, i64, C.POINTER(PfnParams)] + [vp] * 11 + [sz, vp]),
     'gga_points_prepare_workspace_bytes': (sz, [i32, i64, i64]),
     'gga_points_prepare_batch': (i32, [vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64),
                                         i32, i32, C.c_double, vp, C.POINTER(C.c_uint64), vp, vp, vp, sz, vp]),

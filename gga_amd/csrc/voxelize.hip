@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void vox_insert_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         // floor((p - lo) / vs) in f32, true division (voxel_generator.py:189)
-        float cf = floorf(__fdiv_rn(__fsub_rn(p[j], g.lo[j]), g.vs[j]));
+        float cf = gga_voxel_cell(p[j], g.lo[j], g.vs[j]);
         ok = ok && (cf >= 0.0f) && (cf < (float)g.grid[j]);
         c[j] = (int32_t)cf;
     }

@@ -33,10 +33,13 @@ class PreparedInputs:
         return self.n_frames
 
     def tensors(self):
-        yield from (self.voxels, self.num_points, self.coors)
+        yield from (t for t in (self.voxels, self.num_points, self.coors) if t is not None)
         for extra in (getattr(self.coors, 'num_valid', None),):
             if extra is not None:
                 yield extra
+        vmap = getattr(self.coors, 'voxel_map', None)       # dynamic voxelization: `voxels` are the points, one coors row each
+        if vmap is not None:
+            yield from vmap.tensors()
         plan = getattr(self.coors, 'index_plan', None)
         if plan is not None:
             yield from plan.tensors()
@@ -89,7 +92,15 @@ class MVXTwoStageDetector_GGA(nn.Module):
             voxels, num_points, coors = pts.voxels, pts.num_points, pts.coors
         else:
             voxels, num_points, coors = self.voxelize(pts)
-        voxel_features = self.pts_voxel_encoder(voxels, num_points, coors)
+        if self.dynamic_voxelization:
+            # DynamicVoxelNet.extract_feat (dynamic_voxelnet.py:39-50): the encoder takes the points and their cells
+            # and returns the voxels' features with the voxels' coordinates
+            if self._dynamic_front_is_sync_free():
+                voxel_features, coors = self.pts_voxel_encoder(voxels, coors, capacity=True)
+            else:
+                voxel_features, coors = self.pts_voxel_encoder(voxels, coors)
+        else:
+            voxel_features = self.pts_voxel_encoder(voxels, num_points, coors)
         batch_size = len(pts)      # the reference reads coors[-1, 0] + 1 back from the device
         x = self.pts_middle_encoder(voxel_features, coors, batch_size)
         x = self.pts_backbone(x)
@@ -108,15 +119,31 @@ class MVXTwoStageDetector_GGA(nn.Module):
         one batched HIP call instead of the per-frame loop + cat + pad of the reference."""
         # no host read-back when both consumers take the device-side pillar count (fused PFN + scatter):
         # the buffers then keep their capacity B * max_voxels and `coors.num_valid` carries the count
+        if self.dynamic_voxelization:
+            # DynamicVoxelNet.voxelize (dynamic_voxelnet.py:52-72): -> points [SN,C], None, coors [SN,4] per point, which
+            # carry the sorted point-to-voxel map of the batch
+            cat, coors = self.pts_voxel_layer.forward_batch(points)
+            return cat, None, coors
         sync = not (getattr(self.pts_voxel_encoder, 'accepts_num_valid', False)
                     and getattr(self.pts_middle_encoder, 'accepts_num_valid', False))
         voxels, num_points, coors, _ = self.pts_voxel_layer.forward_batch(points, sync=sync)
         return voxels, num_points, coors
 
+    def _dynamic_front_is_sync_free(self):
+        enc = self.pts_voxel_encoder
+        return (getattr(enc, 'accepts_num_valid', False) and getattr(self.pts_middle_encoder, 'accepts_num_valid', False)
+                and hasattr(enc, 'fusable_config') and enc.fusable_config())
+
+    dynamic_voxelization = property(lambda self: getattr(getattr(self, 'pts_voxel_layer', None), 'dynamic', False))
+
     @property
     def front_reads_counts(self):
         """True when the point-only front of a step reads voxel / site counts back to the host
         (the sparse-conv trunk: data-dependent level sizes); the PointPillars front does not."""
+        if self.dynamic_voxelization:
+            # the fused pillar front hands capacity-sized rows and a device-side count on; every other dynamic encoder sizes
+            # its outputs by the voxel count (one read per batch)
+            return not self._dynamic_front_is_sync_free()
         return not (getattr(self.pts_voxel_encoder, 'accepts_num_valid', False)
                     and getattr(self.pts_middle_encoder, 'accepts_num_valid', False))
 
@@ -129,6 +156,10 @@ class MVXTwoStageDetector_GGA(nn.Module):
         if isinstance(points, PreparedInputs):
             return points
         voxels, num_points, coors = self.voxelize(points)
+        if self.dynamic_voxelization:
+            if self.front_reads_counts:
+                coors.voxel_map.host_counts()   # the one read-back of the dynamic front, taken here (on the side stream)
+            return PreparedInputs(voxels, None, coors, len(points))
         if hasattr(self.pts_middle_encoder, 'build_indices'):
             coors = self.pts_middle_encoder.build_indices(coors, len(points))
         return PreparedInputs(voxels, num_points, coors, len(points))

@@ -1,0 +1,193 @@
+"""Dynamic voxelization on the HIP kernels of gga_amd/csrc/dynamic_voxel.hip: per-point cells, the sorted
+point-to-voxel map (built once per batch and carried by the coordinates tensor as ``coors.voxel_map``) and the
+segmented mean / max over it that ``ops.DynamicScatter`` and the dynamic voxel encoders are made of."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import functional as F
+from ._lib import check
+
+MEAN, MAX = 0, 1
+
+
+class VoxelMap:
+    """Point-to-voxel map of ``n`` points (capacity ``n`` everywhere, nothing read back until ``m`` is asked for):
+    ``voxel_coors [n,4]`` ascending (b,z,y,x) - the order of ``torch.unique(dim=0)`` -, ``voxel_start [n+1]``,
+    ``order [n]`` (point indices grouped by voxel, ascending inside a voxel), ``point2voxel [n]`` (-1 = dropped),
+    ``counts [2]`` = (voxels, points kept) on the device."""
+
+    def __init__(self, n, batch, grid, voxel_coors, voxel_start, order, point2voxel, counts):
+        self.n, self.batch, self.grid = int(n), int(batch), tuple(grid)
+        self.voxel_coors, self.voxel_start, self.order, self.point2voxel, self.counts = \
+            voxel_coors, voxel_start, order, point2voxel, counts
+        self._host = None
+
+    @property
+    def num_valid(self):
+        return self.counts[:1]
+
+    def host_counts(self):
+        """(voxels M, points kept) on the host: ONE read-back per map, however many scatters use it."""
+        if self._host is None:
+            self._host = tuple(int(v) for v in self.counts.cpu().tolist()) if self.n else (0, 0)
+        return self._host
+
+    @property
+    def m(self):
+        return self.host_counts()[0]
+
+    def tensors(self):
+        yield from (self.voxel_coors, self.voxel_start, self.order, self.point2voxel, self.counts)
+
+
+def grid_of(voxel_size, point_cloud_range):
+    return F.voxel_grid_size(F.voxel_params(voxel_size, point_cloud_range, 1, 1))
+
+
+def _as_offsets(arr):
+    return np.ascontiguousarray(arr, np.int64)
+
+
+@torch.no_grad()
+def build_map(n, batch, grid, dev, keys=None, coors=None):
+    """Map of ``keys`` (u32 as int32 storage, from :func:`dynamic_voxelize`) or of caller-supplied ``coors``
+    ([n,3] (z,y,x) or [n,4] (b,z,y,x), int32)."""
+    L = _lib.lib()
+    gx, gy, gz = (int(g) for g in grid)
+    if n == 0:          # (empty tensors have no device pointer to pass)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        return VoxelMap(0, batch, (gx, gy, gz), z(0, 4), z(1), z(0), z(0), z(2))
+    voxel_coors = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    voxel_start = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    p2v = torch.empty((n,), dtype=torch.int32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    ws = F._workspace('dvmap', max(L.gga_dynamic_voxel_map_workspace_bytes(n), 1), dev)
+    cols = 0 if coors is None else int(coors.shape[1])
+    check(L.gga_dynamic_voxel_map(F._p(keys), F._p(coors), cols, n, int(batch), gx, gy, gz, F._p(voxel_coors),
+                                  F._p(voxel_start), F._p(order), F._p(p2v), F._p(counts), F._p(ws), ws.numel(),
+                                  F._stream()), 'gga_dynamic_voxel_map')
+    return VoxelMap(n, batch, (gx, gy, gz), voxel_coors, voxel_start, order, p2v, counts)
+
+
+@torch.no_grad()
+def dynamic_voxelize(cat, offsets, counts_dev, voxel_size, point_cloud_range):
+    """``cat`` [total, C] f32 (frames at ``offsets``; ``counts_dev`` = device-side point counts of frames stored at capacity
+    offsets, or None) -> coors [total,4] int32 (b,z,y,x) carrying ``coors.voxel_map``; a point outside the grid (or past its
+    frame's count, or not finite) gets (b,-1,-1,-1) and takes part in nothing."""
+    F._need_cuda(cat)
+    if cat.dtype != torch.float32:
+        cat = cat.float()
+    cat = cat.contiguous()
+    offs = _as_offsets(offsets)
+    B, total, dev = len(offs) - 1, int(offs[-1]), cat.device
+    prm = F.voxel_params(voxel_size, point_cloud_range, 1, 1)
+    coors = torch.empty((total, 4), dtype=torch.int32, device=dev)
+    keys = torch.empty((total,), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    if total:          # (empty tensors have no device pointer to pass)
+        check(L.gga_dynamic_voxelize(F._p(cat), int(cat.shape[1]), offs.ctypes.data_as(C.POINTER(C.c_int64)), F._p(counts_dev),
+                                     B, C.byref(prm), F._p(coors), F._p(keys), F._stream()), 'gga_dynamic_voxelize')
+    coors.voxel_map = build_map(total, B, F.voxel_grid_size(prm), dev, keys=keys)
+    return coors
+
+
+def map_of(coors, grid, batch=None):
+    """The map ``coors`` carries, or a new one built from its values (mmcv rebuilds a ``unique`` in every scatter call)."""
+    vmap = getattr(coors, 'voxel_map', None)
+    if vmap is not None and vmap.n == coors.shape[0] and vmap.grid == tuple(int(g) for g in grid):
+        return vmap
+    F._need_cuda(coors)
+    assert coors.dim() == 2 and coors.shape[1] in (3, 4), f'coors {tuple(coors.shape)} must be [N,3] or [N,4]'
+    c = coors.int().contiguous()
+    if batch is None:
+        # (the reference reads coors[-1, 0] + 1 back as well)
+        batch = 1 if c.shape[1] == 3 or c.shape[0] == 0 else max(int(c[:, 0].max().item()) + 1, 1)
+    return build_map(c.shape[0], batch, grid, c.device, coors=c)
+
+
+class _DynamicScatter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, vmap, mode, rows):
+        F._need_cuda(feats)
+        x = feats.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        n, ch = x.shape
+        assert n == vmap.n, f'{n} feature rows for a map of {vmap.n} points'
+        dev = x.device
+        L = _lib.lib()
+        out = torch.zeros((rows, ch), dtype=torch.float32, device=dev)
+        argmax = torch.zeros((rows, ch), dtype=torch.int32, device=dev) if mode == MAX else None
+        ws = F._workspace('dvscat', max(L.gga_dynamic_scatter_workspace_bytes(n, ch), 1), dev)
+        check(L.gga_dynamic_scatter_fwd(F._p(x), ch, n, F._p(vmap.order), F._p(vmap.point2voxel), F._p(vmap.voxel_start),
+                                        F._p(vmap.counts), rows, mode, F._p(out), F._p(argmax), F._p(ws), ws.numel(),
+                                        F._stream()), 'gga_dynamic_scatter_fwd')
+        ctx.vmap, ctx.mode, ctx.shape, ctx.argmax, ctx.in_dtype = vmap, mode, (n, ch), argmax, feats.dtype
+        if argmax is not None:
+            ctx.mark_non_differentiable(argmax)
+            return out, argmax
+        return out, None
+
+    @staticmethod
+    def backward(ctx, g, _ga=None):
+        vmap, (n, ch) = ctx.vmap, ctx.shape
+        g = g.contiguous().float()
+        gin = torch.empty((n, ch), dtype=torch.float32, device=g.device)
+        check(_lib.lib().gga_dynamic_scatter_bwd(F._p(g), ch, n, F._p(vmap.point2voxel), F._p(vmap.voxel_start),
+                                                 F._p(ctx.argmax), g.shape[0], ctx.mode, F._p(gin), F._stream()),
+              'gga_dynamic_scatter_bwd')
+        return gin.to(ctx.in_dtype), None, None, None
+
+
+def scatter(feats, vmap, mode, rows=None, return_argmax=False):
+    """Mean (``MEAN``) or max (``MAX``) of ``feats [n,C]`` over the voxels of ``vmap`` -> ``[rows, C]``; ``rows`` defaults to
+    the exact voxel count (one host read per map), ``rows = vmap.n`` keeps the capacity and reads nothing back."""
+    rows = vmap.m if rows is None else int(rows)
+    out, argmax = _DynamicScatter.apply(feats, vmap, mode, rows)
+    return (out, argmax) if return_argmax else out
+
+
+class _FusedDynamicPFN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, coors, vmap, weight, gamma, beta, running_mean, running_var, prm, rows):
+        F._need_cuda(points, coors, weight)
+        n, dev = points.shape[0], points.device
+        L = _lib.lib()
+        out = torch.zeros((rows, 64), dtype=torch.float32, device=dev)
+        argmax = torch.zeros((rows, 64), dtype=torch.int32, device=dev)
+        mean = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        saved = torch.empty(239, dtype=torch.float64, device=dev)
+        ws = F._workspace('dvpfn', L.gga_dynamic_pfn_workspace_bytes(n), dev)
+        w = weight.contiguous()
+        check(L.gga_dynamic_pfn_fwd(F._p(points), F._p(coors), n, F._p(vmap.order), F._p(vmap.point2voxel), F._p(vmap.voxel_start),
+                                    F._p(vmap.counts), rows, C.byref(prm), F._p(w), F._p(gamma), F._p(beta), F._p(running_mean),
+                                    F._p(running_var), F._p(out), F._p(argmax), F._p(mean), F._p(saved), F._p(ws), ws.numel(),
+                                    F._stream()), 'gga_dynamic_pfn_fwd')
+        ctx.save_for_backward(points, coors, w, gamma, out, argmax, mean, saved)
+        ctx.prm, ctx.vmap = prm, vmap
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        points, coors, w, gamma, out, argmax, mean, saved = ctx.saved_tensors
+        n = points.shape[0]
+        L = _lib.lib()
+        gw, gg, gb = torch.empty_like(w), torch.empty_like(gamma), torch.empty_like(gamma)
+        ws = F._workspace('dvpfn', L.gga_dynamic_pfn_workspace_bytes(n), g.device)
+        g = g.contiguous()
+        check(L.gga_dynamic_pfn_bwd(F._p(points), F._p(coors), n, F._p(ctx.vmap.counts), out.shape[0], C.byref(ctx.prm), F._p(w),
+                                    F._p(gamma), F._p(out), F._p(argmax), F._p(mean), F._p(saved), F._p(g), F._p(gw), F._p(gg),
+                                    F._p(gb), F._p(ws), ws.numel(), F._stream()), 'gga_dynamic_pfn_bwd')
+        return None, None, None, gw, gg, gb, None, None, None, None
+
+
+def fused_pfn(points, coors, vmap, weight, gamma, beta, running_mean, running_var, prm, rows=None):
+    """Fused DynamicPillarFeatureNet: points [N,4] with their cells [N,4] and map -> [rows,64] (running stats updated in place
+    when training). ``rows`` defaults to the capacity N: nothing is read back, rows past the device-side voxel count
+    (``vmap.num_valid``) are zero."""
+    rows = vmap.n if rows is None else int(rows)
+    return _FusedDynamicPFN.apply(points, coors, vmap, weight, gamma, beta, running_mean, running_var, prm, rows)

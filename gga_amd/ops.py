@@ -7,8 +7,11 @@ gga_amd/csrc/postproc.hip, with the call signatures the reference uses:
 * ``box_iou_rotated(b1, b2, mode='iou', aligned=False)`` — mmcv op used by base_box3d.py:469
 * ``points_in_boxes_part / points_in_boxes_all(points [B,M,3], boxes [B,T,7])`` — base_box3d.py:534,566
 * ``xywhr2xyxyr`` — mmdet3d/core/bbox/structures/utils.py:121-139
+* ``DynamicScatter(voxel_size, point_cloud_range, average_points)`` — ``mmcv.ops.DynamicScatter`` as the dynamic voxel
+  encoders use it (voxel_encoders/voxel_encoder.py:64,155-174), on gga_amd/csrc/dynamic_voxel.hip
 """
 import torch
+from torch import nn
 
 from . import _lib
 from . import functional as F
@@ -159,3 +162,31 @@ def box3d_multiclass_nms(mlvl_bboxes, mlvl_bboxes_for_nms, mlvl_scores, score_th
     empty = (mlvl_scores.new_zeros((0, mlvl_bboxes.size(-1))), mlvl_scores.new_zeros((0, )),
              mlvl_scores.new_zeros((0, ), dtype=torch.long))
     return empty + tuple(t.new_zeros((0, ) + tuple(t.shape[1:])) for t in extras)
+
+
+class DynamicScatter(nn.Module):
+    """``forward(points [N,C], coors [N,3] (z,y,x) or [N,4] (b,z,y,x)) -> (voxel_feats [M,C], voxel_coors [M,3|4])``: mean
+    (``average_points=True``) or max of the points of every voxel, voxels in ascending coordinate order (what mmcv's
+    ``unique`` gives; a 4-column input is mmcv's loop over the batch index). Rows with a negative coordinate are dropped.
+    Differentiable w.r.t. ``points``. Coordinates that come from ``Voxelization`` in dynamic mode carry their sorted
+    point-to-voxel map (``coors.voxel_map``), which is then reused instead of being rebuilt per call."""
+
+    def __init__(self, voxel_size, point_cloud_range, average_points):
+        super().__init__()
+        self.voxel_size = voxel_size
+        self.point_cloud_range = point_cloud_range
+        self.average_points = average_points
+        self._grid = None
+
+    def forward(self, points, coors):
+        from . import dynamic_voxel as DV
+        if self._grid is None:
+            self._grid = DV.grid_of(self.voxel_size, self.point_cloud_range)
+        vmap = DV.map_of(coors, self._grid)
+        feats = DV.scatter(points, vmap, DV.MEAN if self.average_points else DV.MAX)
+        voxel_coors = vmap.voxel_coors[:vmap.m]
+        return feats, (voxel_coors if coors.shape[1] == 4 else voxel_coors[:, 1:].contiguous())
+
+    def __repr__(self):
+        return (f'{self.__class__.__name__}(voxel_size={self.voxel_size}, point_cloud_range={self.point_cloud_range}, '
+                f'average_points={self.average_points})')

@@ -137,6 +137,53 @@ int gga_voxel_mean(const float* voxels, const int32_t* num_points, int64_t m, in
                    int ndim, int num_features, float* out, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* a1d. Dynamic voxelization: every point keeps its cell, no cap on points per  */
+/* voxel or voxels per frame. Replaces mmcv.ops.Voxelization(max_num_points=-1, */
+/* max_voxels=-1) (mmdet3d/models/detectors/dynamic_voxelnet.py:52-72: per-frame */
+/* loop + F.pad + cat) and mmcv.ops.DynamicScatter (voxel_encoders/             */
+/* voxel_encoder.py:64,155-174, pillar_encoder.py:231-234).                      */
+/* ------------------------------------------------------------------------- */
+/*
+ * points [total, ndim] f32, frames at offsets_host [batch + 1]; counts_dev: optional device i32 [batch] point counts of
+ * frames stored at capacity offsets (NULL = every row is a point).
+ * coors [total, 4] i32 (b, z, y, x): the cell of the hard voxelizer (same device function); (b, -1, -1, -1) for a point
+ * outside the grid, at or past its frame's count, or with a non-finite coordinate.
+ * keys [total] u32: ((b Z + z) Y + y) X + x, 0xFFFFFFFF for such a dropped point. batch x grid must stay below 2^32 - 1.
+ */
+int gga_dynamic_voxelize(const float* points, int ndim, const int64_t* offsets_host, const int32_t* counts_dev, int batch,
+                         const gga_voxel_params* prm, int32_t* coors, uint32_t* keys, void* stream);
+
+/*
+ * Sorted point-to-voxel map of n_points keys (or, keys == NULL, of coors [n_points, coor_cols] with 3 (z, y, x) or
+ * 4 (b, z, y, x) columns; a row with an entry outside the batch / grid is dropped). Capacity of every output is n_points:
+ * voxel_coors [n_points, 4] ascending (b, z, y, x) (rows >= M zero), voxel_start [n_points + 1] (segment v of `order` is
+ * [voxel_start[v], voxel_start[v + 1])), order [n_points] point indices grouped by voxel, ascending inside a voxel, dropped
+ * points last; point2voxel [n_points] (-1 = dropped); counts [2] = (voxels M, points kept). No host read-back.
+ */
+size_t gga_dynamic_voxel_map_workspace_bytes(int64_t n_points);
+int gga_dynamic_voxel_map(const uint32_t* keys, const int32_t* coors, int coor_cols, int64_t n_points, int batch, int grid_x,
+                          int grid_y, int grid_z, int32_t* voxel_coors, int32_t* voxel_start, int32_t* order,
+                          int32_t* point2voxel, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * DynamicScatter over such a map: out [out_rows, channels] = mean or max of feats [n_points, channels] over each voxel's
+ * points, channels in [1, 128]. Only voxels < min(counts[0], out_rows) are written. No float atomics: the order of the
+ * additions is fixed, two calls give the same bits. A voxel of more than gga_dynamic_scatter_chunk() points is reduced tile
+ * by tile and its partials are combined in tile order. Max also writes argmax [out_rows, channels] i32, the point holding
+ * the maximum (the lowest index on ties). Backward: grad_in [n_points, channels] = grad_out[voxel] / n (mean) or grad_out
+ * at the arg-max point (max); dropped points get zero; every element of grad_in is written.
+ */
+enum { GGA_DYNAMIC_MEAN = 0, GGA_DYNAMIC_MAX = 1 };
+int gga_dynamic_scatter_chunk(void);
+size_t gga_dynamic_scatter_workspace_bytes(int64_t n_points, int channels);
+int gga_dynamic_scatter_fwd(const float* feats, int channels, int64_t n_points, const int32_t* order,
+                            const int32_t* point2voxel, const int32_t* voxel_start, const int32_t* counts, int64_t out_rows,
+                            int mode, float* out, int32_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
+int gga_dynamic_scatter_bwd(const float* grad_out, int channels, int64_t n_points, const int32_t* point2voxel,
+                            const int32_t* voxel_start, const int32_t* argmax, int64_t out_rows, int mode, float* grad_in,
+                            void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* a2'. Fused PillarFeatureNet (one PFNLayer, legacy=True, mode='max'):       */
 /* decorate (cluster-mean / pillar-centre offsets) + Linear(10->64, no bias)  */
 /* + BatchNorm1d (batch statistics over all m*P rows, padding included) +     */
@@ -175,6 +222,30 @@ int gga_pfn_bwd(const float* voxels, const int32_t* num_points, const int32_t* c
                 const float* out, const uint8_t* argmax, const double* saved, const float* grad_out,
                 float* grad_weight, float* grad_gamma, float* grad_beta, void* workspace,
                 size_t workspace_bytes, void* stream);
+
+/*
+ * Fused DynamicPillarFeatureNet (pillar_encoder.py:162-323) in its shipped form: one layer, 4 point features -> 64
+ * channels, mode = 'max', cluster and voxel centre, no distance, affine BatchNorm1d with running statistics, fp32.
+ * Decoration (x, y, z, r, x-mx, y-my, z-mz, x-cx, y-cy, z-cz); the BatchNorm statistics run over the kept points
+ * (counts[1]) only - a dropped point takes part in nothing.
+ * points [n_points, 4] f32, coors [n_points, 4] i32 (b, z, y, x) per point, order / point2voxel / voxel_start / counts: the
+ * map of gga_dynamic_voxel_map. weight [64, 10], gamma / beta [64], running_mean / var [64] (updated in place when
+ * prm->training; gga_pfn_params as for gga_pfn_fwd). out [out_rows, 64] f32 and argmax [out_rows, 64] i32 (the point holding
+ * the maximum, the lowest index on ties): only voxels < min(counts[0], out_rows) are written. mean [out_rows, 4] f32: the
+ * voxels' point means (kept for the backward). saved [239] f64: moments, per-channel mean / invstd, row count.
+ * Backward w.r.t. weight, gamma, beta (training mode); the points need no gradient.
+ */
+size_t gga_dynamic_pfn_workspace_bytes(int64_t n_points);
+int gga_dynamic_pfn_fwd(const float* points, const int32_t* coors, int64_t n_points, const int32_t* order,
+                        const int32_t* point2voxel, const int32_t* voxel_start, const int32_t* counts, int64_t out_rows,
+                        const gga_pfn_params* prm, const float* weight, const float* gamma, const float* beta,
+                        float* running_mean, float* running_var, float* out, int32_t* argmax, float* mean, double* saved,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int gga_dynamic_pfn_bwd(const float* points, const int32_t* coors, int64_t n_points, const int32_t* counts, int64_t out_rows,
+                        const gga_pfn_params* prm, const float* weight, const float* gamma, const float* out,
+                        const int32_t* argmax, const float* mean, const double* saved, const float* grad_out,
+                        float* grad_weight, float* grad_gamma, float* grad_beta, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a3. PointPillars scatter (the kernel the "HBM GB/s on voxel scatter"       */

@@ -1725,6 +1725,63 @@ def golden_configs(ref):
     print('  reference configs:', ', '.join(f'{rel} ({len(keys)} sections)' for rel, keys in REFERENCE_CONFIG_SECTIONS.items()))
 
 
+def golden_dynamic_voxel(ref):
+    """The reference's dynamic voxel encoders (DynamicPillarFeatureNet, DynamicVFE max / avg, DynamicSimpleVFE) on about
+    1 500 in-range points of two frames; ``mmcv.ops.DynamicScatter`` is the restatement of tests/_dynamic_voxel_ref.py.
+    Arrays and parameter-name lists only."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _dynamic_voxel_ref as DR
+    ref['pe'].DynamicScatter = DR.DynamicScatterRef
+    ref['ve'].DynamicScatter = DR.DynamicScatterRef
+    rng_ = [0, -39.68, -3, 69.12, 39.68, 1]
+    # (the points of a 20 m x 20 m corner of the range: a dozen points per voxel, a few hundred voxels)
+    frames = [synthetic.make_frame(700 + i, n_points=760, pc_range=(0, -10.24, -3, 20.48, 10.24, 1))['points'].float() for i in range(2)]
+    grids = dict(dpfn=[2.56, 2.56, 4], vfe=[2.56, 2.56, 2.0], simple=[2.56, 2.56, 2.0])      # coarse cells: several points per voxel, a small archive
+    ok = (DR.point_coors(frames, grids['dpfn'], rng_)[:, 1:] >= 0).all(1) & (DR.point_coors(frames, grids['vfe'], rng_)[:, 1:] >= 0).all(1)
+    n0 = frames[0].shape[0]
+    frames = [frames[0][ok[:n0]], frames[1][ok[n0:]]]
+    pts = torch.cat(frames, 0)
+    out = {'points': pts.numpy(), 'frame_sizes': np.array([f.shape[0] for f in frames]), 'pc_range': np.array(rng_, np.float64)}
+    mods = dict(
+        dpfn=lambda: ref['pe'].DynamicPillarFeatureNet(in_channels=4, feat_channels=(64,), voxel_size=tuple(grids['dpfn']),
+                                                       point_cloud_range=tuple(rng_)),
+        vfe_max=lambda: ref['ve'].DynamicVFE(in_channels=4, feat_channels=[32, 64], with_cluster_center=True, with_voxel_center=True,
+                                             voxel_size=tuple(grids['vfe']), point_cloud_range=tuple(rng_), mode='max'),
+        vfe_avg=lambda: ref['ve'].DynamicVFE(in_channels=4, feat_channels=[32, 64], with_cluster_center=True, with_voxel_center=True,
+                                             voxel_size=tuple(grids['vfe']), point_cloud_range=tuple(rng_), mode='avg'),
+        simple=lambda: ref['ve'].DynamicSimpleVFE(voxel_size=tuple(grids['simple']), point_cloud_range=tuple(rng_)))
+    for seed, (name, make) in enumerate(mods.items()):
+        vs = grids[name.split('_')[0]]
+        coors = DR.point_coors(frames, vs, rng_)
+        assert (coors >= 0).all()
+        torch.manual_seed(40 + seed)
+        m = make()
+        with torch.no_grad():
+            for mod in m.modules():
+                if isinstance(mod, nn.BatchNorm1d):
+                    mod.weight.uniform_(0.5, 1.5)
+                    mod.bias.uniform_(-0.3, 0.3)
+        m.train()
+        out[f'{name}.voxel_size'] = np.array(vs, np.float64)
+        out[f'{name}.coors'] = coors.numpy()
+        out[f'{name}.state_keys'] = np.array(sorted(m.state_dict().keys()))
+        for k, v in m.state_dict().items():
+            out[f'{name}.init.{k}'] = v.detach().clone().numpy()
+        y, vc = m(pts.clone(), coors)
+        out[f'{name}.out'], out[f'{name}.voxel_coors'] = y.detach().numpy(), vc.numpy().astype(np.int32)
+        if name != 'simple':
+            gy = torch.from_numpy(np.random.default_rng(11 + seed).normal(size=tuple(y.shape)).astype(np.float32))
+            y.backward(gy)
+            out[f'{name}.grad_out'] = gy.numpy()
+            for k, p_ in m.named_parameters():
+                out[f'{name}.grad.{k}'] = p_.grad.numpy()
+            for k, v in m.state_dict().items():
+                if 'running' in k:
+                    out[f'{name}.after.{k}'] = v.numpy()
+        print(f'  dynamic {name}: {tuple(pts.shape)} -> {tuple(y.shape)}')
+    np.savez_compressed(os.path.join(OUT, 'dynamic_voxel.npz'), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -1748,6 +1805,7 @@ def main():
     golden_gt_database(ref)
     golden_pgd(ref)
     golden_configs(ref)
+    golden_dynamic_voxel(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
