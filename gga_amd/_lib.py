@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _lib = None
 
@@ -28,6 +28,22 @@ class PfnParams(C.Structure):
     _fields_ = [('voxel_size', C.c_float * 3), ('offsets', C.c_float * 3), ('eps', C.c_float),
                 ('momentum', C.c_float), ('training', C.c_int32), ('in_features', C.c_int32),
                 ('channels', C.c_int32)]
+
+
+MAX_TASKS = 8      # GGA_MAX_TASKS
+
+
+class Task(C.Structure):
+    """gga_task: one task's pointers for the task-batched loss kernels (a stage reads only its own fields)."""
+    _fields_ = [('logits', vp), ('target', vp), ('n_heat', i64), ('focal_out', vp), ('focal_grad', vp), ('grad_logits', vp),
+                ('reg', vp), ('height', vp), ('dim', vp), ('rot', vp), ('g_reg', vp), ('g_height', vp), ('g_dim', vp),
+                ('g_rot', vp), ('ind', vp), ('mask', vp), ('pred', vp), ('grad_pred', vp), ('anno_box', vp), ('lidar2img', vp),
+                ('bound_mask', vp), ('ibp_xy', vp), ('ibp_offsets', vp), ('ibp_slot', vp), ('n_ibp_obj', C.c_int32),
+                ('losses', vp), ('box_out', vp), ('term_grads', vp), ('grad_losses', vp)]
+
+
+class TaskTable(C.Structure):
+    _fields_ = [('n_tasks', C.c_int32), ('task', Task * MAX_TASKS)]
 
 
 class LossParams(C.Structure):
@@ -130,6 +146,14 @@ SIGNATURES = {
     'gga_focal_loss_workspace_bytes': (sz, [i64]),
     'gga_focal_loss_fwd': (i32, [vp, vp, i64, f32, f32, f32, vp, vp, sz, vp]),
     'gga_focal_loss_bwd': (i32, [vp, vp, i64, f32, f32, f32, vp, vp, vp, vp]),
+    'gga_focal_loss_workspace_bytes_tasks': (sz, [i64, i32]),
+    'gga_focal_loss_fwd_tasks': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp, sz, vp]),
+    'gga_focal_loss_bwd_tasks': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp]),
+    'gga_gather_pred_fwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
+    'gga_gather_pred_bwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
+    'gga_box_losses_workspace_bytes_tasks': (sz, [i32, i32, i32]),
+    'gga_box_losses_fwd_tasks': (i32, [C.POINTER(TaskTable), C.POINTER(LossParams), vp, sz, vp]),
+    'gga_box_losses_bwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, vp]),
     'gga_gather_pred_fwd': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     'gga_gather_pred_bwd': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'gga_box_losses_workspace_bytes': (sz, [i32, i32]),

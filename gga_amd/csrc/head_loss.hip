@@ -21,91 +21,152 @@
 #include "gga_common.h"
 
 // ----------------------------------------------------------------------------- gather
-__global__ __launch_bounds__(256) void gather_pred_kernel(const float* __restrict__ reg,
-                                                         const float* __restrict__ height,
-                                                         const float* __restrict__ dim,
-                                                         const float* __restrict__ rot,
-                                                         const int64_t* __restrict__ ind, int n, int K, int64_t hw,
-                                                         float* __restrict__ pred) {
+// The kernels of this file (box_slot_kernel excepted, see there) serve all tasks of a head in one launch: blockIdx.y picks the task's entry of the table
+// (include/gga_hip.h gga_task_table, passed by value), and the body for a task is what a launch for that task alone runs -
+// the tasks are independent and each is latency-bound on a few thousand threads, so T tasks in one grid take the time of one.
+__global__ __launch_bounds__(256) void gather_pred_kernel(gga_task_table tb, int n, int K, int64_t hw) {
+    const gga_task& T = tb.task[blockIdx.y];
     const int t = blockIdx.x * 256 + threadIdx.x;   // one thread per (slot, channel)
     if (t >= n * 8) return;
     const int s = t >> 3, c = t & 7;
     const int64_t b = s / K;
-    const int64_t i = ind[s];
+    const int64_t i = T.ind[s];
     const float* src;
     switch (c) {
-        case 0: case 1: src = reg + (b * 2 + c) * hw; break;
-        case 2: src = height + b * hw; break;
-        case 3: case 4: case 5: src = dim + (b * 3 + (c - 3)) * hw; break;
-        default: src = rot + (b * 2 + (c - 6)) * hw; break;
+        case 0: case 1: src = T.reg + (b * 2 + c) * hw; break;
+        case 2: src = T.height + b * hw; break;
+        case 3: case 4: case 5: src = T.dim + (b * 3 + (c - 3)) * hw; break;
+        default: src = T.rot + (b * 2 + (c - 6)) * hw; break;
     }
-    pred[t] = src[i];
+    T.pred[t] = src[i];
 }
 
-__global__ __launch_bounds__(256) void gather_pred_bwd_kernel(const float* __restrict__ grad_pred,
-                                                             const int64_t* __restrict__ ind,
-                                                             const uint8_t* __restrict__ mask, int n, int K,
-                                                             int64_t hw, float* __restrict__ g_reg,
-                                                             float* __restrict__ g_height, float* __restrict__ g_dim,
-                                                             float* __restrict__ g_rot) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n * 8) return;
-    const int s = t >> 3, c = t & 7;
-    if (!mask[s]) return;                 // zero weight in every loss term
-    const int64_t b = s / K;
-    const int64_t i = ind[s];
-    // Two objects of a frame may share a cell. Deterministic without atomics: the FIRST live slot of a cell (in slot order)
-    // writes the sum over all of that cell's live slots, added in slot order; the others write nothing. K <= 500 slots
-    // per frame and a few dozen live ones: the scans are a few thousand cached loads per step.
-    const int s0 = (int)b * K, k = s - s0;
-    for (int j = 0; j < k; ++j)
-        if (mask[s0 + j] && ind[s0 + j] == i) return;
-    float g = grad_pred[t];
-    for (int j = k + 1; j < K; ++j)
-        if (mask[s0 + j] && ind[s0 + j] == i) g += grad_pred[(int64_t)(s0 + j) * 8 + c];
-    float* dst;
-    switch (c) {
-        case 0: case 1: dst = g_reg + (b * 2 + c) * hw; break;
-        case 2: dst = g_height + b * hw; break;
-        case 3: case 4: case 5: dst = g_dim + (b * 3 + (c - 3)) * hw; break;
-        default: dst = g_rot + (b * 2 + (c - 6)) * hw; break;
+// slots of one frame the workgroup of gather_pred_bwd_kernel keeps in LDS (8 B ind + 1 B mask each: 4.5 KB)
+#define GATHER_LDS_K 512
+
+// One workgroup per (task, frame). Two objects of a frame may share a cell. Deterministic without atomics: the FIRST live
+// slot of a cell (in slot order) writes the sum over all of that cell's live slots, added in slot order; the others write
+// nothing. Every live thread scans the frame's slots for that: the frame's ind and mask are copied to LDS once and the scans
+// read LDS (they were two dependent global loads per slot and thread), and they stop behind the frame's last live slot -
+// the slots after it are dead and add nothing.
+__global__ __launch_bounds__(256) void gather_pred_bwd_kernel(gga_task_table tb, int K, int64_t hw) {
+    const gga_task& T = tb.task[blockIdx.y];
+    __shared__ int64_t s_ind[GATHER_LDS_K];
+    __shared__ uint8_t s_mask[GATHER_LDS_K];
+    __shared__ int s_end;
+    const int64_t b = blockIdx.x;
+    const int s0 = (int)b * K;
+    if (threadIdx.x == 0) s_end = 0;
+    __syncthreads();
+    int last = 0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const uint8_t m = T.mask[s0 + k];
+        s_mask[k] = m;
+        s_ind[k] = T.ind[s0 + k];
+        if (m) last = k + 1;
     }
-    dst[i] = g;
+    if (last) atomicMax(&s_end, last);
+    __syncthreads();
+    const int end = s_end;                   // one past the frame's last live slot
+    const float* __restrict__ gp = T.grad_pred + (int64_t)s0 * 8;
+    for (int t = threadIdx.x; t < end * 8; t += 256) {
+        const int k = t >> 3, c = t & 7;
+        if (!s_mask[k]) continue;             // zero weight in every loss term
+        const int64_t i = s_ind[k];
+        bool first = true;
+        for (int j = 0; j < k; ++j)
+            if (s_mask[j] && s_ind[j] == i) { first = false; break; }
+        if (!first) continue;
+        float g = gp[t];
+        for (int j = k + 1; j < end; ++j)
+            if (s_mask[j] && s_ind[j] == i) g += gp[j * 8 + c];
+        float* dst;
+        switch (c) {
+            case 0: case 1: dst = T.g_reg + (b * 2 + c) * hw; break;
+            case 2: dst = T.g_height + b * hw; break;
+            case 3: case 4: case 5: dst = T.g_dim + (b * 3 + (c - 3)) * hw; break;
+            default: dst = T.g_rot + (b * 2 + (c - 6)) * hw; break;
+        }
+        dst[i] = g;
+    }
 }
 
-extern "C" int gga_gather_pred_fwd(const float* reg, const float* height, const float* dim, const float* rot,
-                                   const int64_t* ind, int B, int K, int H, int W, float* pred, void* stream) {
-    GGA_REQUIRE(reg && height && dim && rot && ind && pred, "gga_gather_pred_fwd: null pointer argument");
-    GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "gga_gather_pred_fwd: bad sizes");
+static int check_table(const char* fn, const gga_task_table* tb) {
+    GGA_REQUIRE(tb, "%s: null task table", fn);
+    GGA_REQUIRE(tb->n_tasks >= 1 && tb->n_tasks <= GGA_MAX_TASKS, "%s: n_tasks %d not in 1..%d", fn, tb->n_tasks, GGA_MAX_TASKS);
+    return GGA_OK;
+}
+
+extern "C" int gga_gather_pred_fwd_tasks(const gga_task_table* tb, int B, int K, int H, int W, void* stream) {
+    const char* fn = "gga_gather_pred_fwd_tasks";
+    if (int rc = check_table(fn, tb)) return rc;
+    GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "%s: bad sizes", fn);
+    for (int t = 0; t < tb->n_tasks; ++t) {
+        const gga_task& T = tb->task[t];
+        GGA_REQUIRE(T.reg && T.height && T.dim && T.rot && T.ind && T.pred, "%s: null pointer argument (task %d)", fn, t);
+    }
     const int n = B * K;
-    hipLaunchKernelGGL(gather_pred_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream, reg, height,
-                       dim, rot, ind, n, K, (int64_t)H * W, pred);
+    hipLaunchKernelGGL(gather_pred_kernel, dim3((n * 8 + 255) / 256, tb->n_tasks), dim3(256), 0, (hipStream_t)stream, *tb, n, K,
+                       (int64_t)H * W);
     GGA_CHECK_LAUNCH("gather_pred_kernel");
     return GGA_OK;
 }
 
-extern "C" int gga_gather_pred_bwd(const float* grad_pred, const int64_t* ind, const uint8_t* mask, int B, int K,
-                                   int H, int W, float* g_reg, float* g_height, float* g_dim, float* g_rot,
-                                   void* stream_) {
+extern "C" int gga_gather_pred_bwd_tasks(const gga_task_table* tb, int B, int K, int H, int W, void* stream_) {
+    const char* fn = "gga_gather_pred_bwd_tasks";
     hipStream_t stream = (hipStream_t)stream_;
-    GGA_REQUIRE(grad_pred && ind && mask && g_reg && g_height && g_dim && g_rot,
-                "gga_gather_pred_bwd: null pointer argument");
-    GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "gga_gather_pred_bwd: bad sizes");
+    if (int rc = check_table(fn, tb)) return rc;
+    GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "%s: bad sizes", fn);
+    GGA_REQUIRE(K <= GATHER_LDS_K, "%s: K = %d slots per frame, the kernel holds at most %d", fn, K, GATHER_LDS_K);
     const size_t hw = (size_t)H * W * sizeof(float);
     const size_t fl = (size_t)H * W * B;
-    if (g_height == g_reg + 2 * fl && g_dim == g_height + fl && g_rot == g_dim + 3 * fl) {      // four views of one allocation: one memset
-        GGA_CHECK_HIP(hipMemsetAsync(g_reg, 0, hw * B * 8, stream), "gather bwd memset");
-    } else {
-        GGA_CHECK_HIP(hipMemsetAsync(g_reg, 0, hw * B * 2, stream), "gather bwd memset");
-        GGA_CHECK_HIP(hipMemsetAsync(g_height, 0, hw * B, stream), "gather bwd memset");
-        GGA_CHECK_HIP(hipMemsetAsync(g_dim, 0, hw * B * 3, stream), "gather bwd memset");
-        GGA_CHECK_HIP(hipMemsetAsync(g_rot, 0, hw * B * 2, stream), "gather bwd memset");
+    bool one = true;                         // every task's four maps are views of ONE allocation, task behind task
+    for (int t = 0; t < tb->n_tasks; ++t) {
+        const gga_task& T = tb->task[t];
+        GGA_REQUIRE(T.grad_pred && T.ind && T.mask && T.g_reg && T.g_height && T.g_dim && T.g_rot,
+                    "%s: null pointer argument (task %d)", fn, t);
+        one = one && T.g_reg == tb->task[0].g_reg + 8 * fl * t && T.g_height == T.g_reg + 2 * fl && T.g_dim == T.g_height + fl &&
+              T.g_rot == T.g_dim + 3 * fl;
     }
-    const int n = B * K;
-    hipLaunchKernelGGL(gather_pred_bwd_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, stream, grad_pred, ind, mask,
-                       n, K, (int64_t)H * W, g_reg, g_height, g_dim, g_rot);
+    if (one) {
+        GGA_CHECK_HIP(hipMemsetAsync(tb->task[0].g_reg, 0, hw * B * 8 * tb->n_tasks, stream), "gather bwd memset");
+    } else {
+        for (int t = 0; t < tb->n_tasks; ++t) {
+            const gga_task& T = tb->task[t];
+            if (T.g_height == T.g_reg + 2 * fl && T.g_dim == T.g_height + fl && T.g_rot == T.g_dim + 3 * fl) {      // four views of one allocation
+                GGA_CHECK_HIP(hipMemsetAsync(T.g_reg, 0, hw * B * 8, stream), "gather bwd memset");
+            } else {
+                GGA_CHECK_HIP(hipMemsetAsync(T.g_reg, 0, hw * B * 2, stream), "gather bwd memset");
+                GGA_CHECK_HIP(hipMemsetAsync(T.g_height, 0, hw * B, stream), "gather bwd memset");
+                GGA_CHECK_HIP(hipMemsetAsync(T.g_dim, 0, hw * B * 3, stream), "gather bwd memset");
+                GGA_CHECK_HIP(hipMemsetAsync(T.g_rot, 0, hw * B * 2, stream), "gather bwd memset");
+            }
+        }
+    }
+    hipLaunchKernelGGL(gather_pred_bwd_kernel, dim3(B, tb->n_tasks), dim3(256), 0, stream, *tb, K, (int64_t)H * W);
     GGA_CHECK_LAUNCH("gather_pred_bwd_kernel");
     return GGA_OK;
+}
+
+// The per-task entry points: the same kernels with a table of one entry.
+extern "C" int gga_gather_pred_fwd(const float* reg, const float* height, const float* dim, const float* rot,
+                                   const int64_t* ind, int B, int K, int H, int W, float* pred, void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.reg = reg; T.height = height; T.dim = dim; T.rot = rot; T.ind = ind; T.pred = pred;
+    return gga_gather_pred_fwd_tasks(&tb, B, K, H, W, stream);
+}
+
+extern "C" int gga_gather_pred_bwd(const float* grad_pred, const int64_t* ind, const uint8_t* mask, int B, int K,
+                                   int H, int W, float* g_reg, float* g_height, float* g_dim, float* g_rot,
+                                   void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.grad_pred = (float*)grad_pred; T.ind = ind; T.mask = mask;
+    T.g_reg = g_reg; T.g_height = g_height; T.g_dim = g_dim; T.g_rot = g_rot;
+    return gga_gather_pred_bwd_tasks(&tb, B, K, H, W, stream);
 }
 
 // ----------------------------------------------------------------------------- losses
@@ -196,6 +257,10 @@ __device__ __forceinline__ float sgn(float x) { return (x > 0.0f) - (x < 0.0f); 
 // box_out row layout: rot, l, w, umin, vmin, umax, vmax, X, Y, p2c_min, p2c_x, p2c_y
 #define BOX_OUT_W 12
 
+// One launch per task, with the task's pointers as __restrict__ kernel parameters - the one kernel of this file that does not
+// take the task table: handed its pointers any other way (table entry, inlined body with __restrict__ parameters, a called
+// function; all three built and compared) the compiler contracts other products of the analytic gradient into fmas and
+// box_out / grad_pred move by an ulp (EXPERIMENTS.md 6m). The results stay bit for bit what they were, so it stays as it was.
 __global__ __launch_bounds__(256) void box_slot_kernel(const float* __restrict__ pred,
                                                       const int64_t* __restrict__ ind,
                                                       const uint8_t* __restrict__ mask,
@@ -274,13 +339,12 @@ __global__ __launch_bounds__(256) void box_slot_kernel(const float* __restrict__
 }
 
 // One wavefront per object with in-box points (head:184-239).
-__global__ __launch_bounds__(256) void pal_kernel(const float* __restrict__ pred, const int64_t* __restrict__ ind,
-                                                 const uint8_t* __restrict__ mask, const float* __restrict__ anno,
-                                                 const float2* __restrict__ ibp_xy,
-                                                 const int32_t* __restrict__ ibp_offsets,
-                                                 const int32_t* __restrict__ ibp_slot, int n_obj, gga_loss_params prm,
-                                                 float* __restrict__ box_out, float* __restrict__ grad_pred,
-                                                 float* __restrict__ part) {
+__device__ __forceinline__ void pal_body(const float* __restrict__ pred, const int64_t* __restrict__ ind,
+                                         const uint8_t* __restrict__ mask, const float* __restrict__ anno,
+                                         const float2* __restrict__ ibp_xy, const int32_t* __restrict__ ibp_offsets,
+                                         const int32_t* __restrict__ ibp_slot, int n_obj, const gga_loss_params& prm,
+                                         float* __restrict__ box_out, float* __restrict__ grad_pred,
+                                         float* __restrict__ part) {
     const int n = prm.B * prm.K;
     const float avg = block_avg_factor(mask, n);
     const int lane = threadIdx.x & 63;
@@ -362,11 +426,21 @@ __global__ __launch_bounds__(256) void pal_kernel(const float* __restrict__ pred
     }
 }
 
-__global__ __launch_bounds__(1024) void box_reduce_kernel(const float* __restrict__ part,
-                                                         const uint8_t* __restrict__ mask, gga_loss_params prm,
-                                                         float* __restrict__ losses) {
+__global__ __launch_bounds__(256) void pal_kernel(gga_task_table tb, gga_loss_params prm, float* __restrict__ part_all) {
+    const gga_task& T = tb.task[blockIdx.y];
+    if ((int)blockIdx.x * 4 >= T.n_ibp_obj) return;      // the grid is sized for the task with the most objects
+    pal_body(T.pred, T.ind, T.mask, T.anno_box, (const float2*)T.ibp_xy, T.ibp_offsets, T.ibp_slot, T.n_ibp_obj, prm, T.box_out,
+             T.term_grads, part_all + (int64_t)blockIdx.y * GGA_L_NUM * prm.B * prm.K);
+}
+
+__global__ __launch_bounds__(1024) void box_reduce_kernel(gga_task_table tb, gga_loss_params prm,
+                                                         const float* __restrict__ part_all) {
     // one pass: every thread carries the five partial sums, wave shuffle, then a fixed-order fold
+    const gga_task& T = tb.task[blockIdx.x];
+    const uint8_t* __restrict__ mask = T.mask;
+    float* __restrict__ losses = T.losses;
     const int n = prm.B * prm.K;
+    const float* __restrict__ part = part_all + (int64_t)blockIdx.x * GGA_L_NUM * n;
     const float avg = block_avg_factor(mask, n);
     __shared__ double sh[GGA_L_NUM][16];
     double acc[GGA_L_NUM];
@@ -391,9 +465,11 @@ __global__ __launch_bounds__(1024) void box_reduce_kernel(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void box_bwd_kernel(const float* __restrict__ grad_pred,
-                                                     const float* __restrict__ grad_losses, int n8,
-                                                     float* __restrict__ out) {
+__global__ __launch_bounds__(256) void box_bwd_kernel(gga_task_table tb, int n8) {
+    const gga_task& T = tb.task[blockIdx.y];
+    const float* __restrict__ grad_pred = T.term_grads;
+    const float* __restrict__ grad_losses = T.grad_losses;
+    float* __restrict__ out = T.grad_pred;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n8) return;
     float acc = 0.0f;
@@ -405,55 +481,101 @@ __global__ __launch_bounds__(256) void box_bwd_kernel(const float* __restrict__ 
     out[t] = acc;
 }
 
-extern "C" size_t gga_box_losses_workspace_bytes(int B, int K) {
-    return (size_t)GGA_L_NUM * B * K * sizeof(float);
+extern "C" size_t gga_box_losses_workspace_bytes_tasks(int B, int K, int n_tasks) {
+    return (size_t)GGA_L_NUM * B * K * sizeof(float) * n_tasks;
 }
 
-extern "C" int gga_box_losses_fwd(const float* pred, const int64_t* ind, const uint8_t* mask, const float* anno_box,
-                                  const float* lidar2img, const uint8_t* bound_mask, const float* ibp_xy,
-                                  const int32_t* ibp_offsets, const int32_t* ibp_slot, int n_ibp_obj,
-                                  const gga_loss_params* prm, float* losses, float* box_out, float* grad_pred,
-                                  void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" size_t gga_box_losses_workspace_bytes(int B, int K) { return gga_box_losses_workspace_bytes_tasks(B, K, 1); }
+
+extern "C" int gga_box_losses_fwd_tasks(const gga_task_table* tb, const gga_loss_params* prm, void* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_box_losses_fwd_tasks";
     hipStream_t stream = (hipStream_t)stream_;
-    GGA_REQUIRE(pred && ind && mask && anno_box && lidar2img && bound_mask && prm && losses && box_out && grad_pred &&
-                    workspace,
-                "gga_box_losses_fwd: null pointer argument");
-    GGA_REQUIRE(prm->B >= 1 && prm->K >= 1 && prm->fm_w >= 1, "gga_box_losses_fwd: bad B/K/fm_w");
-    GGA_REQUIRE(n_ibp_obj == 0 || (ibp_xy && ibp_offsets && ibp_slot), "gga_box_losses_fwd: null in-box-point arrays");
-    const int n = prm->B * prm->K;
-    if (workspace_bytes < gga_box_losses_workspace_bytes(prm->B, prm->K)) {
-        gga_set_error("gga_box_losses_fwd: workspace %zu B < required %zu B", workspace_bytes,
-                      gga_box_losses_workspace_bytes(prm->B, prm->K));
+    if (int rc = check_table(fn, tb)) return rc;
+    GGA_REQUIRE(prm && workspace, "%s: null pointer argument", fn);
+    GGA_REQUIRE(prm->B >= 1 && prm->K >= 1 && prm->fm_w >= 1, "%s: bad B/K/fm_w", fn);
+    const int n = prm->B * prm->K, nt = tb->n_tasks;
+    const size_t per_task = (size_t)GGA_L_NUM * n * 8 + (size_t)n * BOX_OUT_W;      // floats of term_grads + box_out
+    int max_obj = 0;
+    bool one = true;                         // every task's term_grads and box_out are views of ONE allocation, task behind task
+    for (int t = 0; t < nt; ++t) {
+        const gga_task& T = tb->task[t];
+        GGA_REQUIRE(T.pred && T.ind && T.mask && T.anno_box && T.lidar2img && T.bound_mask && T.losses && T.box_out && T.term_grads,
+                    "%s: null pointer argument (task %d)", fn, t);
+        GGA_REQUIRE(T.n_ibp_obj >= 0 && (T.n_ibp_obj == 0 || (T.ibp_xy && T.ibp_offsets && T.ibp_slot)),
+                    "%s: null in-box-point arrays (task %d)", fn, t);
+        max_obj = T.n_ibp_obj > max_obj ? T.n_ibp_obj : max_obj;
+        one = one && T.term_grads == tb->task[0].term_grads + per_task * t && T.box_out == T.term_grads + (size_t)GGA_L_NUM * n * 8;
+    }
+    if (workspace_bytes < gga_box_losses_workspace_bytes_tasks(prm->B, prm->K, nt)) {
+        gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes,
+                      gga_box_losses_workspace_bytes_tasks(prm->B, prm->K, nt));
         return GGA_ERR_WORKSPACE;
     }
-    float* part = (float*)workspace;
-    GGA_CHECK_HIP(hipMemsetAsync(part, 0, (size_t)GGA_L_NUM * n * sizeof(float), stream), "box losses memset");
-    if (box_out == grad_pred + (size_t)GGA_L_NUM * n * 8) {         // two views of one allocation: one memset
-        GGA_CHECK_HIP(hipMemsetAsync(grad_pred, 0, ((size_t)GGA_L_NUM * n * 8 + (size_t)n * BOX_OUT_W) * sizeof(float), stream), "box losses memset");
+    float* part = (float*)workspace;             // [task][GGA_L_NUM][n]
+    GGA_CHECK_HIP(hipMemsetAsync(part, 0, (size_t)GGA_L_NUM * n * sizeof(float) * nt, stream), "box losses memset");
+    if (one) {
+        GGA_CHECK_HIP(hipMemsetAsync(tb->task[0].term_grads, 0, per_task * nt * sizeof(float), stream), "box losses memset");
     } else {
-        GGA_CHECK_HIP(hipMemsetAsync(grad_pred, 0, (size_t)GGA_L_NUM * n * 8 * sizeof(float), stream), "box losses memset");
-        GGA_CHECK_HIP(hipMemsetAsync(box_out, 0, (size_t)n * BOX_OUT_W * sizeof(float), stream), "box losses memset");
+        for (int t = 0; t < nt; ++t) {
+            const gga_task& T = tb->task[t];
+            if (T.box_out == T.term_grads + (size_t)GGA_L_NUM * n * 8) {         // two views of one allocation
+                GGA_CHECK_HIP(hipMemsetAsync(T.term_grads, 0, per_task * sizeof(float), stream), "box losses memset");
+            } else {
+                GGA_CHECK_HIP(hipMemsetAsync(T.term_grads, 0, (size_t)GGA_L_NUM * n * 8 * sizeof(float), stream), "box losses memset");
+                GGA_CHECK_HIP(hipMemsetAsync(T.box_out, 0, (size_t)n * BOX_OUT_W * sizeof(float), stream), "box losses memset");
+            }
+        }
     }
-    hipLaunchKernelGGL(box_slot_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, pred, ind, mask, anno_box,
-                       lidar2img, bound_mask, *prm, box_out, grad_pred, part);
-    GGA_CHECK_LAUNCH("box_slot_kernel");
-    if (n_ibp_obj > 0) {
-        hipLaunchKernelGGL(pal_kernel, dim3((n_ibp_obj + 3) / 4), dim3(256), 0, stream, pred, ind, mask, anno_box,
-                           (const float2*)ibp_xy, ibp_offsets, ibp_slot, n_ibp_obj, *prm, box_out, grad_pred, part);
+    for (int t = 0; t < nt; ++t) {
+        const gga_task& T = tb->task[t];
+        hipLaunchKernelGGL(box_slot_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, T.pred, T.ind, T.mask, T.anno_box,
+                           T.lidar2img, T.bound_mask, *prm, T.box_out, T.term_grads, part + (size_t)t * GGA_L_NUM * n);
+        GGA_CHECK_LAUNCH("box_slot_kernel");
+    }
+    if (max_obj > 0) {
+        hipLaunchKernelGGL(pal_kernel, dim3((max_obj + 3) / 4, nt), dim3(256), 0, stream, *tb, *prm, part);
         GGA_CHECK_LAUNCH("pal_kernel");
     }
-    hipLaunchKernelGGL(box_reduce_kernel, dim3(1), dim3(1024), 0, stream, part, mask, *prm, losses);
+    hipLaunchKernelGGL(box_reduce_kernel, dim3(nt), dim3(1024), 0, stream, *tb, *prm, (const float*)part);
     GGA_CHECK_LAUNCH("box_reduce_kernel");
     return GGA_OK;
 }
 
-extern "C" int gga_box_losses_bwd(const float* grad_pred, const float* grad_losses, int B, int K,
-                                  float* grad_pred_out, void* stream) {
-    GGA_REQUIRE(grad_pred && grad_losses && grad_pred_out && B >= 1 && K >= 1,
-                "gga_box_losses_bwd: null pointer or bad sizes");
+extern "C" int gga_box_losses_bwd_tasks(const gga_task_table* tb, int B, int K, void* stream) {
+    const char* fn = "gga_box_losses_bwd_tasks";
+    if (int rc = check_table(fn, tb)) return rc;
+    GGA_REQUIRE(B >= 1 && K >= 1, "%s: bad sizes", fn);
+    for (int t = 0; t < tb->n_tasks; ++t) {
+        const gga_task& T = tb->task[t];
+        GGA_REQUIRE(T.term_grads && T.grad_losses && T.grad_pred, "%s: null pointer argument (task %d)", fn, t);
+    }
     const int n8 = B * K * 8;
-    hipLaunchKernelGGL(box_bwd_kernel, dim3((n8 + 255) / 256), dim3(256), 0, (hipStream_t)stream, grad_pred,
-                       grad_losses, n8, grad_pred_out);
+    hipLaunchKernelGGL(box_bwd_kernel, dim3((n8 + 255) / 256, tb->n_tasks), dim3(256), 0, (hipStream_t)stream, *tb, n8);
     GGA_CHECK_LAUNCH("box_bwd_kernel");
     return GGA_OK;
+}
+
+// The per-task entry points: the same kernels with a table of one entry.
+extern "C" int gga_box_losses_fwd(const float* pred, const int64_t* ind, const uint8_t* mask, const float* anno_box,
+                                  const float* lidar2img, const uint8_t* bound_mask, const float* ibp_xy,
+                                  const int32_t* ibp_offsets, const int32_t* ibp_slot, int n_ibp_obj,
+                                  const gga_loss_params* prm, float* losses, float* box_out, float* grad_pred,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.pred = (float*)pred; T.ind = ind; T.mask = mask; T.anno_box = anno_box; T.lidar2img = lidar2img; T.bound_mask = bound_mask;
+    T.ibp_xy = ibp_xy; T.ibp_offsets = ibp_offsets; T.ibp_slot = ibp_slot; T.n_ibp_obj = n_ibp_obj;
+    T.losses = losses; T.box_out = box_out; T.term_grads = grad_pred;
+    return gga_box_losses_fwd_tasks(&tb, prm, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gga_box_losses_bwd(const float* grad_pred, const float* grad_losses, int B, int K,
+                                  float* grad_pred_out, void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.term_grads = (float*)grad_pred; T.grad_losses = grad_losses; T.grad_pred = grad_pred_out;
+    return gga_box_losses_bwd_tasks(&tb, B, K, stream);
 }

@@ -88,13 +88,30 @@ __device__ __forceinline__ FocalTerms focal_terms(float x, float t, float alpha,
     return r;
 }
 
-__global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict__ logits,
-                                                       const float* __restrict__ target, int64_t n, float alpha,
-                                                       float gamma, float* __restrict__ partials) {
+// Workgroups of a pass over n elements: the forward's partial sums depend on it (a grid-stride walk), so a task's count is a
+// function of its own n alone, whichever other tasks share the launch.
+__host__ __device__ static inline int focal_blocks(int64_t n, int cap) {
+    int64_t b = (n / 4 + 255) / 256;
+    if (b < 1) b = 1;
+    return (int)(b > cap ? cap : b);
+}
+#define FOCAL_BWD_MAX_BLOCKS 4096
+
+// The three kernels serve all tasks of a head in one launch: blockIdx.y picks the task's entry of the table (gga_task_table),
+// the grid is as wide as the largest task needs and a task's surplus workgroups leave at once. partials: [task][slice].
+__global__ __launch_bounds__(256) void focal_fwd_kernel(gga_task_table tb, float alpha, float gamma,
+                                                       float* __restrict__ partials_all, int slice) {
+    const gga_task& T = tb.task[blockIdx.y];
+    const int64_t n = T.n_heat;
+    const int nb = focal_blocks(n, FOCAL_MAX_BLOCKS);
+    if ((int)blockIdx.x >= nb) return;
+    const float* __restrict__ logits = T.logits;
+    const float* __restrict__ target = T.target;
+    float* __restrict__ partials = partials_all + (int64_t)blockIdx.y * slice;
     float acc = 0.0f;
     int npos = 0;
     const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t stride = (int64_t)nb * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
         const float4 x = reinterpret_cast<const float4*>(logits)[i];
         const float4 t = reinterpret_cast<const float4*>(target)[i];
@@ -121,8 +138,12 @@ __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void focal_final_kernel(const float* __restrict__ partials, int nblocks,
-                                                         float scale, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void focal_final_kernel(gga_task_table tb, const float* __restrict__ partials_all, int slice,
+                                                         float scale) {
+    const gga_task& T = tb.task[blockIdx.x];
+    const float* __restrict__ partials = partials_all + (int64_t)blockIdx.x * slice;
+    const int nblocks = focal_blocks(T.n_heat, FOCAL_MAX_BLOCKS);
+    float* __restrict__ out = T.focal_out;
     double acc = 0.0, cnt = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) { acc += partials[2 * i]; cnt += partials[2 * i + 1]; }
     acc = wave_sum(acc);
@@ -139,16 +160,20 @@ __global__ __launch_bounds__(256) void focal_final_kernel(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict__ logits,
-                                                       const float* __restrict__ target, int64_t n, float alpha,
-                                                       float gamma, float scale, const float* __restrict__ fwd_out,
-                                                       const float* __restrict__ grad_out,
-                                                       float* __restrict__ grad_logits) {
-    const float npos = fwd_out[1];
+__global__ __launch_bounds__(256) void focal_bwd_kernel(gga_task_table tb, float alpha, float gamma, float scale) {
+    const gga_task& T = tb.task[blockIdx.y];
+    const int64_t n = T.n_heat;
+    const int nb = focal_blocks(n, FOCAL_BWD_MAX_BLOCKS);
+    if ((int)blockIdx.x >= nb) return;
+    const float* __restrict__ logits = T.logits;
+    const float* __restrict__ target = T.target;
+    const float* __restrict__ grad_out = T.focal_grad;
+    float* __restrict__ grad_logits = T.grad_logits;
+    const float npos = T.focal_out[1];
     const float avg = (float)((double)(npos > 1.0f ? npos : 1.0f) + (double)FLT_EPSILON);
     const float k = (*grad_out) * scale / avg;
     const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t stride = (int64_t)nb * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
         const float4 x = reinterpret_cast<const float4*>(logits)[i];
         const float4 t = reinterpret_cast<const float4*>(target)[i];
@@ -164,46 +189,74 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
             grad_logits[i] = k * focal_terms<true>(logits[i], target[i], alpha, gamma).dlogit;
 }
 
-static int focal_blocks(int64_t n) {
-    int64_t b = (n / 4 + 255) / 256;
-    if (b < 1) b = 1;
-    return (int)(b > FOCAL_MAX_BLOCKS ? FOCAL_MAX_BLOCKS : b);
+static int focal_check_table(const char* fn, const gga_task_table* tb, bool bwd, int64_t* n_max) {
+    GGA_REQUIRE(tb, "%s: null task table", fn);
+    GGA_REQUIRE(tb->n_tasks >= 1 && tb->n_tasks <= GGA_MAX_TASKS, "%s: n_tasks %d not in 1..%d", fn, tb->n_tasks, GGA_MAX_TASKS);
+    *n_max = 0;
+    for (int t = 0; t < tb->n_tasks; ++t) {
+        const gga_task& T = tb->task[t];
+        GGA_REQUIRE(T.logits && T.target && T.focal_out && T.n_heat > 0 && (!bwd || (T.focal_grad && T.grad_logits)),
+                    "%s: null pointer or n <= 0 (task %d)", fn, t);
+        GGA_REQUIRE(((uintptr_t)T.logits & 15) == 0 && ((uintptr_t)T.target & 15) == 0 && (!bwd || ((uintptr_t)T.grad_logits & 15) == 0),
+                    "%s: logits/target/grad_logits must be 16-byte aligned (task %d)", fn, t);
+        *n_max = T.n_heat > *n_max ? T.n_heat : *n_max;
+    }
+    return GGA_OK;
 }
 
-extern "C" size_t gga_focal_loss_workspace_bytes(int64_t n) { return (size_t)focal_blocks(n) * 2 * sizeof(float); }
+extern "C" size_t gga_focal_loss_workspace_bytes_tasks(int64_t n_max, int n_tasks) {
+    return (size_t)focal_blocks(n_max, FOCAL_MAX_BLOCKS) * 2 * sizeof(float) * n_tasks;
+}
 
-extern "C" int gga_focal_loss_fwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
-                                  float scale, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" size_t gga_focal_loss_workspace_bytes(int64_t n) { return gga_focal_loss_workspace_bytes_tasks(n, 1); }
+
+extern "C" int gga_focal_loss_fwd_tasks(const gga_task_table* tb, float alpha, float gamma, float scale, void* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_focal_loss_fwd_tasks";
     hipStream_t stream = (hipStream_t)stream_;
-    GGA_REQUIRE(logits && target && out && workspace && n > 0, "gga_focal_loss_fwd: null pointer or n <= 0");
-    GGA_REQUIRE(((uintptr_t)logits & 15) == 0 && ((uintptr_t)target & 15) == 0,
-                "gga_focal_loss_fwd: logits/target must be 16-byte aligned");
-    if (workspace_bytes < gga_focal_loss_workspace_bytes(n)) {
-        gga_set_error("gga_focal_loss_fwd: workspace %zu B < required %zu B", workspace_bytes,
-                      gga_focal_loss_workspace_bytes(n));
+    int64_t n_max;
+    if (int rc = focal_check_table(fn, tb, false, &n_max)) return rc;
+    GGA_REQUIRE(workspace, "%s: null workspace", fn);
+    if (workspace_bytes < gga_focal_loss_workspace_bytes_tasks(n_max, tb->n_tasks)) {
+        gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes,
+                      gga_focal_loss_workspace_bytes_tasks(n_max, tb->n_tasks));
         return GGA_ERR_WORKSPACE;
     }
-    const int nb = focal_blocks(n);
-    hipLaunchKernelGGL(focal_fwd_kernel, dim3(nb), dim3(256), 0, stream, logits, target, n, alpha, gamma,
-                       (float*)workspace);
+    const int nb = focal_blocks(n_max, FOCAL_MAX_BLOCKS), slice = 2 * nb;
+    hipLaunchKernelGGL(focal_fwd_kernel, dim3(nb, tb->n_tasks), dim3(256), 0, stream, *tb, alpha, gamma, (float*)workspace, slice);
     GGA_CHECK_LAUNCH("focal_fwd_kernel");
-    hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, stream, (const float*)workspace, nb, scale, out);
+    hipLaunchKernelGGL(focal_final_kernel, dim3(tb->n_tasks), dim3(256), 0, stream, *tb, (const float*)workspace, slice, scale);
     GGA_CHECK_LAUNCH("focal_final_kernel");
     return GGA_OK;
 }
 
-extern "C" int gga_focal_loss_bwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
-                                  float scale, const float* fwd_out, const float* grad_out, float* grad_logits,
-                                  void* stream_) {
-    GGA_REQUIRE(logits && target && fwd_out && grad_out && grad_logits && n > 0,
-                "gga_focal_loss_bwd: null pointer or n <= 0");
-    GGA_REQUIRE(((uintptr_t)logits & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)grad_logits & 15) == 0,
-                "gga_focal_loss_bwd: buffers must be 16-byte aligned");
-    int64_t b = (n / 4 + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(focal_bwd_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream_, logits, target, n,
-                       alpha, gamma, scale, fwd_out, grad_out, grad_logits);
+extern "C" int gga_focal_loss_bwd_tasks(const gga_task_table* tb, float alpha, float gamma, float scale, void* stream_) {
+    const char* fn = "gga_focal_loss_bwd_tasks";
+    int64_t n_max;
+    if (int rc = focal_check_table(fn, tb, true, &n_max)) return rc;
+    hipLaunchKernelGGL(focal_bwd_kernel, dim3(focal_blocks(n_max, FOCAL_BWD_MAX_BLOCKS), tb->n_tasks), dim3(256), 0,
+                       (hipStream_t)stream_, *tb, alpha, gamma, scale);
     GGA_CHECK_LAUNCH("focal_bwd_kernel");
     return GGA_OK;
+}
+
+// The per-task entry points: the same kernels with a table of one entry.
+extern "C" int gga_focal_loss_fwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
+                                  float scale, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.logits = logits; T.target = target; T.n_heat = n; T.focal_out = out;
+    return gga_focal_loss_fwd_tasks(&tb, alpha, gamma, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gga_focal_loss_bwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
+                                  float scale, const float* fwd_out, const float* grad_out, float* grad_logits,
+                                  void* stream) {
+    gga_task_table tb = {};
+    tb.n_tasks = 1;
+    gga_task& T = tb.task[0];
+    T.logits = logits; T.target = target; T.n_heat = n; T.focal_out = (float*)fwd_out; T.focal_grad = grad_out;
+    T.grad_logits = grad_logits;
+    return gga_focal_loss_bwd_tasks(&tb, alpha, gamma, scale, stream);
 }

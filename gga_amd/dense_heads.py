@@ -360,10 +360,52 @@ class CenterHead_GGA(nn.Module):
         return self.loss_from_targets(preds_dicts, heatmaps, anno_boxes, inds, masks, anno_lidar2imgs, ibp_points,
                                       anno_bound_masks)
 
+    @staticmethod
+    def _tasks_share_a_launch(preds_dicts, inds):
+        """True when the task-batched loss kernels apply: device maps of one B x H x W and one K for every task, and no more
+        tasks than a launch takes; else ``loss_from_targets`` goes task by task."""
+        from . import _lib
+        T = len(preds_dicts)
+        if not 1 <= T <= _lib.MAX_TASKS:
+            return False
+        first = preds_dicts[0][0]['reg']
+        if not first.is_cuda:
+            return False
+        for t in range(T):
+            pd = preds_dicts[t][0]
+            if inds[t].shape != inds[0].shape or not inds[t].is_cuda:
+                return False
+            for k in ('heatmap', 'reg', 'height', 'dim', 'rot'):
+                m = pd[k]
+                if m.device != first.device or m.dtype != torch.float32 or m.shape[0] != first.shape[0] or m.shape[2:] != first.shape[2:]:
+                    return False
+        return True
+
     def loss_from_targets(self, preds_dicts, heatmaps, anno_boxes, inds, masks, anno_lidar2imgs, ibp_points,
                           anno_bound_masks):
         loss_dict = dict()
         tc = self.train_cfg
+        if self._tasks_share_a_launch(preds_dicts, inds):
+            # every stage once for all tasks (F.*_tasks: the kernels pick their task from the grid), same values bit for bit
+            T = len(preds_dicts)
+            pds = [p[0] for p in preds_dicts]
+            B, K = inds[0].shape
+            l_heat, _ = F.gaussian_focal_loss_tasks([pd['heatmap'] for pd in pds], heatmaps[:T], alpha=self.loss_cls.alpha,
+                                                    gamma=self.loss_cls.gamma, scale=self.loss_cls.loss_weight * 5.0)
+            preds = F.gather_pred_tasks([(pd['reg'], pd['height'], pd['dim'], pd['rot']) for pd in pds], inds[:T], masks[:T])
+            prm = F.loss_params(B, K, tc, l1_loss_weight=self.loss_bbox.loss_weight)
+            terms, _ = F.box_loss_terms_tasks(
+                [(preds[t], inds[t], masks[t], anno_boxes[t], anno_lidar2imgs[t], anno_bound_masks[t], ibp_points[t][0],
+                  ibp_points[t][1], ibp_points[t][2] if ibp_points[t][2].numel() else None) for t in range(T)], prm)
+            for task_id in range(T):
+                l_bpl, l_srl, l_pmin, l_px, l_py = terms[task_id]
+                loss_dict[f'task{task_id}.distancex'] = l_px
+                loss_dict[f'task{task_id}.distancey'] = l_py
+                loss_dict[f'task{task_id}.distancemin'] = l_pmin
+                loss_dict[f'task{task_id}.loss_heatmap'] = l_heat[task_id]
+                loss_dict[f'task{task_id}.loss_bbox'] = l_bpl
+                loss_dict[f'task{task_id}.loss_ratio'] = l_srl
+            return loss_dict
         for task_id, preds_dict in enumerate(preds_dicts):
             pd = preds_dict[0]
             B, K = inds[task_id].shape

@@ -503,6 +503,68 @@ def gaussian_focal_loss(logits, target, alpha=2.0, gamma=4.0, scale=1.0):
     return _GaussianFocal.apply(logits, target, float(alpha), float(gamma), float(scale))
 
 
+def _task_table(n):
+    """An empty gga_task_table for ``n`` tasks; the caller fills the fields its stage reads (pointers as ints)."""
+    if not 1 <= n <= _lib.MAX_TASKS:
+        raise ValueError(f'{n} tasks: the loss kernels take 1..{_lib.MAX_TASKS} per launch')
+    tb = _lib.TaskTable()
+    tb.n_tasks = n
+    return tb
+
+
+class _GaussianFocalTasks(torch.autograd.Function):
+    """_GaussianFocal for all tasks of a head: one launch per kernel (gga_focal_loss_*_tasks), every task's loss and gradient
+    bit for bit its own call's. Inputs: T logits, then T targets; outputs: T losses, then T num_pos."""
+
+    @staticmethod
+    def forward(ctx, alpha, gamma, scale, *maps):
+        T = len(maps) // 2
+        _need_cuda(*maps)
+        maps = [m.contiguous() for m in maps]
+        L = _lib.lib()
+        dev = maps[0].device
+        out = torch.empty((T, 2), dtype=torch.float32, device=dev)
+        tb = _task_table(T)
+        for t in range(T):
+            e = tb.task[t]
+            e.logits, e.target, e.n_heat, e.focal_out = _p(maps[t]), _p(maps[T + t]), maps[t].numel(), out.data_ptr() + 8 * t
+        nbytes = L.gga_focal_loss_workspace_bytes_tasks(max(m.numel() for m in maps[:T]), T)
+        ws = _workspace('focal', nbytes, dev)
+        check(L.gga_focal_loss_fwd_tasks(C.byref(tb), alpha, gamma, scale, _p(ws), ws.numel(), _stream()),
+              'gga_focal_loss_fwd_tasks')
+        ctx.save_for_backward(out, *maps)
+        ctx.cfg = (alpha, gamma, scale)
+        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
+        return (*out[:, 0].unbind(0), *out[:, 1].unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        out, *maps = ctx.saved_tensors
+        T = len(maps) // 2
+        live = [t for t in range(T) if gs[t] is not None]
+        if not live:
+            return (None,) * (3 + 2 * T)
+        alpha, gamma, scale = ctx.cfg
+        grads = [None] * T
+        g = [None] * T
+        tb = _task_table(len(live))
+        for j, t in enumerate(live):
+            grads[t] = torch.empty_like(maps[t])
+            g[t] = gs[t].contiguous().float()
+            e = tb.task[j]
+            e.logits, e.target, e.n_heat, e.focal_out = _p(maps[t]), _p(maps[T + t]), maps[t].numel(), out.data_ptr() + 8 * t
+            e.focal_grad, e.grad_logits = _p(g[t]), _p(grads[t])
+        check(_lib.lib().gga_focal_loss_bwd_tasks(C.byref(tb), alpha, gamma, scale, _stream()), 'gga_focal_loss_bwd_tasks')
+        return (None, None, None, *grads, *([None] * T))
+
+
+def gaussian_focal_loss_tasks(logits, targets, alpha=2.0, gamma=4.0, scale=1.0):
+    """``gaussian_focal_loss`` of every task (lists of T maps) in one launch per kernel -> (T losses, T num_pos)."""
+    T = len(logits)
+    out = _GaussianFocalTasks.apply(float(alpha), float(gamma), float(scale), *logits, *targets)
+    return out[:T], out[T:]
+
+
 # ----------------------------------------------------------------------------- a9
 class _GatherPred(torch.autograd.Function):
     @staticmethod
@@ -540,6 +602,59 @@ class _GatherPred(torch.autograd.Function):
 def gather_pred(reg, height, dim, rot, ind, mask):
     """cat(reg,height,dim,rot) gathered at ``ind`` -> pred [B,K,8] (head:657-676)."""
     return _GatherPred.apply(reg, height, dim, rot, ind.contiguous(), mask.contiguous())
+
+
+class _GatherPredTasks(torch.autograd.Function):
+    """_GatherPred for all tasks of a head (maps of one size, one K): one launch each way. Inputs: per task reg, height, dim,
+    rot, ind, mask; outputs: T preds. The tables carry the maps' pointers - nothing is stacked."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        T = len(args) // 6
+        _need_cuda(*args)
+        B, _, H, W = args[0].shape
+        K = args[4].shape[1]
+        pred = torch.empty((T, B, K, 8), dtype=torch.float32, device=args[0].device)
+        keep = [a.contiguous() for a in args]          # bound to names until the launch is queued (see _GatherPred.forward)
+        tb = _task_table(T)
+        for t in range(T):
+            e = tb.task[t]
+            e.reg, e.height, e.dim, e.rot, e.ind = (_p(a) for a in keep[6 * t:6 * t + 5])
+            e.pred = _p(pred[t])
+        check(_lib.lib().gga_gather_pred_fwd_tasks(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_fwd_tasks')
+        ctx.save_for_backward(*[keep[6 * t + i] for t in range(T) for i in (4, 5)])
+        ctx.geom = (T, B, K, H, W)
+        return tuple(pred.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        T, B, K, H, W = ctx.geom
+        im = ctx.saved_tensors
+        dev = gs[0].device
+        # one allocation, the tasks' four views one behind the other: the entry point clears them all with ONE memset
+        hw = B * H * W
+        flat = torch.empty(T * 8 * hw, dtype=torch.float32, device=dev)
+        gs = [g.contiguous() for g in gs]
+        tb = _task_table(T)
+        out = []
+        for t in range(T):
+            f = flat[t * 8 * hw:(t + 1) * 8 * hw]
+            maps = (f[:2 * hw].view(B, 2, H, W), f[2 * hw:3 * hw].view(B, 1, H, W), f[3 * hw:6 * hw].view(B, 3, H, W),
+                    f[6 * hw:].view(B, 2, H, W))
+            e = tb.task[t]
+            e.grad_pred, e.ind, e.mask = _p(gs[t]), _p(im[2 * t]), _p(im[2 * t + 1])
+            e.g_reg, e.g_height, e.g_dim, e.g_rot = (_p(m) for m in maps)
+            out += [*maps, None, None]
+        check(_lib.lib().gga_gather_pred_bwd_tasks(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_bwd_tasks')
+        return tuple(out)
+
+
+def gather_pred_tasks(maps, inds, masks):
+    """``gather_pred`` of every task in one launch: ``maps[t]`` = (reg, height, dim, rot) -> T preds [B,K,8]."""
+    args = []
+    for m, ind, mask in zip(maps, inds, masks):
+        args += [*m, ind.contiguous(), mask.contiguous()]
+    return _GatherPredTasks.apply(*args)
 
 
 # ----------------------------------------------------------------------------- a10-a13
@@ -640,6 +755,74 @@ def box_loss_terms(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp
     out = _BoxLossTerms.apply(pred, ind.contiguous(), mask.contiguous(), anno_box.contiguous(), lidar2img.contiguous(),
                               bound_mask.contiguous(), ibp_xy, ibp_offsets, ibp_slot, prm)
     return out[:5], out[5]
+
+
+class _BoxLossTermsTasks(torch.autograd.Function):
+    """_BoxLossTerms for all tasks of a head (one ``prm``): one launch per kernel. Inputs: per task the nine tensors of
+    ``box_loss_terms``; outputs: per task its five scalar terms, then the T ``box_out``."""
+
+    @staticmethod
+    def forward(ctx, prm, *args):
+        T = len(args) // 9
+        B, K = prm.B, prm.K
+        n = B * K
+        L = _lib.lib()
+        _need_cuda(*[a for t in range(T) for a in args[9 * t:9 * t + 6]])
+        dev = args[0].device
+        losses = torch.empty((T, 5), dtype=torch.float32, device=dev)
+        flat = torch.empty((T, n * (5 * 8 + 12)), dtype=torch.float32, device=dev)      # one allocation: the entry point clears it with one memset
+        ws = _workspace('box', L.gga_box_losses_workspace_bytes_tasks(B, K, T), dev)
+        tb = _task_table(T)
+        keep, grads, boxes = [], [], []
+        for t in range(T):
+            pred, ind, mask, anno, l2i, bmask, xy, off, slot = args[9 * t:9 * t + 9]
+            pred = pred.contiguous()
+            keep.append(pred)
+            grads.append(flat[t, :5 * n * 8].view(5, B, K, 8))
+            boxes.append(flat[t, 5 * n * 8:].view(B, K, 12))
+            e = tb.task[t]
+            e.pred, e.ind, e.mask, e.anno_box, e.lidar2img, e.bound_mask = _p(pred), _p(ind), _p(mask), _p(anno), _p(l2i), _p(bmask)
+            e.ibp_xy, e.ibp_offsets, e.ibp_slot = _p(xy), _p(off), _p(slot)
+            e.n_ibp_obj = 0 if slot is None else int(slot.shape[0])
+            e.losses, e.box_out, e.term_grads = losses.data_ptr() + 20 * t, _p(boxes[t]), _p(grads[t])
+        check(L.gga_box_losses_fwd_tasks(C.byref(tb), C.byref(prm), _p(ws), ws.numel(), _stream()), 'gga_box_losses_fwd_tasks')
+        ctx.save_for_backward(flat)
+        ctx.geom = (T, B, K)
+        ctx.mark_non_differentiable(*boxes)
+        ctx.set_materialize_grads(False)     # the terms nobody differentiates arrive in backward as None
+        return (*losses.view(-1).unbind(0), *boxes)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        (flat,) = ctx.saved_tensors
+        T, B, K = ctx.geom
+        gs = gs[:5 * T]
+        if all(g is None for g in gs):
+            return (None,) * (1 + 9 * T)
+        dev = flat.device
+        z = _zero_scalar(dev)
+        g_losses = torch.stack([z if g is None else g.float().reshape(()) for g in gs])      # [5 T] scalars: ONE stack for all tasks
+        out = torch.empty((T, B, K, 8), dtype=torch.float32, device=dev)
+        tb = _task_table(T)
+        for t in range(T):
+            e = tb.task[t]
+            e.term_grads, e.grad_losses, e.grad_pred = _p(flat[t]), g_losses.data_ptr() + 20 * t, _p(out[t])
+        check(_lib.lib().gga_box_losses_bwd_tasks(C.byref(tb), B, K, _stream()), 'gga_box_losses_bwd_tasks')
+        res = [None]
+        for t in range(T):
+            res += [out[t]] + [None] * 8
+        return tuple(res)
+
+
+def box_loss_terms_tasks(tasks, prm):
+    """``box_loss_terms`` of every task in one launch per kernel. ``tasks[t]`` = (pred, ind, mask, anno_box, lidar2img,
+    bound_mask, ibp_xy, ibp_offsets, ibp_slot) -> (T tuples of the five scalar terms, T box_out)."""
+    args = []
+    for pred, ind, mask, anno, l2i, bmask, xy, off, slot in tasks:
+        args += [pred, ind.contiguous(), mask.contiguous(), anno.contiguous(), l2i.contiguous(), bmask.contiguous(), xy, off, slot]
+    T = len(tasks)
+    out = _BoxLossTermsTasks.apply(prm, *args)
+    return [out[5 * t:5 * t + 5] for t in range(T)], out[5 * T:]
 
 
 def box_losses(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot, prm):

@@ -724,6 +724,53 @@ int gga_heatmap_splat(float* heatmap, int n_maps, int H, int W, const int32_t* o
                       void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* The tasks of a head in one launch (a8 - a13).                              */
+/* A CenterHead computes the same losses for every task (class group), on     */
+/* maps of one size. Each loss kernel takes this table BY VALUE and picks its */
+/* task from blockIdx.y, so a stage costs one launch whatever the number of   */
+/* tasks. An entry carries the device pointers that stage's per-task entry    */
+/* point takes (same shapes, documented there) and the two sizes that differ  */
+/* between tasks; a stage reads only its own fields, the others may stay null.*/
+/* ------------------------------------------------------------------------- */
+#define GGA_MAX_TASKS 8
+typedef struct {
+    /* focal loss: logits, target [n_heat] (n_heat = B * classes of the task * H * W); focal_out [2] = (loss, num_pos),
+     * written by the forward and read by the backward; focal_grad [1] = d / d loss; grad_logits [n_heat] */
+    const float* logits;
+    const float* target;
+    int64_t n_heat;
+    float* focal_out;
+    const float* focal_grad;
+    float* grad_logits;
+    /* gather: the four maps and their gradients */
+    const float *reg, *height, *dim, *rot;
+    float *g_reg, *g_height, *g_dim, *g_rot;
+    /* gather and box losses: ind [B,K] i64, mask [B,K] u8; pred [B,K,8] (written by the gather, read by the losses);
+     * grad_pred [B,K,8] (written by the losses' backward, read by the gather's) */
+    const int64_t* ind;
+    const uint8_t* mask;
+    float* pred;
+    float* grad_pred;
+    /* box losses: inputs and outputs of gga_box_losses_fwd (term_grads is its grad_pred [5,B,K,8]); grad_losses [5] */
+    const float* anno_box;
+    const float* lidar2img;
+    const uint8_t* bound_mask;
+    const float* ibp_xy;
+    const int32_t* ibp_offsets;
+    const int32_t* ibp_slot;
+    int32_t n_ibp_obj;
+    float* losses;
+    float* box_out;
+    float* term_grads;
+    const float* grad_losses;
+} gga_task;
+
+typedef struct {
+    int32_t n_tasks;                      /* 1 .. GGA_MAX_TASKS */
+    gga_task task[GGA_MAX_TASKS];
+} gga_task_table;
+
+/* ------------------------------------------------------------------------- */
 /* a8. clip_sigmoid + GaussianFocalLoss (mean over max(num_pos,1)), fused.    */
 /* Replaces mmdet3d/models/utils/clip_sigmoid.py:16 + mmdet GaussianFocalLoss */
 /* + the host-syncing num_pos.item() of centerpoint_head_gga.py:650-655.      */
@@ -738,6 +785,12 @@ int gga_focal_loss_fwd(const float* logits, const float* target, int64_t n, floa
 int gga_focal_loss_bwd(const float* logits, const float* target, int64_t n, float alpha,
                        float gamma, float scale, const float* fwd_out, const float* grad_out,
                        float* grad_logits, void* stream);
+/* The same for every task of the table in one launch per kernel (the per-task calls above are these with one entry: every
+ * task's result is bit for bit what its own call gives). Workspace: n_max = the largest n_heat of the table. */
+size_t gga_focal_loss_workspace_bytes_tasks(int64_t n_max, int n_tasks);
+int gga_focal_loss_fwd_tasks(const gga_task_table* tasks, float alpha, float gamma, float scale, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int gga_focal_loss_bwd_tasks(const gga_task_table* tasks, float alpha, float gamma, float scale, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a9. Gather the 8 regression channels at the object cells, and its backward */
@@ -753,6 +806,12 @@ int gga_gather_pred_fwd(const float* reg, const float* height, const float* dim,
 int gga_gather_pred_bwd(const float* grad_pred, const int64_t* ind, const uint8_t* mask, int B,
                         int K, int H, int W, float* g_reg, float* g_height, float* g_dim,
                         float* g_rot, void* stream);
+/* All tasks of the table in one launch (B, K, H, W are the tasks' common sizes). The backward keeps a frame's K slots in
+ * LDS: K <= 512, else GGA_ERR_INVALID_ARG (this holds for the per-task call too). It clears every gradient map with ONE
+ * memset when each task's four maps lie one behind the other (reg, height, dim, rot) and the tasks one behind the other,
+ * else with one memset per task or map. */
+int gga_gather_pred_fwd_tasks(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
+int gga_gather_pred_bwd_tasks(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a10-a13. The GGA geometry-aware losses for one task, forward + analytic    */
@@ -800,6 +859,15 @@ int gga_box_losses_fwd(const float* pred, const int64_t* ind, const uint8_t* mas
 /* grad_pred_out [B,K,8] = sum_t grad_losses[t] * grad_pred[t] (grad_losses [5] on device). */
 int gga_box_losses_bwd(const float* grad_pred, const float* grad_losses, int B, int K,
                        float* grad_pred_out, void* stream);
+
+/* All tasks of the table in one launch per kernel (box_slot_kernel excepted: one launch per task, see head_loss.hip); prm
+ * (B, K included) is common to the tasks. term_grads and box_out are cleared with ONE memset when each task's box_out lies
+ * behind its term_grads and the tasks one behind the other; a second one clears the workspace. */
+size_t gga_box_losses_workspace_bytes_tasks(int B, int K, int n_tasks);
+int gga_box_losses_fwd_tasks(const gga_task_table* tasks, const gga_loss_params* prm, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* task.grad_pred [B,K,8] = sum_t task.grad_losses[t] * task.term_grads[t] */
+int gga_box_losses_bwd_tasks(const gga_task_table* tasks, int B, int K, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SURVEY.md §8(f) rank 1 — inference / pseudo-label post-processing.        */
