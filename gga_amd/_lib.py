@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _lib = None
 
@@ -34,7 +34,7 @@ MAX_TASKS = 8      # GGA_MAX_TASKS
 
 
 class Task(C.Structure):
-    """gga_task: one task's pointers for the task-batched loss kernels (a stage reads only its own fields)."""
+    """gga_task: one task's pointers for the loss kernels (a stage reads only its own fields)."""
     _fields_ = [('logits', vp), ('target', vp), ('n_heat', i64), ('focal_out', vp), ('focal_grad', vp), ('grad_logits', vp),
                 ('reg', vp), ('height', vp), ('dim', vp), ('rot', vp), ('g_reg', vp), ('g_height', vp), ('g_dim', vp),
                 ('g_rot', vp), ('ind', vp), ('mask', vp), ('pred', vp), ('grad_pred', vp), ('anno_box', vp), ('lidar2img', vp),
@@ -143,23 +143,14 @@ SIGNATURES = {
     'gga_head_branch_bwd_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'gga_head_branch_bwd': (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp, sz, vp]),
     'gga_heatmap_splat': (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp]),
-    'gga_focal_loss_workspace_bytes': (sz, [i64]),
-    'gga_focal_loss_fwd': (i32, [vp, vp, i64, f32, f32, f32, vp, vp, sz, vp]),
-    'gga_focal_loss_bwd': (i32, [vp, vp, i64, f32, f32, f32, vp, vp, vp, vp]),
-    'gga_focal_loss_workspace_bytes_tasks': (sz, [i64, i32]),
-    'gga_focal_loss_fwd_tasks': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp, sz, vp]),
-    'gga_focal_loss_bwd_tasks': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp]),
-    'gga_gather_pred_fwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
-    'gga_gather_pred_bwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
-    'gga_box_losses_workspace_bytes_tasks': (sz, [i32, i32, i32]),
-    'gga_box_losses_fwd_tasks': (i32, [C.POINTER(TaskTable), C.POINTER(LossParams), vp, sz, vp]),
-    'gga_box_losses_bwd_tasks': (i32, [C.POINTER(TaskTable), i32, i32, vp]),
-    'gga_gather_pred_fwd': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    'gga_gather_pred_bwd': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
-    'gga_box_losses_workspace_bytes': (sz, [i32, i32]),
-    'gga_box_losses_fwd': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(LossParams),
-                                  vp, vp, vp, vp, sz, vp]),
-    'gga_box_losses_bwd': (i32, [vp, vp, i32, i32, vp, vp]),
+    'gga_focal_loss_workspace_bytes': (sz, [i64, i32]),
+    'gga_focal_loss_fwd': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp, sz, vp]),
+    'gga_focal_loss_bwd': (i32, [C.POINTER(TaskTable), f32, f32, f32, vp]),
+    'gga_gather_pred_fwd': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
+    'gga_gather_pred_bwd': (i32, [C.POINTER(TaskTable), i32, i32, i32, i32, vp]),
+    'gga_box_losses_workspace_bytes': (sz, [i32, i32, i32]),
+    'gga_box_losses_fwd': (i32, [C.POINTER(TaskTable), C.POINTER(LossParams), vp, sz, vp]),
+    'gga_box_losses_bwd': (i32, [C.POINTER(TaskTable), i32, i32, vp]),
     'gga_box_iou_rotated': (i32, [vp, i32, vp, i32, i32, i32, vp, vp]),
     'gga_nms_rotated_workspace_bytes': (sz, [i32]),
     'gga_nms_rotated_sorted': (i32, [vp, i32, f32, i32, vp, vp, vp, sz, vp]),

@@ -97,8 +97,8 @@ static int check_table(const char* fn, const gga_task_table* tb) {
     return GGA_OK;
 }
 
-extern "C" int gga_gather_pred_fwd_tasks(const gga_task_table* tb, int B, int K, int H, int W, void* stream) {
-    const char* fn = "gga_gather_pred_fwd_tasks";
+extern "C" int gga_gather_pred_fwd(const gga_task_table* tb, int B, int K, int H, int W, void* stream) {
+    const char* fn = "gga_gather_pred_fwd";
     if (int rc = check_table(fn, tb)) return rc;
     GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "%s: bad sizes", fn);
     for (int t = 0; t < tb->n_tasks; ++t) {
@@ -112,8 +112,8 @@ extern "C" int gga_gather_pred_fwd_tasks(const gga_task_table* tb, int B, int K,
     return GGA_OK;
 }
 
-extern "C" int gga_gather_pred_bwd_tasks(const gga_task_table* tb, int B, int K, int H, int W, void* stream_) {
-    const char* fn = "gga_gather_pred_bwd_tasks";
+extern "C" int gga_gather_pred_bwd(const gga_task_table* tb, int B, int K, int H, int W, void* stream_) {
+    const char* fn = "gga_gather_pred_bwd";
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_table(fn, tb)) return rc;
     GGA_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "%s: bad sizes", fn);
@@ -146,27 +146,6 @@ extern "C" int gga_gather_pred_bwd_tasks(const gga_task_table* tb, int B, int K,
     hipLaunchKernelGGL(gather_pred_bwd_kernel, dim3(B, tb->n_tasks), dim3(256), 0, stream, *tb, K, (int64_t)H * W);
     GGA_CHECK_LAUNCH("gather_pred_bwd_kernel");
     return GGA_OK;
-}
-
-// The per-task entry points: the same kernels with a table of one entry.
-extern "C" int gga_gather_pred_fwd(const float* reg, const float* height, const float* dim, const float* rot,
-                                   const int64_t* ind, int B, int K, int H, int W, float* pred, void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.reg = reg; T.height = height; T.dim = dim; T.rot = rot; T.ind = ind; T.pred = pred;
-    return gga_gather_pred_fwd_tasks(&tb, B, K, H, W, stream);
-}
-
-extern "C" int gga_gather_pred_bwd(const float* grad_pred, const int64_t* ind, const uint8_t* mask, int B, int K,
-                                   int H, int W, float* g_reg, float* g_height, float* g_dim, float* g_rot,
-                                   void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.grad_pred = (float*)grad_pred; T.ind = ind; T.mask = mask;
-    T.g_reg = g_reg; T.g_height = g_height; T.g_dim = g_dim; T.g_rot = g_rot;
-    return gga_gather_pred_bwd_tasks(&tb, B, K, H, W, stream);
 }
 
 // ----------------------------------------------------------------------------- losses
@@ -481,15 +460,13 @@ __global__ __launch_bounds__(256) void box_bwd_kernel(gga_task_table tb, int n8)
     out[t] = acc;
 }
 
-extern "C" size_t gga_box_losses_workspace_bytes_tasks(int B, int K, int n_tasks) {
+extern "C" size_t gga_box_losses_workspace_bytes(int B, int K, int n_tasks) {
     return (size_t)GGA_L_NUM * B * K * sizeof(float) * n_tasks;
 }
 
-extern "C" size_t gga_box_losses_workspace_bytes(int B, int K) { return gga_box_losses_workspace_bytes_tasks(B, K, 1); }
-
-extern "C" int gga_box_losses_fwd_tasks(const gga_task_table* tb, const gga_loss_params* prm, void* workspace,
-                                        size_t workspace_bytes, void* stream_) {
-    const char* fn = "gga_box_losses_fwd_tasks";
+extern "C" int gga_box_losses_fwd(const gga_task_table* tb, const gga_loss_params* prm, void* workspace,
+                                  size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_box_losses_fwd";
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_table(fn, tb)) return rc;
     GGA_REQUIRE(prm && workspace, "%s: null pointer argument", fn);
@@ -507,9 +484,9 @@ extern "C" int gga_box_losses_fwd_tasks(const gga_task_table* tb, const gga_loss
         max_obj = T.n_ibp_obj > max_obj ? T.n_ibp_obj : max_obj;
         one = one && T.term_grads == tb->task[0].term_grads + per_task * t && T.box_out == T.term_grads + (size_t)GGA_L_NUM * n * 8;
     }
-    if (workspace_bytes < gga_box_losses_workspace_bytes_tasks(prm->B, prm->K, nt)) {
+    if (workspace_bytes < gga_box_losses_workspace_bytes(prm->B, prm->K, nt)) {
         gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes,
-                      gga_box_losses_workspace_bytes_tasks(prm->B, prm->K, nt));
+                      gga_box_losses_workspace_bytes(prm->B, prm->K, nt));
         return GGA_ERR_WORKSPACE;
     }
     float* part = (float*)workspace;             // [task][GGA_L_NUM][n]
@@ -542,8 +519,8 @@ extern "C" int gga_box_losses_fwd_tasks(const gga_task_table* tb, const gga_loss
     return GGA_OK;
 }
 
-extern "C" int gga_box_losses_bwd_tasks(const gga_task_table* tb, int B, int K, void* stream) {
-    const char* fn = "gga_box_losses_bwd_tasks";
+extern "C" int gga_box_losses_bwd(const gga_task_table* tb, int B, int K, void* stream) {
+    const char* fn = "gga_box_losses_bwd";
     if (int rc = check_table(fn, tb)) return rc;
     GGA_REQUIRE(B >= 1 && K >= 1, "%s: bad sizes", fn);
     for (int t = 0; t < tb->n_tasks; ++t) {
@@ -554,28 +531,4 @@ extern "C" int gga_box_losses_bwd_tasks(const gga_task_table* tb, int B, int K, 
     hipLaunchKernelGGL(box_bwd_kernel, dim3((n8 + 255) / 256, tb->n_tasks), dim3(256), 0, (hipStream_t)stream, *tb, n8);
     GGA_CHECK_LAUNCH("box_bwd_kernel");
     return GGA_OK;
-}
-
-// The per-task entry points: the same kernels with a table of one entry.
-extern "C" int gga_box_losses_fwd(const float* pred, const int64_t* ind, const uint8_t* mask, const float* anno_box,
-                                  const float* lidar2img, const uint8_t* bound_mask, const float* ibp_xy,
-                                  const int32_t* ibp_offsets, const int32_t* ibp_slot, int n_ibp_obj,
-                                  const gga_loss_params* prm, float* losses, float* box_out, float* grad_pred,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.pred = (float*)pred; T.ind = ind; T.mask = mask; T.anno_box = anno_box; T.lidar2img = lidar2img; T.bound_mask = bound_mask;
-    T.ibp_xy = ibp_xy; T.ibp_offsets = ibp_offsets; T.ibp_slot = ibp_slot; T.n_ibp_obj = n_ibp_obj;
-    T.losses = losses; T.box_out = box_out; T.term_grads = grad_pred;
-    return gga_box_losses_fwd_tasks(&tb, prm, workspace, workspace_bytes, stream);
-}
-
-extern "C" int gga_box_losses_bwd(const float* grad_pred, const float* grad_losses, int B, int K,
-                                  float* grad_pred_out, void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.term_grads = (float*)grad_pred; T.grad_losses = grad_losses; T.grad_pred = grad_pred_out;
-    return gga_box_losses_bwd_tasks(&tb, B, K, stream);
 }

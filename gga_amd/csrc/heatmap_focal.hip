@@ -204,22 +204,20 @@ static int focal_check_table(const char* fn, const gga_task_table* tb, bool bwd,
     return GGA_OK;
 }
 
-extern "C" size_t gga_focal_loss_workspace_bytes_tasks(int64_t n_max, int n_tasks) {
+extern "C" size_t gga_focal_loss_workspace_bytes(int64_t n_max, int n_tasks) {
     return (size_t)focal_blocks(n_max, FOCAL_MAX_BLOCKS) * 2 * sizeof(float) * n_tasks;
 }
 
-extern "C" size_t gga_focal_loss_workspace_bytes(int64_t n) { return gga_focal_loss_workspace_bytes_tasks(n, 1); }
-
-extern "C" int gga_focal_loss_fwd_tasks(const gga_task_table* tb, float alpha, float gamma, float scale, void* workspace,
-                                        size_t workspace_bytes, void* stream_) {
-    const char* fn = "gga_focal_loss_fwd_tasks";
+extern "C" int gga_focal_loss_fwd(const gga_task_table* tb, float alpha, float gamma, float scale, void* workspace,
+                                  size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_focal_loss_fwd";
     hipStream_t stream = (hipStream_t)stream_;
     int64_t n_max;
     if (int rc = focal_check_table(fn, tb, false, &n_max)) return rc;
     GGA_REQUIRE(workspace, "%s: null workspace", fn);
-    if (workspace_bytes < gga_focal_loss_workspace_bytes_tasks(n_max, tb->n_tasks)) {
+    if (workspace_bytes < gga_focal_loss_workspace_bytes(n_max, tb->n_tasks)) {
         gga_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes,
-                      gga_focal_loss_workspace_bytes_tasks(n_max, tb->n_tasks));
+                      gga_focal_loss_workspace_bytes(n_max, tb->n_tasks));
         return GGA_ERR_WORKSPACE;
     }
     const int nb = focal_blocks(n_max, FOCAL_MAX_BLOCKS), slice = 2 * nb;
@@ -230,33 +228,12 @@ extern "C" int gga_focal_loss_fwd_tasks(const gga_task_table* tb, float alpha, f
     return GGA_OK;
 }
 
-extern "C" int gga_focal_loss_bwd_tasks(const gga_task_table* tb, float alpha, float gamma, float scale, void* stream_) {
-    const char* fn = "gga_focal_loss_bwd_tasks";
+extern "C" int gga_focal_loss_bwd(const gga_task_table* tb, float alpha, float gamma, float scale, void* stream_) {
+    const char* fn = "gga_focal_loss_bwd";
     int64_t n_max;
     if (int rc = focal_check_table(fn, tb, true, &n_max)) return rc;
     hipLaunchKernelGGL(focal_bwd_kernel, dim3(focal_blocks(n_max, FOCAL_BWD_MAX_BLOCKS), tb->n_tasks), dim3(256), 0,
                        (hipStream_t)stream_, *tb, alpha, gamma, scale);
     GGA_CHECK_LAUNCH("focal_bwd_kernel");
     return GGA_OK;
-}
-
-// The per-task entry points: the same kernels with a table of one entry.
-extern "C" int gga_focal_loss_fwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
-                                  float scale, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.logits = logits; T.target = target; T.n_heat = n; T.focal_out = out;
-    return gga_focal_loss_fwd_tasks(&tb, alpha, gamma, scale, workspace, workspace_bytes, stream);
-}
-
-extern "C" int gga_focal_loss_bwd(const float* logits, const float* target, int64_t n, float alpha, float gamma,
-                                  float scale, const float* fwd_out, const float* grad_out, float* grad_logits,
-                                  void* stream) {
-    gga_task_table tb = {};
-    tb.n_tasks = 1;
-    gga_task& T = tb.task[0];
-    T.logits = logits; T.target = target; T.n_heat = n; T.focal_out = (float*)fwd_out; T.focal_grad = grad_out;
-    T.grad_logits = grad_logits;
-    return gga_focal_loss_bwd_tasks(&tb, alpha, gamma, scale, stream);
 }

@@ -362,8 +362,8 @@ class CenterHead_GGA(nn.Module):
 
     @staticmethod
     def _tasks_share_a_launch(preds_dicts, inds):
-        """True when the task-batched loss kernels apply: device maps of one B x H x W and one K for every task, and no more
-        tasks than a launch takes; else ``loss_from_targets`` goes task by task."""
+        """True when one launch per loss kernel serves all tasks: device maps of one B x H x W and one K for every task, and no
+        more tasks than a launch takes; else ``loss_from_targets`` goes task by task."""
         from . import _lib
         T = len(preds_dicts)
         if not 1 <= T <= _lib.MAX_TASKS:
@@ -384,47 +384,29 @@ class CenterHead_GGA(nn.Module):
     def loss_from_targets(self, preds_dicts, heatmaps, anno_boxes, inds, masks, anno_lidar2imgs, ibp_points,
                           anno_bound_masks):
         loss_dict = dict()
-        tc = self.train_cfg
-        if self._tasks_share_a_launch(preds_dicts, inds):
-            # every stage once for all tasks (F.*_tasks: the kernels pick their task from the grid), same values bit for bit
-            T = len(preds_dicts)
-            pds = [p[0] for p in preds_dicts]
-            B, K = inds[0].shape
-            l_heat, _ = F.gaussian_focal_loss_tasks([pd['heatmap'] for pd in pds], heatmaps[:T], alpha=self.loss_cls.alpha,
-                                                    gamma=self.loss_cls.gamma, scale=self.loss_cls.loss_weight * 5.0)
-            preds = F.gather_pred_tasks([(pd['reg'], pd['height'], pd['dim'], pd['rot']) for pd in pds], inds[:T], masks[:T])
-            prm = F.loss_params(B, K, tc, l1_loss_weight=self.loss_bbox.loss_weight)
+        T = len(preds_dicts)
+        # every stage once for all tasks (the kernels pick their task from the grid), or task by task: same values bit for bit
+        groups = [range(T)] if self._tasks_share_a_launch(preds_dicts, inds) else [[t] for t in range(T)]
+        for group in groups:
+            pds = [preds_dicts[t][0] for t in group]
+            B, K = inds[group[0]].shape
+            # heat-map focal loss on the raw logits (clip_sigmoid fused, num_pos stays on device)
+            l_heat, _ = F.gaussian_focal_loss_tasks([pd['heatmap'] for pd in pds], [heatmaps[t] for t in group],
+                                                    alpha=self.loss_cls.alpha, gamma=self.loss_cls.gamma,
+                                                    scale=self.loss_cls.loss_weight * 5.0)
+            preds = F.gather_pred_tasks([(pd['reg'], pd['height'], pd['dim'], pd['rot']) for pd in pds],
+                                        [inds[t] for t in group], [masks[t] for t in group])
+            prm = F.loss_params(B, K, self.train_cfg, l1_loss_weight=self.loss_bbox.loss_weight)
             terms, _ = F.box_loss_terms_tasks(
-                [(preds[t], inds[t], masks[t], anno_boxes[t], anno_lidar2imgs[t], anno_bound_masks[t], ibp_points[t][0],
-                  ibp_points[t][1], ibp_points[t][2] if ibp_points[t][2].numel() else None) for t in range(T)], prm)
-            for task_id in range(T):
-                l_bpl, l_srl, l_pmin, l_px, l_py = terms[task_id]
+                [(pred, inds[t], masks[t], anno_boxes[t], anno_lidar2imgs[t], anno_bound_masks[t], ibp_points[t][0],
+                  ibp_points[t][1], ibp_points[t][2] if ibp_points[t][2].numel() else None) for t, pred in zip(group, preds)], prm)
+            for task_id, loss_heatmap, (l_bpl, l_srl, l_pmin, l_px, l_py) in zip(group, l_heat, terms):
                 loss_dict[f'task{task_id}.distancex'] = l_px
                 loss_dict[f'task{task_id}.distancey'] = l_py
                 loss_dict[f'task{task_id}.distancemin'] = l_pmin
-                loss_dict[f'task{task_id}.loss_heatmap'] = l_heat[task_id]
+                loss_dict[f'task{task_id}.loss_heatmap'] = loss_heatmap
                 loss_dict[f'task{task_id}.loss_bbox'] = l_bpl
                 loss_dict[f'task{task_id}.loss_ratio'] = l_srl
-            return loss_dict
-        for task_id, preds_dict in enumerate(preds_dicts):
-            pd = preds_dict[0]
-            B, K = inds[task_id].shape
-            # heat-map focal loss on the raw logits (clip_sigmoid fused, num_pos stays on device)
-            loss_heatmap, _ = F.gaussian_focal_loss(pd['heatmap'], heatmaps[task_id],
-                                                    alpha=self.loss_cls.alpha, gamma=self.loss_cls.gamma,
-                                                    scale=self.loss_cls.loss_weight * 5.0)
-            pred = F.gather_pred(pd['reg'], pd['height'], pd['dim'], pd['rot'], inds[task_id], masks[task_id])
-            prm = F.loss_params(B, K, tc, l1_loss_weight=self.loss_bbox.loss_weight)
-            xy, offs, slot = ibp_points[task_id]
-            (l_bpl, l_srl, l_pmin, l_px, l_py), _ = F.box_loss_terms(pred, inds[task_id], masks[task_id], anno_boxes[task_id],
-                                                                     anno_lidar2imgs[task_id], anno_bound_masks[task_id],
-                                                                     xy, offs, slot if slot.numel() else None, prm)
-            loss_dict[f'task{task_id}.distancex'] = l_px
-            loss_dict[f'task{task_id}.distancey'] = l_py
-            loss_dict[f'task{task_id}.distancemin'] = l_pmin
-            loss_dict[f'task{task_id}.loss_heatmap'] = loss_heatmap
-            loss_dict[f'task{task_id}.loss_bbox'] = l_bpl
-            loss_dict[f'task{task_id}.loss_ratio'] = l_srl
         return loss_dict
 
     # ------------------------------------------------------------------ inference

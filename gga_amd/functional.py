@@ -468,41 +468,6 @@ def heatmap_splat(objs, n_maps, H, W, device, max_radius=64):
 
 
 # ----------------------------------------------------------------------------- a8
-class _GaussianFocal(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, alpha, gamma, scale):
-        _need_cuda(logits, target)
-        logits, target = logits.contiguous(), target.contiguous()
-        n = logits.numel()
-        L = _lib.lib()
-        ws = _workspace('focal', L.gga_focal_loss_workspace_bytes(n), logits.device)
-        out = torch.empty(2, dtype=torch.float32, device=logits.device)
-        check(L.gga_focal_loss_fwd(_p(logits), _p(target), n, alpha, gamma, scale, _p(out), _p(ws),
-                                   ws.numel(), _stream()), 'gga_focal_loss_fwd')
-        ctx.save_for_backward(logits, target, out)
-        ctx.cfg = (alpha, gamma, scale)
-        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
-        return out[0], out[1]
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_npos):
-        if g_loss is None:
-            return None, None, None, None, None
-        logits, target, out = ctx.saved_tensors
-        alpha, gamma, scale = ctx.cfg
-        grad = torch.empty_like(logits)
-        g = g_loss.contiguous().float()
-        check(_lib.lib().gga_focal_loss_bwd(_p(logits), _p(target), logits.numel(), alpha, gamma, scale,
-                                            _p(out), _p(g), _p(grad), _stream()), 'gga_focal_loss_bwd')
-        return grad, None, None, None, None
-
-
-def gaussian_focal_loss(logits, target, alpha=2.0, gamma=4.0, scale=1.0):
-    """clip_sigmoid + GaussianFocalLoss(reduction='mean', avg_factor=max(num_pos,1)), times
-    ``scale``. Takes the raw heat-map logits. Returns (loss, num_pos) device scalars."""
-    return _GaussianFocal.apply(logits, target, float(alpha), float(gamma), float(scale))
-
-
 def _task_table(n):
     """An empty gga_task_table for ``n`` tasks; the caller fills the fields its stage reads (pointers as ints)."""
     if not 1 <= n <= _lib.MAX_TASKS:
@@ -512,9 +477,9 @@ def _task_table(n):
     return tb
 
 
-class _GaussianFocalTasks(torch.autograd.Function):
-    """_GaussianFocal for all tasks of a head: one launch per kernel (gga_focal_loss_*_tasks), every task's loss and gradient
-    bit for bit its own call's. Inputs: T logits, then T targets; outputs: T losses, then T num_pos."""
+class _GaussianFocal(torch.autograd.Function):
+    """The focal loss of all tasks of a head: one launch per kernel (gga_focal_loss_*), every task's loss and gradient bit for
+    bit what a call with that task alone gives. Inputs: T logits, then T targets; outputs: T losses, then T num_pos."""
 
     @staticmethod
     def forward(ctx, alpha, gamma, scale, *maps):
@@ -528,10 +493,9 @@ class _GaussianFocalTasks(torch.autograd.Function):
         for t in range(T):
             e = tb.task[t]
             e.logits, e.target, e.n_heat, e.focal_out = _p(maps[t]), _p(maps[T + t]), maps[t].numel(), out.data_ptr() + 8 * t
-        nbytes = L.gga_focal_loss_workspace_bytes_tasks(max(m.numel() for m in maps[:T]), T)
+        nbytes = L.gga_focal_loss_workspace_bytes(max(m.numel() for m in maps[:T]), T)
         ws = _workspace('focal', nbytes, dev)
-        check(L.gga_focal_loss_fwd_tasks(C.byref(tb), alpha, gamma, scale, _p(ws), ws.numel(), _stream()),
-              'gga_focal_loss_fwd_tasks')
+        check(L.gga_focal_loss_fwd(C.byref(tb), alpha, gamma, scale, _p(ws), ws.numel(), _stream()), 'gga_focal_loss_fwd')
         ctx.save_for_backward(out, *maps)
         ctx.cfg = (alpha, gamma, scale)
         ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
@@ -554,58 +518,27 @@ class _GaussianFocalTasks(torch.autograd.Function):
             e = tb.task[j]
             e.logits, e.target, e.n_heat, e.focal_out = _p(maps[t]), _p(maps[T + t]), maps[t].numel(), out.data_ptr() + 8 * t
             e.focal_grad, e.grad_logits = _p(g[t]), _p(grads[t])
-        check(_lib.lib().gga_focal_loss_bwd_tasks(C.byref(tb), alpha, gamma, scale, _stream()), 'gga_focal_loss_bwd_tasks')
+        check(_lib.lib().gga_focal_loss_bwd(C.byref(tb), alpha, gamma, scale, _stream()), 'gga_focal_loss_bwd')
         return (None, None, None, *grads, *([None] * T))
 
 
 def gaussian_focal_loss_tasks(logits, targets, alpha=2.0, gamma=4.0, scale=1.0):
-    """``gaussian_focal_loss`` of every task (lists of T maps) in one launch per kernel -> (T losses, T num_pos)."""
+    """clip_sigmoid + GaussianFocalLoss(reduction='mean', avg_factor=max(num_pos,1)), times ``scale``, of every task (lists of
+    T maps of raw heat-map logits and T targets) in one launch per kernel -> (T losses, T num_pos) device scalars."""
     T = len(logits)
-    out = _GaussianFocalTasks.apply(float(alpha), float(gamma), float(scale), *logits, *targets)
+    out = _GaussianFocal.apply(float(alpha), float(gamma), float(scale), *logits, *targets)
     return out[:T], out[T:]
+
+
+def gaussian_focal_loss(logits, target, alpha=2.0, gamma=4.0, scale=1.0):
+    """``gaussian_focal_loss_tasks`` of one task. Returns (loss, num_pos) device scalars."""
+    loss, num_pos = gaussian_focal_loss_tasks([logits], [target], alpha, gamma, scale)
+    return loss[0], num_pos[0]
 
 
 # ----------------------------------------------------------------------------- a9
 class _GatherPred(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, reg, height, dim, rot, ind, mask):
-        _need_cuda(reg, height, dim, rot, ind, mask)
-        B, _, H, W = reg.shape
-        K = ind.shape[1]
-        pred = torch.empty((B, K, 8), dtype=torch.float32, device=reg.device)
-        # NB: bind the NCHW copies to names. `_p(x.contiguous())` would free each temporary as soon
-        # as its pointer is taken, and the next copy would be allocated over it (channels-last maps).
-        reg, height, dim, rot = reg.contiguous(), height.contiguous(), dim.contiguous(), rot.contiguous()
-        check(_lib.lib().gga_gather_pred_fwd(_p(reg), _p(height),
-                                             _p(dim), _p(rot), _p(ind), B, K, H, W,
-                                             _p(pred), _stream()), 'gga_gather_pred_fwd')
-        ctx.save_for_backward(ind, mask)
-        ctx.geom = (B, K, H, W)
-        return pred
-
-    @staticmethod
-    def backward(ctx, g):
-        ind, mask = ctx.saved_tensors
-        B, K, H, W = ctx.geom
-        dev = g.device
-        # one allocation, four views one behind the other: the entry point then clears them with ONE memset
-        flat = torch.empty(B * 8 * H * W, dtype=torch.float32, device=dev)
-        hw = B * H * W
-        g_reg, g_h = flat[:2 * hw].view(B, 2, H, W), flat[2 * hw:3 * hw].view(B, 1, H, W)
-        g_dim, g_rot = flat[3 * hw:6 * hw].view(B, 3, H, W), flat[6 * hw:].view(B, 2, H, W)
-        g = g.contiguous()
-        check(_lib.lib().gga_gather_pred_bwd(_p(g), _p(ind), _p(mask), B, K, H, W, _p(g_reg),
-                                             _p(g_h), _p(g_dim), _p(g_rot), _stream()), 'gga_gather_pred_bwd')
-        return g_reg, g_h, g_dim, g_rot, None, None
-
-
-def gather_pred(reg, height, dim, rot, ind, mask):
-    """cat(reg,height,dim,rot) gathered at ``ind`` -> pred [B,K,8] (head:657-676)."""
-    return _GatherPred.apply(reg, height, dim, rot, ind.contiguous(), mask.contiguous())
-
-
-class _GatherPredTasks(torch.autograd.Function):
-    """_GatherPred for all tasks of a head (maps of one size, one K): one launch each way. Inputs: per task reg, height, dim,
+    """The gather of all tasks of a head (maps of one size, one K): one launch each way. Inputs: per task reg, height, dim,
     rot, ind, mask; outputs: T preds. The tables carry the maps' pointers - nothing is stacked."""
 
     @staticmethod
@@ -615,13 +548,15 @@ class _GatherPredTasks(torch.autograd.Function):
         B, _, H, W = args[0].shape
         K = args[4].shape[1]
         pred = torch.empty((T, B, K, 8), dtype=torch.float32, device=args[0].device)
-        keep = [a.contiguous() for a in args]          # bound to names until the launch is queued (see _GatherPred.forward)
+        # NB: bind the NCHW copies to a name until the launch is queued. `_p(x.contiguous())` would free each temporary as soon
+        # as its pointer is taken, and the next copy would be allocated over it (channels-last maps).
+        keep = [a.contiguous() for a in args]
         tb = _task_table(T)
         for t in range(T):
             e = tb.task[t]
             e.reg, e.height, e.dim, e.rot, e.ind = (_p(a) for a in keep[6 * t:6 * t + 5])
             e.pred = _p(pred[t])
-        check(_lib.lib().gga_gather_pred_fwd_tasks(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_fwd_tasks')
+        check(_lib.lib().gga_gather_pred_fwd(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_fwd')
         ctx.save_for_backward(*[keep[6 * t + i] for t in range(T) for i in (4, 5)])
         ctx.geom = (T, B, K, H, W)
         return tuple(pred.unbind(0))
@@ -645,16 +580,22 @@ class _GatherPredTasks(torch.autograd.Function):
             e.grad_pred, e.ind, e.mask = _p(gs[t]), _p(im[2 * t]), _p(im[2 * t + 1])
             e.g_reg, e.g_height, e.g_dim, e.g_rot = (_p(m) for m in maps)
             out += [*maps, None, None]
-        check(_lib.lib().gga_gather_pred_bwd_tasks(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_bwd_tasks')
+        check(_lib.lib().gga_gather_pred_bwd(C.byref(tb), B, K, H, W, _stream()), 'gga_gather_pred_bwd')
         return tuple(out)
 
 
 def gather_pred_tasks(maps, inds, masks):
-    """``gather_pred`` of every task in one launch: ``maps[t]`` = (reg, height, dim, rot) -> T preds [B,K,8]."""
+    """cat(reg,height,dim,rot) gathered at ``ind`` (head:657-676) for every task in one launch: ``maps[t]`` = (reg, height,
+    dim, rot) -> T preds [B,K,8]."""
     args = []
     for m, ind, mask in zip(maps, inds, masks):
         args += [*m, ind.contiguous(), mask.contiguous()]
-    return _GatherPredTasks.apply(*args)
+    return _GatherPred.apply(*args)
+
+
+def gather_pred(reg, height, dim, rot, ind, mask):
+    """``gather_pred_tasks`` of one task -> pred [B,K,8]."""
+    return gather_pred_tasks([(reg, height, dim, rot)], [ind], [mask])[0]
 
 
 # ----------------------------------------------------------------------------- a10-a13
@@ -686,40 +627,6 @@ def _build_loss_params(B, K, train_cfg, l1_loss_weight, w_bpl, w_srl, w_pal):
     return prm
 
 
-class _BoxLosses(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, ind, mask, anno, l2i, bmask, ibp_xy, ibp_off, ibp_slot, prm):
-        _need_cuda(pred, ind, mask, anno, l2i, bmask)
-        B, K = prm.B, prm.K
-        dev = pred.device
-        L = _lib.lib()
-        losses = torch.empty(5, dtype=torch.float32, device=dev)
-        flat = torch.empty(B * K * (5 * 8 + 12), dtype=torch.float32, device=dev)      # one allocation: the entry point clears both with one memset
-        grad_pred, box_out = flat[:5 * B * K * 8].view(5, B, K, 8), flat[5 * B * K * 8:].view(B, K, 12)
-        ws = _workspace('box', L.gga_box_losses_workspace_bytes(B, K), dev)
-        n_obj = 0 if ibp_slot is None else int(ibp_slot.shape[0])
-        pred = pred.contiguous()
-        check(L.gga_box_losses_fwd(_p(pred), _p(ind), _p(mask), _p(anno), _p(l2i), _p(bmask),
-                                   _p(ibp_xy), _p(ibp_off), _p(ibp_slot), n_obj, C.byref(prm), _p(losses),
-                                   _p(box_out), _p(grad_pred), _p(ws), ws.numel(), _stream()),
-              'gga_box_losses_fwd')
-        ctx.save_for_backward(grad_pred)
-        ctx.geom = (B, K)
-        ctx.mark_non_differentiable(box_out)
-        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
-        return losses, box_out
-
-    @staticmethod
-    def backward(ctx, g_losses, _g_box):
-        (grad_pred,) = ctx.saved_tensors
-        B, K = ctx.geom
-        out = torch.empty((B, K, 8), dtype=torch.float32, device=grad_pred.device)
-        g_losses = g_losses.contiguous().float()
-        check(_lib.lib().gga_box_losses_bwd(_p(grad_pred), _p(g_losses), B, K, _p(out),
-                                            _stream()), 'gga_box_losses_bwd')
-        return (out,) + (None,) * 9
-
-
 _ZERO_SCALAR = {}
 
 
@@ -731,35 +638,11 @@ def _zero_scalar(dev):
 
 
 class _BoxLossTerms(torch.autograd.Function):
-    """_BoxLosses with the five terms as five scalar outputs: a head that puts two of them into the total loss and logs the
-    other three gets no UnbindBackward (a zero fill per unused term and a stack, every step and task) - the terms nobody
-    differentiates arrive here as None and the gradient vector is ONE stack over a cached zero."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        losses, box_out = _BoxLosses.forward(ctx, *args)
-        return (*losses.unbind(0), box_out)
-
-    @staticmethod
-    def backward(ctx, g0, g1, g2, g3, g4, _g_box):
-        gs = (g0, g1, g2, g3, g4)
-        if all(g is None for g in gs):
-            return (None,) * 10
-        z = _zero_scalar(ctx.saved_tensors[0].device)
-        g_losses = torch.stack([z if g is None else g.float().reshape(()) for g in gs])
-        return _BoxLosses.backward(ctx, g_losses, None)
-
-
-def box_loss_terms(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot, prm):
-    """``box_losses`` with the losses as a tuple of five scalars (bpl, srl, pal_min, pal_x, pal_y) instead of one [5] tensor."""
-    out = _BoxLossTerms.apply(pred, ind.contiguous(), mask.contiguous(), anno_box.contiguous(), lidar2img.contiguous(),
-                              bound_mask.contiguous(), ibp_xy, ibp_offsets, ibp_slot, prm)
-    return out[:5], out[5]
-
-
-class _BoxLossTermsTasks(torch.autograd.Function):
-    """_BoxLossTerms for all tasks of a head (one ``prm``): one launch per kernel. Inputs: per task the nine tensors of
-    ``box_loss_terms``; outputs: per task its five scalar terms, then the T ``box_out``."""
+    """The GGA losses of all tasks of a head (one ``prm``): one launch per kernel. Inputs: per task the nine tensors of
+    ``box_loss_terms``; outputs: per task its five terms as five scalars, then the T ``box_out``. Scalars, not one [5] tensor: a
+    head that puts two of them into the total loss and logs the other three gets no UnbindBackward (a zero fill per unused term
+    and a stack, every step and task) - the terms nobody differentiates arrive in backward as None and the gradient vector is
+    ONE stack over a cached zero."""
 
     @staticmethod
     def forward(ctx, prm, *args):
@@ -771,7 +654,7 @@ class _BoxLossTermsTasks(torch.autograd.Function):
         dev = args[0].device
         losses = torch.empty((T, 5), dtype=torch.float32, device=dev)
         flat = torch.empty((T, n * (5 * 8 + 12)), dtype=torch.float32, device=dev)      # one allocation: the entry point clears it with one memset
-        ws = _workspace('box', L.gga_box_losses_workspace_bytes_tasks(B, K, T), dev)
+        ws = _workspace('box', L.gga_box_losses_workspace_bytes(B, K, T), dev)
         tb = _task_table(T)
         keep, grads, boxes = [], [], []
         for t in range(T):
@@ -785,7 +668,7 @@ class _BoxLossTermsTasks(torch.autograd.Function):
             e.ibp_xy, e.ibp_offsets, e.ibp_slot = _p(xy), _p(off), _p(slot)
             e.n_ibp_obj = 0 if slot is None else int(slot.shape[0])
             e.losses, e.box_out, e.term_grads = losses.data_ptr() + 20 * t, _p(boxes[t]), _p(grads[t])
-        check(L.gga_box_losses_fwd_tasks(C.byref(tb), C.byref(prm), _p(ws), ws.numel(), _stream()), 'gga_box_losses_fwd_tasks')
+        check(L.gga_box_losses_fwd(C.byref(tb), C.byref(prm), _p(ws), ws.numel(), _stream()), 'gga_box_losses_fwd')
         ctx.save_for_backward(flat)
         ctx.geom = (T, B, K)
         ctx.mark_non_differentiable(*boxes)
@@ -807,7 +690,7 @@ class _BoxLossTermsTasks(torch.autograd.Function):
         for t in range(T):
             e = tb.task[t]
             e.term_grads, e.grad_losses, e.grad_pred = _p(flat[t]), g_losses.data_ptr() + 20 * t, _p(out[t])
-        check(_lib.lib().gga_box_losses_bwd_tasks(C.byref(tb), B, K, _stream()), 'gga_box_losses_bwd_tasks')
+        check(_lib.lib().gga_box_losses_bwd(C.byref(tb), B, K, _stream()), 'gga_box_losses_bwd')
         res = [None]
         for t in range(T):
             res += [out[t]] + [None] * 8
@@ -815,21 +698,27 @@ class _BoxLossTermsTasks(torch.autograd.Function):
 
 
 def box_loss_terms_tasks(tasks, prm):
-    """``box_loss_terms`` of every task in one launch per kernel. ``tasks[t]`` = (pred, ind, mask, anno_box, lidar2img,
-    bound_mask, ibp_xy, ibp_offsets, ibp_slot) -> (T tuples of the five scalar terms, T box_out)."""
+    """The GGA losses of every task in one launch per kernel. ``tasks[t]`` = (pred, ind, mask, anno_box, lidar2img, bound_mask,
+    ibp_xy, ibp_offsets, ibp_slot) -> (T tuples of the five scalar terms (bpl, srl, pal_min, pal_x, pal_y - the final dict
+    values), T ``box_out [B,K,12]`` (rot, l, w, box2d[4], X, Y, p2c_min/x/y))."""
     args = []
     for pred, ind, mask, anno, l2i, bmask, xy, off, slot in tasks:
         args += [pred, ind.contiguous(), mask.contiguous(), anno.contiguous(), l2i.contiguous(), bmask.contiguous(), xy, off, slot]
     T = len(tasks)
-    out = _BoxLossTermsTasks.apply(prm, *args)
+    out = _BoxLossTerms.apply(prm, *args)
     return [out[5 * t:5 * t + 5] for t in range(T)], out[5 * T:]
 
 
+def box_loss_terms(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot, prm):
+    """``box_loss_terms_tasks`` of one task -> (the five scalar terms, ``box_out``)."""
+    terms, box_out = box_loss_terms_tasks([(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot)], prm)
+    return terms[0], box_out[0]
+
+
 def box_losses(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot, prm):
-    """GGA losses of one task. Returns ``losses [5]`` (bpl, srl, pal_min, pal_x, pal_y — the
-    final dict values) and ``box_out [B,K,12]`` (rot, l, w, box2d[4], X, Y, p2c_min/x/y)."""
-    return _BoxLosses.apply(pred, ind.contiguous(), mask.contiguous(), anno_box.contiguous(),
-                            lidar2img.contiguous(), bound_mask.contiguous(), ibp_xy, ibp_offsets, ibp_slot, prm)
+    """``box_loss_terms`` with the five terms stacked -> (``losses [5]``, ``box_out``)."""
+    terms, box_out = box_loss_terms(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_offsets, ibp_slot, prm)
+    return torch.stack(terms), box_out
 
 
 # ----------------------------------------------------------------------------- fused BN (+res) (+ReLU)

@@ -728,9 +728,11 @@ int gga_heatmap_splat(float* heatmap, int n_maps, int H, int W, const int32_t* o
 /* A CenterHead computes the same losses for every task (class group), on     */
 /* maps of one size. Each loss kernel takes this table BY VALUE and picks its */
 /* task from blockIdx.y, so a stage costs one launch whatever the number of   */
-/* tasks. An entry carries the device pointers that stage's per-task entry    */
-/* point takes (same shapes, documented there) and the two sizes that differ  */
-/* between tasks; a stage reads only its own fields, the others may stay null.*/
+/* tasks, and every task's result is bit for bit what a table holding that    */
+/* task alone gives. An entry carries one task's device pointers (shapes at   */
+/* the fields, semantics at the stage that uses them) and the two sizes that  */
+/* differ between tasks; a stage reads only its own fields, the others may    */
+/* stay null. B, K, H, W are common to the tasks of a table.                  */
 /* ------------------------------------------------------------------------- */
 #define GGA_MAX_TASKS 8
 typedef struct {
@@ -742,16 +744,18 @@ typedef struct {
     float* focal_out;
     const float* focal_grad;
     float* grad_logits;
-    /* gather: the four maps and their gradients */
+    /* gather: reg [B,2,H,W], height [B,1,H,W], dim [B,3,H,W], rot [B,2,H,W] and their gradients (same shapes) */
     const float *reg, *height, *dim, *rot;
     float *g_reg, *g_height, *g_dim, *g_rot;
-    /* gather and box losses: ind [B,K] i64, mask [B,K] u8; pred [B,K,8] (written by the gather, read by the losses);
-     * grad_pred [B,K,8] (written by the losses' backward, read by the gather's) */
+    /* gather and box losses: ind [B,K] i64, mask [B,K] u8; pred [B,K,8] = (dx, dy, z, log l, log w, log h, sin, cos)
+     * (written by the gather, read by the losses); grad_pred [B,K,8] (written by the losses' backward, read by the gather's) */
     const int64_t* ind;
     const uint8_t* mask;
     float* pred;
     float* grad_pred;
-    /* box losses: inputs and outputs of gga_box_losses_fwd (term_grads is its grad_pred [5,B,K,8]); grad_losses [5] */
+    /* box losses, inputs: anno_box [B,K,5] (x1, y1, x2, y2, srl); lidar2img [B,K,4,4]; bound_mask [B,K,4];
+     * ibp_xy [n_pts,2] in-box points of every object (xy, packed); ibp_offsets [n_ibp_obj + 1] point ranges;
+     * ibp_slot [n_ibp_obj] = b * K + k (the three may be null when n_ibp_obj == 0) */
     const float* anno_box;
     const float* lidar2img;
     const uint8_t* bound_mask;
@@ -759,6 +763,8 @@ typedef struct {
     const int32_t* ibp_offsets;
     const int32_t* ibp_slot;
     int32_t n_ibp_obj;
+    /* box losses, outputs of the forward: losses [GGA_L_NUM], box_out [B,K,12], term_grads [GGA_L_NUM,B,K,8] = d losses[t] /
+     * d pred per term (see gga_box_losses_fwd); the backward reads term_grads and grad_losses [GGA_L_NUM] = d / d losses */
     float* losses;
     float* box_out;
     float* term_grads;
@@ -766,7 +772,7 @@ typedef struct {
 } gga_task;
 
 typedef struct {
-    int32_t n_tasks;                      /* 1 .. GGA_MAX_TASKS */
+    int32_t n_tasks;                      /* 1 .. GGA_MAX_TASKS, else GGA_ERR_INVALID_ARG */
     gga_task task[GGA_MAX_TASKS];
 } gga_task_table;
 
@@ -775,22 +781,15 @@ typedef struct {
 /* Replaces mmdet3d/models/utils/clip_sigmoid.py:16 + mmdet GaussianFocalLoss */
 /* + the host-syncing num_pos.item() of centerpoint_head_gga.py:650-655.      */
 /* ------------------------------------------------------------------------- */
-size_t gga_focal_loss_workspace_bytes(int64_t n);
-/* out[0] = scale * sum(loss) / (max(num_pos,1) + eps_f32); out[1] = num_pos. */
-int gga_focal_loss_fwd(const float* logits, const float* target, int64_t n, float alpha,
-                       float gamma, float scale, float* out, void* workspace,
+/* Every task of the table in one launch per kernel. Workspace: n_max = the largest n_heat of the table.
+ * forward:  focal_out[0] = scale * sum(loss) / (max(num_pos,1) + eps_f32); focal_out[1] = num_pos.
+ * backward: grad_logits[i] = (*focal_grad) * scale * dloss_i/dlogit_i / (max(num_pos,1)+eps); focal_out is what the
+ *           forward call wrote (num_pos is read from focal_out[1]).
+ * logits, target and grad_logits must be 16-byte aligned. */
+size_t gga_focal_loss_workspace_bytes(int64_t n_max, int n_tasks);
+int gga_focal_loss_fwd(const gga_task_table* tasks, float alpha, float gamma, float scale, void* workspace,
                        size_t workspace_bytes, void* stream);
-/* grad_logits[i] = (*grad_out) * scale * dloss_i/dlogit_i / (max(num_pos,1)+eps);
- * fwd_out is the `out` of the forward call (num_pos is read from fwd_out[1]). */
-int gga_focal_loss_bwd(const float* logits, const float* target, int64_t n, float alpha,
-                       float gamma, float scale, const float* fwd_out, const float* grad_out,
-                       float* grad_logits, void* stream);
-/* The same for every task of the table in one launch per kernel (the per-task calls above are these with one entry: every
- * task's result is bit for bit what its own call gives). Workspace: n_max = the largest n_heat of the table. */
-size_t gga_focal_loss_workspace_bytes_tasks(int64_t n_max, int n_tasks);
-int gga_focal_loss_fwd_tasks(const gga_task_table* tasks, float alpha, float gamma, float scale, void* workspace,
-                             size_t workspace_bytes, void* stream);
-int gga_focal_loss_bwd_tasks(const gga_task_table* tasks, float alpha, float gamma, float scale, void* stream);
+int gga_focal_loss_bwd(const gga_task_table* tasks, float alpha, float gamma, float scale, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a9. Gather the 8 regression channels at the object cells, and its backward */
@@ -798,23 +797,17 @@ int gga_focal_loss_bwd_tasks(const gga_task_table* tasks, float alpha, float gam
 /* Replaces cat + permute + contiguous + gather of                            */
 /* centerpoint_head_gga.py:141-164,657-676.                                   */
 /* ------------------------------------------------------------------------- */
-/* reg [B,2,H,W] height [B,1,H,W] dim [B,3,H,W] rot [B,2,H,W] -> pred [B,K,8] */
-int gga_gather_pred_fwd(const float* reg, const float* height, const float* dim, const float* rot,
-                        const int64_t* ind, int B, int K, int H, int W, float* pred, void* stream);
-/* The four grad maps are zero-filled here, then grad_pred is scatter-added;
- * slots with mask == 0 are skipped (their weight is zero in every loss term). */
-int gga_gather_pred_bwd(const float* grad_pred, const int64_t* ind, const uint8_t* mask, int B,
-                        int K, int H, int W, float* g_reg, float* g_height, float* g_dim,
-                        float* g_rot, void* stream);
-/* All tasks of the table in one launch (B, K, H, W are the tasks' common sizes). The backward keeps a frame's K slots in
- * LDS: K <= 512, else GGA_ERR_INVALID_ARG (this holds for the per-task call too). It clears every gradient map with ONE
- * memset when each task's four maps lie one behind the other (reg, height, dim, rot) and the tasks one behind the other,
- * else with one memset per task or map. */
-int gga_gather_pred_fwd_tasks(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
-int gga_gather_pred_bwd_tasks(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
+/* All tasks of the table in one launch (B, K, H, W are the tasks' common sizes).
+ * forward:  reg, height, dim, rot gathered at ind -> pred [B,K,8].
+ * backward: the four gradient maps are zero-filled here, then grad_pred is scatter-added; slots with mask == 0 are skipped
+ *           (their weight is zero in every loss term). It keeps a frame's K slots in LDS: K <= 512, else
+ *           GGA_ERR_INVALID_ARG. It clears every gradient map with ONE memset when each task's four maps lie one behind the
+ *           other (reg, height, dim, rot) and the tasks one behind the other, else with one memset per task or map. */
+int gga_gather_pred_fwd(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
+int gga_gather_pred_bwd(const gga_task_table* tasks, int B, int K, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* a10-a13. The GGA geometry-aware losses for one task, forward + analytic    */
+/* a10-a13. The GGA geometry-aware losses of a task, forward + analytic       */
 /* gradient in one pass: rotation, decode, 8 corners, lidar2img projection,   */
 /* 2D box (BPL), semantic ratio (SRL), point-to-box alignment (PAL).          */
 /* Replaces centerpoint_head_gga.py:167-341 (GGA_calculate_rotation,          */
@@ -836,38 +829,20 @@ typedef struct {
 enum { GGA_L_BPL = 0, GGA_L_SRL = 1, GGA_L_PAL_MIN = 2, GGA_L_PAL_X = 3, GGA_L_PAL_Y = 4,
        GGA_L_NUM = 5 };
 
-size_t gga_box_losses_workspace_bytes(int B, int K);
-
-/*
- * pred        [B,K,8] f32 (dx, dy, z, log l, log w, log h, sin, cos)
- * ind         [B,K] i64; mask [B,K] u8; anno_box [B,K,5] f32 (x1,y1,x2,y2,srl)
- * lidar2img   [B,K,4,4] f32; bound_mask [B,K,4] u8
- * ibp_xy      [n_pts,2] f32 in-box points of every object (xy, packed)
- * ibp_offsets [n_ibp_obj + 1] i32 point ranges; ibp_slot [n_ibp_obj] i32 = b*K + k
- * outputs
+/* All tasks of the table in one launch per kernel (box_slot_kernel excepted: one launch per task, see head_loss.hip); prm
+ * (B, K included) is common to the tasks. Inputs: the task's pred, ind, mask, anno_box, lidar2img, bound_mask and in-box
+ * points (shapes at gga_task). Outputs per task:
  *   losses      [5] f32, final dict values (weights and 1/(num+1e-4+eps) applied)
  *   box_out     [B,K,12] f32: rot, l, w, u_min, v_min, u_max, v_max, X, Y, p2c_min, p2c_x, p2c_y
  *               (intermediates, for parity tests / logging)
- *   grad_pred   [5,B,K,8] f32: d losses[t] / d pred, per term
- */
-int gga_box_losses_fwd(const float* pred, const int64_t* ind, const uint8_t* mask,
-                       const float* anno_box, const float* lidar2img, const uint8_t* bound_mask,
-                       const float* ibp_xy, const int32_t* ibp_offsets, const int32_t* ibp_slot,
-                       int n_ibp_obj, const gga_loss_params* prm, float* losses, float* box_out,
-                       float* grad_pred, void* workspace, size_t workspace_bytes, void* stream);
-
-/* grad_pred_out [B,K,8] = sum_t grad_losses[t] * grad_pred[t] (grad_losses [5] on device). */
-int gga_box_losses_bwd(const float* grad_pred, const float* grad_losses, int B, int K,
-                       float* grad_pred_out, void* stream);
-
-/* All tasks of the table in one launch per kernel (box_slot_kernel excepted: one launch per task, see head_loss.hip); prm
- * (B, K included) is common to the tasks. term_grads and box_out are cleared with ONE memset when each task's box_out lies
- * behind its term_grads and the tasks one behind the other; a second one clears the workspace. */
-size_t gga_box_losses_workspace_bytes_tasks(int B, int K, int n_tasks);
-int gga_box_losses_fwd_tasks(const gga_task_table* tasks, const gga_loss_params* prm, void* workspace,
-                             size_t workspace_bytes, void* stream);
-/* task.grad_pred [B,K,8] = sum_t task.grad_losses[t] * task.term_grads[t] */
-int gga_box_losses_bwd_tasks(const gga_task_table* tasks, int B, int K, void* stream);
+ *   term_grads  [5,B,K,8] f32: d losses[t] / d pred, per term
+ * term_grads and box_out are cleared with ONE memset when each task's box_out lies behind its term_grads and the tasks one
+ * behind the other (else with one memset per task or buffer); a second one clears the workspace. */
+size_t gga_box_losses_workspace_bytes(int B, int K, int n_tasks);
+int gga_box_losses_fwd(const gga_task_table* tasks, const gga_loss_params* prm, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* task.grad_pred [B,K,8] = sum_t task.grad_losses[t] * task.term_grads[t] (grad_losses [5] on the device). */
+int gga_box_losses_bwd(const gga_task_table* tasks, int B, int K, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SURVEY.md §8(f) rank 1 — inference / pseudo-label post-processing.        */

@@ -57,6 +57,33 @@ def test_argument_validation_without_gpu():
     assert rc == -1 and b'multiple of 4' in L.gga_last_error()
 
 
+def test_loss_stages_validate_their_task_table_without_gpu():
+    # the head-loss entry points take a gga_task_table: a null table and a task count outside 1..GGA_MAX_TASKS are rejected
+    # before any HIP call, and the message names the entry point (the two workspace-size functions take no table: they are
+    # plain arithmetic in n_tasks)
+    import ctypes as C
+    L = _lib.lib()
+    prm = _lib.LossParams()
+    calls = {
+        'gga_focal_loss_fwd': lambda tb: L.gga_focal_loss_fwd(tb, 0.0, 4.0, 1.0, None, 0, None),
+        'gga_focal_loss_bwd': lambda tb: L.gga_focal_loss_bwd(tb, 0.0, 4.0, 1.0, None),
+        'gga_gather_pred_fwd': lambda tb: L.gga_gather_pred_fwd(tb, 2, 12, 20, 72, None),
+        'gga_gather_pred_bwd': lambda tb: L.gga_gather_pred_bwd(tb, 2, 12, 20, 72, None),
+        'gga_box_losses_fwd': lambda tb: L.gga_box_losses_fwd(tb, C.byref(prm), None, 0, None),
+        'gga_box_losses_bwd': lambda tb: L.gga_box_losses_bwd(tb, 2, 12, None),
+    }
+    for name, call in calls.items():
+        assert call(None) == -1
+        assert L.gga_last_error().decode().startswith(name + ': null task table'), name
+        for n in (0, _lib.MAX_TASKS + 1):
+            tb = _lib.TaskTable()
+            tb.n_tasks = n
+            assert call(C.byref(tb)) == -1
+            assert L.gga_last_error().decode().startswith(f'{name}: n_tasks {n} not in 1..{_lib.MAX_TASKS}'), (name, n)
+    assert L.gga_focal_loss_workspace_bytes(4096, 3) == 3 * L.gga_focal_loss_workspace_bytes(4096, 1) > 0
+    assert L.gga_box_losses_workspace_bytes(2, 12, 3) == 3 * L.gga_box_losses_workspace_bytes(2, 12, 1) == 3 * 5 * 2 * 12 * 4
+
+
 def test_product_refuses_cpu_tensors():
     import torch
     from gga_amd import functional as F

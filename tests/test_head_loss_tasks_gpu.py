@@ -1,7 +1,8 @@
 """The loss kernels over all tasks of a head in one launch (F.gaussian_focal_loss_tasks, F.gather_pred_tasks,
-F.box_loss_terms_tasks: gga_*_tasks of include/gga_hip.h) against one call per task on the same inputs: every loss, every
-intermediate and every gradient bit for bit (torch.equal). What a task's call computes is checked against float64 in
-tests/test_head_loss_gpu.py - its per-task entry points run the same kernels with a table of one entry.
+F.box_loss_terms_tasks: the gga_task_table entry points of include/gga_hip.h) against one call per task on the same inputs:
+every loss, every intermediate and every gradient bit for bit (torch.equal) - a task's bits do not depend on which other tasks
+share its grid. What a task's call computes is checked against float64 in tests/test_head_loss_gpu.py - F.gaussian_focal_loss,
+F.gather_pred and F.box_loss_terms are the one-task calls of the same autograd Functions.
 
 Shapes: B = 2, K = 12, H x W = 20 x 72 (two 8 x 32 tile rows and a partial third, two tile columns and a partial third),
 3 tasks with 1, 2 and 1 heat-map classes."""
@@ -34,8 +35,9 @@ def up_box(t):
     return [1.0 + 0.1 * t, 0.7, 1.3 - 0.2 * t, 0.45, 1.9]
 
 
-def make_task(seed, classes=1, live=(4, 5), cells=None, counts=(0, 1, 300)):
-    """One task's inputs on the CPU. live[b]: live slots of frame b (the first ones, as the target assignment fills them);
+def make_task(seed, classes=1, live=(4, 5), cells=None, counts=(0, 1, 300), H=H, W=W):
+    """One task's inputs on the CPU (maps of H x W, the module's size unless given). live[b]: live slots of frame b (the
+    first ones, as the target assignment fills them);
     cells[b]: ind of the frame's first slots (the rest are drawn); counts: in-box points of the objects, cycled over the live
     slots - every other dead slot gets an entry too (its box_out columns are filled, its losses are not)."""
     rng = np.random.default_rng(seed)
@@ -218,3 +220,41 @@ def test_head_loss_takes_the_batched_path_with_the_same_values(per_task):
     odd = [[dict(p[0])] for p in preds]
     odd[1][0]['reg'] = odd[1][0]['reg'][:, :, :-1]
     assert not CenterHead_GGA._tasks_share_a_launch(odd, [d['ind'] for d in ds])
+
+
+def test_tasks_of_different_map_sizes_go_task_by_task_through_the_head():
+    """Three tasks whose middle one has maps of 19 x 72 instead of 20 x 72 (the same width, so the same fm_w and one ``prm``):
+    CenterHead_GGA.loss_from_targets, unpatched, takes one launch group per task. Its 18 entries and the gradients of all
+    fifteen maps equal F.gaussian_focal_loss / F.gather_pred / F.box_loss_terms called task by task on fresh copies."""
+    tasks = [make_task(21, 1, live=(4, 5)), make_task(22, 2, live=(K, 3), H=H - 1), make_task(23, 1, live=(6, 5))]
+    assert tasks[1]['reg'].shape[2:] == (H - 1, W) and int(tasks[1]['ind'].max()) < (H - 1) * W
+    head = types.SimpleNamespace(train_cfg=CFG, loss_cls=types.SimpleNamespace(alpha=0.0, gamma=4.0, loss_weight=1.0),
+                                 loss_bbox=types.SimpleNamespace(loss_weight=0.25),
+                                 _tasks_share_a_launch=CenterHead_GGA._tasks_share_a_launch)
+    maps = ('heatmap', 'reg', 'height', 'dim', 'rot')
+    ds = [on_device(t) for t in tasks]
+    preds = [[{k: d[k] for k in maps}] for d in ds]
+    assert not CenterHead_GGA._tasks_share_a_launch(preds, [d['ind'] for d in ds])
+    losses = CenterHead_GGA.loss_from_targets(head, preds, [d['target'] for d in ds], [d['anno'] for d in ds],
+                                              [d['ind'] for d in ds], [d['mask'] for d in ds], [d['l2i'] for d in ds],
+                                              [(d['xy'], d['off'], d['slot']) for d in ds], [d['bmask'] for d in ds])
+    sum(v for k, v in losses.items() if 'distance' not in k).backward()
+    # the same, task by task
+    rs = [on_device(t) for t in tasks]
+    prm = F.loss_params(B, K, CFG, l1_loss_weight=0.25)
+    ref = {}
+    for t, d in enumerate(rs):
+        heat, _ = F.gaussian_focal_loss(d['heatmap'], d['target'], **FOCAL)
+        pred = F.gather_pred(d['reg'], d['height'], d['dim'], d['rot'], d['ind'], d['mask'])
+        (bpl, srl, pmin, px, py), _ = F.box_loss_terms(*box_args(d, pred), prm)
+        ref.update({f'task{t}.distancex': px, f'task{t}.distancey': py, f'task{t}.distancemin': pmin,
+                    f'task{t}.loss_heatmap': heat, f'task{t}.loss_bbox': bpl, f'task{t}.loss_ratio': srl})
+    sum(v for k, v in ref.items() if 'distance' not in k).backward()
+    torch.cuda.synchronize()
+    assert len(losses) == 18 and list(losses) == list(ref)
+    for k in ref:
+        assert torch.isfinite(losses[k]) and torch.equal(losses[k], ref[k]), k
+    for t, (d, r) in enumerate(zip(ds, rs)):
+        for k in maps:
+            assert d[k].grad.shape == tasks[t][k].shape and torch.equal(d[k].grad, r[k].grad), (t, k)
+    assert all(float(d['reg'].grad.abs().sum()) > 0 for d in ds)
