@@ -35,6 +35,8 @@
 // plus the tile's origin, and BOTH pixel groups of the next tile are requested a whole tile ahead (16 loads in flight per
 // lane; the waits are counted, see HQ_LOAD). Z is kept compactly (9 * COUT columns, odd stride) for the whole tile, then
 // one thread per output pixel adds its nine taps; a one-channel branch needs one 16-column product instead of two.
+// MAP (gga_head_conv3x3_fwd_tiles): the walk visits only the tiles a byte map calls active and writes nothing else - a tile's
+// values are built from scratch (accumulators and Z per tile), so they do not depend on which tiles were visited before it.
 #define HM_TW 32                                       // forward tile: HP_TR x HM_TW output pixels, halo HP_HR x HM_HW
 #define HM_HW (HM_TW + 2)
 #define HP_TR 13
@@ -43,11 +45,58 @@
 #define HP_NGRP 16
 static_assert((HP_NPIX + 31) / 32 == HP_NGRP, "tile geometry");
 
-template <int COUT, bool AFF>
+// The tiles first, first + stride, ... of a persistent workgroup, restricted to the active ones and in the same order: the
+// activity bytes of 64 of them are fetched with one load per lane and kept as a wave-uniform bit mask, so a step costs a
+// few scalar instructions and memory is touched once per 64 owned tiles (every wave computes the same mask).
+struct HeadTileWalk {
+    const uint8_t* act;
+    int64_t base, stride, n_tiles;
+    unsigned long long mask;
+    __device__ __forceinline__ unsigned long long window(int64_t from) const {
+        const int64_t t = from + (int64_t)(threadIdx.x & 63) * stride;
+        return __ballot(t < n_tiles && act[t] != 0);
+    }
+    __device__ __forceinline__ HeadTileWalk(const uint8_t* a, int64_t first, int64_t s, int64_t n) : act(a), base(first), stride(s), n_tiles(n) {
+        mask = window(base);
+    }
+    // the next active tile, n_tiles when there is none
+    __device__ __forceinline__ int64_t next() {
+        while (mask == 0) {
+            if (base + 64 * stride >= n_tiles) return n_tiles;
+            base += 64 * stride;
+            mask = window(base);
+        }
+        const int k = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        return base + k * stride;
+    }
+};
+
+// Which of a task's maps' forward tiles hold a cell the loss gathers (head_loss.hip gather_pred_kernel reads a regression map
+// at ind[s] for EVERY slot s of [B, K], dead ones - ind = 0 - included, and nowhere else): one thread per slot stores 1 for the
+// tile of its cell into a map the caller zeroed; an index outside the map marks nothing. ind: [n_maps, K].
+__global__ __launch_bounds__(256) void head_cell_tiles_kernel(const int64_t* __restrict__ ind, int64_t n, int K, int H, int W,
+                                                              int tiles_x, int tiles_y, uint8_t* __restrict__ act) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= n) return;
+    const int64_t i = ind[s];
+    if (i < 0 || i >= (int64_t)H * W) return;
+    const int cy = (int)(i / W), cx = (int)(i - (int64_t)cy * W);
+    act[((s / K) * tiles_y + cy / HP_TR) * tiles_x + cx / HM_TW] = 1;
+}
+
+template <int COUT, bool AFF, bool MAP>
 __global__ __launch_bounds__(512, 4) void headconv_fwd16_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, int B, int H, int W,
                                                             int tiles_x, int tiles_y, int n_tiles, int cout_total, int co_base,
-                                                            const float* __restrict__ in_ss, int64_t xs, float* __restrict__ y) {
+                                                            const float* __restrict__ in_ss, int64_t xs, float* __restrict__ y,
+                                                            const uint8_t* __restrict__ act) {
+    if (MAP) {          // (uniform, before any barrier) a workgroup none of whose tiles is active leaves before it loads the weights
+        const int xcd_ = blockIdx.x & 7, chunk_ = (n_tiles + 7) >> 3;
+        const int end_ = min(n_tiles, (xcd_ + 1) * chunk_);
+        HeadTileWalk probe(act, xcd_ * chunk_ + ((int)blockIdx.x >> 3), ((int)gridDim.x + 7 - xcd_) >> 3, end_);
+        if (probe.next() >= end_) return;
+    }
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef float f2 __attribute__((ext_vector_type(2)));
     constexpr int NT = COUT == 1 ? 1 : 2;               // 16-column tiles of Z
@@ -140,15 +189,18 @@ __global__ __launch_bounds__(512, 4) void headconv_fwd16_kernel(const float* __r
     const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, wgs = ((int)gridDim.x + 7 - xcd) >> 3;
     const int chunk = (n_tiles + 7) >> 3;
     const int t_end = min(n_tiles, (xcd + 1) * chunk);
-    int tile = xcd * chunk + wg;
+    // MAP: the workgroup keeps its tiles and visits the active ones among them in that order (the walk is built here, behind
+    // the weight loads: built before them it costs the counted waits, EXPERIMENTS.md 6k - hence the throw-away one above)
+    HeadTileWalk walk(MAP ? act : nullptr, MAP ? xcd * chunk + wg : t_end, wgs, t_end);
+    int tile = MAP ? (int)walk.next() : xcd * chunk + wg;
     if (tile >= t_end) return;
     HQ_LOAD(tile, true, 0)
     HQ_LOAD(tile, true, 1)
-    for (; tile < t_end; tile += wgs) {
+    for (int nxt; tile < t_end; tile = nxt) {
         const int b = tile / per_img;
         const int rem = tile - b * per_img;
         const int y0 = (rem / tiles_x) * HP_TR, x0 = (rem % tiles_x) * HM_TW;
-        const int nxt = tile + wgs;
+        nxt = MAP ? (int)walk.next() : tile + wgs;
         HQ_MMA(0)
         HQ_LOAD(nxt, nxt < t_end, 0)                      // a whole tile ahead (past the end: dummy loads, so that the count holds)
         HQ_MMA(1)
@@ -226,33 +278,6 @@ __global__ __launch_bounds__(256) void head_tile_activity_kernel(const float* __
     const bool any = __ballot(bits != 0) != 0;
     if (lane == 0) act[t] = any ? 1 : 0;
 }
-
-// The tiles first, first + stride, ... of a persistent workgroup, restricted to the active ones and in the same order: the
-// activity bytes of 64 of them are fetched with one load per lane and kept as a wave-uniform bit mask, so a step costs a
-// few scalar instructions and memory is touched once per 64 owned tiles (every wave computes the same mask).
-struct HeadTileWalk {
-    const uint8_t* act;
-    int64_t base, stride, n_tiles;
-    unsigned long long mask;
-    __device__ __forceinline__ unsigned long long window(int64_t from) const {
-        const int64_t t = from + (int64_t)(threadIdx.x & 63) * stride;
-        return __ballot(t < n_tiles && act[t] != 0);
-    }
-    __device__ __forceinline__ HeadTileWalk(const uint8_t* a, int64_t first, int64_t s, int64_t n) : act(a), base(first), stride(s), n_tiles(n) {
-        mask = window(base);
-    }
-    // the next active tile, n_tiles when there is none
-    __device__ __forceinline__ int64_t next() {
-        while (mask == 0) {
-            if (base + 64 * stride >= n_tiles) return n_tiles;
-            base += 64 * stride;
-            mask = window(base);
-        }
-        const int k = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        return base + k * stride;
-    }
-};
 
 template <int COUT, bool AFF, bool MAP>
 __global__ __launch_bounds__(512, 4) void headconv_wgrad16_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -466,18 +491,21 @@ static int headconv_limits(const char* fn, int H, int W, int64_t xs, int rows, i
     return GGA_OK;
 }
 
-extern "C" int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
-                                    const float* bias, int B, int H, int W, int cin, int cout, float* y, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = headconv_check("gga_head_conv3x3_fwd", B, H, W, cin, cout)) return rc;
-    GGA_REQUIRE(x && weight && y, "gga_head_conv3x3_fwd: null pointer argument");
-    if (int rc = headconv_stride("gga_head_conv3x3_fwd", x, x_pixel_stride)) return rc;
+// tile_act: nullptr = every tile, else one byte per HP_TR x HM_TW tile (gga_head_cell_tiles; one map serves both launches of cout = 4)
+static int headconv_fwd_run(const char* fn, const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
+                            const float* bias, int B, int H, int W, int cin, int cout, const uint8_t* tile_act, bool tiled,
+                            float* y, hipStream_t stream) {
+    if (int rc = headconv_check(fn, B, H, W, cin, cout)) return rc;
+    GGA_REQUIRE(x && weight && y, "%s: null pointer argument", fn);
+    GGA_REQUIRE(!tiled || tile_act, "%s: null tile map", fn);
+    if (int rc = headconv_stride(fn, x, x_pixel_stride)) return rc;
     const int tx = (W + HM_TW - 1) / HM_TW, ty = (H + HP_TR - 1) / HP_TR;
     const int64_t n_tiles = (int64_t)B * tx * ty;
-    if (int rc = headconv_limits("gga_head_conv3x3_fwd", H, W, x_pixel_stride, HP_HR + 1, n_tiles)) return rc;      // (halo rows -1 .. 13: offsets span up to 16 rows)
+    if (int rc = headconv_limits(fn, H, W, x_pixel_stride, HP_HR + 1, n_tiles)) return rc;      // (halo rows -1 .. 13: offsets span up to 16 rows)
     const dim3 grid((unsigned)(n_tiles < HC_BLOCKS ? n_tiles : HC_BLOCKS)), block(512);
-#define HC_G(CO, BASE, AF) hipLaunchKernelGGL((headconv_fwd16_kernel<CO, AF>), grid, block, 0, stream, x, weight, bias, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, y)
-#define HC_F(CO, BASE) { if (in_scale_shift) HC_G(CO, BASE, true); else HC_G(CO, BASE, false); }
+#define HC_G(CO, BASE, AF, MP) hipLaunchKernelGGL((headconv_fwd16_kernel<CO, AF, MP>), grid, block, 0, stream, x, weight, bias, B, H, W, tx, ty, (int)n_tiles, cout, BASE, in_scale_shift, x_pixel_stride, y, tile_act)
+#define HC_A(CO, BASE, AF) { if (tile_act) HC_G(CO, BASE, AF, true); else HC_G(CO, BASE, AF, false); }
+#define HC_F(CO, BASE) { if (in_scale_shift) HC_A(CO, BASE, true) else HC_A(CO, BASE, false) }
     switch (cout) {
         case 1: HC_F(1, 0); break;
         case 2: HC_F(2, 0); break;
@@ -485,8 +513,39 @@ extern "C" int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, cons
         default: HC_F(2, 0); HC_F(2, 2); break;      // 9*4 columns do not fit two 16-wide tiles
     }
 #undef HC_F
+#undef HC_A
 #undef HC_G
     GGA_CHECK_LAUNCH("headconv_fwd16_kernel");
+    return GGA_OK;
+}
+
+extern "C" int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
+                                    const float* bias, int B, int H, int W, int cin, int cout, float* y, void* stream) {
+    return headconv_fwd_run("gga_head_conv3x3_fwd", x, x_pixel_stride, in_scale_shift, weight, bias, B, H, W, cin, cout, nullptr, false,
+                            y, (hipStream_t)stream);
+}
+
+extern "C" int gga_head_conv3x3_fwd_tiles(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
+                                          const float* bias, int B, int H, int W, int cin, int cout, const uint8_t* tile_active,
+                                          float* y, void* stream) {
+    return headconv_fwd_run("gga_head_conv3x3_fwd_tiles", x, x_pixel_stride, in_scale_shift, weight, bias, B, H, W, cin, cout,
+                            tile_active, true, y, (hipStream_t)stream);
+}
+
+extern "C" int64_t gga_head_cell_tiles_count(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return 0;
+    return (int64_t)B * ((H + HP_TR - 1) / HP_TR) * ((W + HM_TW - 1) / HM_TW);
+}
+
+extern "C" int gga_head_cell_tiles(const int64_t* ind, int n_maps, int K, int H, int W, uint8_t* tile_active, void* stream) {
+    GGA_REQUIRE(n_maps >= 1 && K >= 1 && H >= 1 && W >= 1, "gga_head_cell_tiles: bad sizes (n_maps=%d K=%d H=%d W=%d)", n_maps, K, H, W);
+    GGA_REQUIRE(ind, "gga_head_cell_tiles: null index pointer");
+    GGA_REQUIRE(tile_active, "gga_head_cell_tiles: null tile map");
+    const int64_t n = (int64_t)n_maps * K;
+    GGA_REQUIRE((n + 255) / 256 < 2147483647ll, "gga_head_cell_tiles: too many slots (%lld)", (long long)n);
+    hipLaunchKernelGGL(head_cell_tiles_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ind, n, K, H, W,
+                       (W + HM_TW - 1) / HM_TW, (H + HP_TR - 1) / HP_TR, tile_active);
+    GGA_CHECK_LAUNCH("head_cell_tiles_kernel");
     return GGA_OK;
 }
 

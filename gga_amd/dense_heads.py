@@ -29,6 +29,12 @@ from .registry import HEADS, build_bbox_coder, build_head, build_loss
 SRL_PRIORS = ((1.35, 0.48), (3.60, 0.68), (2.40, 0.28))
 
 
+# Training forward of the regression maps (reg / height / dim / rot) on the tiles that hold a gathered cell only: the detector
+# builds the targets first and hands the gather indices to the head (``CenterHead_GGA.forward(feats, cells=...)``).
+# GGA_HEAD_FWD_CELLS=0: the head runs first and every map is computed whole, the call order and launches before this switch.
+FWD_CELLS = os.environ.get('GGA_HEAD_FWD_CELLS', '1') != '0'
+
+
 def multi_apply(func, *args, **kwargs):
     """mmdet.core.multi_apply: map ``func`` over the zipped args, transpose the results."""
     from functools import partial
@@ -159,7 +165,7 @@ class CenterHead_GGA(nn.Module):
                                           f"reduction='mean' (configs/gga/gga_kitti_config.py:59-60)")
 
     # ------------------------------------------------------------------ forward
-    def forward_single(self, x):
+    def forward_single(self, x, cells=None):
         x = self.shared_conv(x)
         # training on the device: every branch of every task reads this one map - run them as one autograd node
         # (functional._HeadBranches) so that its gradient is produced once instead of summed branch by branch
@@ -175,8 +181,19 @@ class CenterHead_GGA(nn.Module):
         n_all = sum(len(getattr(task, 'heads', ())) for task in self.task_heads)
         # (the regression outputs are read through gather_pred at object cells only: their gradient is zero almost everywhere;
         # the heat-map's, from the focal loss, is dense)
-        outs = (F.head_branches(x, branches, sparse_grad=[head != 'heatmap' for _, head in keys])
-                if branches and len(branches) == n_all and self.training else None)
+        fused = bool(branches) and len(branches) == n_all and self.training
+        tile_maps = None
+        if fused and cells is not None and x.is_cuda:
+            # the loss reads a regression map at cells[task] only (gather_pred): one launch marks the tiles of all tasks, and
+            # those branches compute nothing else; the heat-map stays dense (the focal loss reads all of it)
+            if len(cells) != len(self.task_heads):
+                raise ValueError(f'CenterHead_GGA: cells for {len(cells)} tasks, the head has {len(self.task_heads)}')
+            if any(c.shape[0] != x.shape[0] for c in cells):
+                raise ValueError('CenterHead_GGA: cells must be [B, K] per task, with the batch size of the feature map')
+            maps = F.head_cell_tiles(list(cells), x.shape[2], x.shape[3])
+            tile_maps = [None if head == 'heatmap' else maps[ti] for ti, head in keys]
+        outs = (F.head_branches(x, branches, sparse_grad=[head != 'heatmap' for _, head in keys], tile_maps=tile_maps)
+                if fused else None)
         if outs is None:
             return [task(x) for task in self.task_heads]
         ret = [dict() for _ in self.task_heads]
@@ -184,8 +201,15 @@ class CenterHead_GGA(nn.Module):
             ret[ti][head] = y
         return ret
 
-    def forward(self, feats):
-        return multi_apply(self.forward_single, feats)
+    def forward(self, feats, cells=None):
+        """``cells``: None, or per task the ``[B, K]`` gather indices of ``get_targets`` (its ``inds``). In training on the
+        fused-branch path the ``reg`` / ``height`` / ``dim`` / ``rot`` maps are then computed on the tiles that hold one of
+        those cells and are zero elsewhere: THEY ARE VALID ONLY AT THE GATHERED CELLS, which is all ``loss_from_targets``
+        reads of them. ``heatmap`` is always whole. With ``cells=None``, in eval mode, or where the branches do not qualify
+        for the fused path every map is computed whole."""
+        if cells is None:
+            return multi_apply(self.forward_single, feats)
+        return multi_apply(self.forward_single, feats, cells=cells)
 
     # ------------------------------------------------------------------ targets
     def _feature_map_size(self):

@@ -11,6 +11,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from . import dense_heads
 from .registry import (DETECTORS, build_backbone, build_head, build_middle_encoder, build_neck,
                        build_voxel_encoder)
 from .voxel_layer import Voxelization
@@ -179,7 +180,15 @@ class MVXTwoStageDetector_GGA(nn.Module):
     def forward_pts_train(self, pts_feats, gt_bboxes_3d, gt_labels_3d, GGA_boxes_img, GGA_lidar2img,
                           GGA_init_pseudo_labels, GGA_bdry_masks, GGA_in_box_points, img_metas,
                           gt_bboxes_ignore=None):
-        outs = self.pts_bbox_head(pts_feats)
+        head = self.pts_bbox_head
+        if dense_heads.FWD_CELLS and isinstance(head, dense_heads.CenterHead_GGA):
+            # targets first (they depend on the ground truth alone; the SRL draws come from the CPU generator in the same
+            # order), so that the head computes its regression maps only where the loss gathers them
+            targets = head.get_targets(gt_bboxes_3d, gt_labels_3d, GGA_boxes_img, GGA_lidar2img, GGA_init_pseudo_labels,
+                                       GGA_bdry_masks, GGA_in_box_points, img_metas, device=pts_feats[0].device)
+            outs = head(pts_feats, cells=targets[2])
+            return head.loss_from_targets(outs, *targets)
+        outs = head(pts_feats)
         return self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs, GGA_boxes_img, GGA_lidar2img,
                                        GGA_init_pseudo_labels, GGA_bdry_masks, GGA_in_box_points, img_metas)
 

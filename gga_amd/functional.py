@@ -1142,13 +1142,36 @@ def _branch_streams(device, n):
     return [torch.cuda.current_stream(device)] + pool[:k - 1]
 
 
+def head_cell_tiles(inds, H, W):
+    """Per task, the byte map of the 13 x 32 forward tiles of its ``B`` maps that hold a gathered cell (``gga_head_cell_tiles``:
+    the tile of ``ind[b, k]`` for every slot, dead ones included - ``gather_pred`` reads those too). ``inds``: the per-task
+    ``[B, K]`` int64 index tensors of ``CenterHead_GGA.get_targets``; when they are the consecutive slices of one ``[T, B, K]``
+    tensor, as ``get_targets`` uploads them, one launch serves all tasks. -> list of uint8 ``[B * tiles]`` views of one buffer."""
+    _need_cuda(*inds)
+    L = _lib.lib()
+    T = len(inds)
+    B, K = inds[0].shape
+    for ind in inds:
+        if ind.dtype != torch.int64 or tuple(ind.shape) != (B, K) or not ind.is_contiguous():
+            raise ValueError(f'head_cell_tiles: every ind must be a contiguous int64 [B, K] tensor (got {ind.dtype} {tuple(ind.shape)})')
+    per = int(L.gga_head_cell_tiles_count(B, H, W))
+    maps = torch.zeros((T, per), dtype=torch.uint8, device=inds[0].device)
+    one = all(inds[t].data_ptr() == inds[0].data_ptr() + 8 * B * K * t for t in range(T))
+    for t in range(1 if one else T):
+        check(L.gga_head_cell_tiles(_p(inds[t]), (T if one else 1) * B, K, H, W, _p(maps[t]), _stream()), 'gga_head_cell_tiles')
+    return list(maps.unbind(0))
+
+
 class _HeadBranches(torch.autograd.Function):
     """All branches ``conv3x3(64 -> c_i)(relu(bn_i(conv3x3(64 -> 64)_i(x))))`` of a CenterHead (every task's
     SeparateHead, centerpoint_head.py:46-79) on the one shared feature map, as one autograd node.
 
     Forward: per branch the bf16x6 convolution writes its 64 channels (and their BatchNorm sums) into a column
     block of ONE [B, 64n, H, W] channels-last buffer, the statistics are folded, and the output conv normalises
-    while it loads. Backward: per branch ``gga_head_branch_bwd`` - the output conv's weight gradient and the tail's
+    while it loads. ``maps`` (None, or per branch None / a tile map of ``head_cell_tiles``): a branch with a map gets its
+    output from ``gga_head_conv3x3_fwd_tiles`` - the dense launch's values on the active tiles, +0.0 everywhere else (those
+    outputs are views of one zero-filled buffer) - for a map the loss reads at a few cells only.
+    Backward: per branch ``gga_head_branch_bwd`` - the output conv's weight gradient and the tail's
     BatchNorm backward, both on the tiles of the branch's output gradient that hold anything (the regression branches
     receive one at a few object cells only) - which writes the gradient w.r.t. the branch's column block of a second
     [B, 64n, H, W] buffer; then ONE
@@ -1156,9 +1179,10 @@ class _HeadBranches(torch.autograd.Function):
     branch left autograd n - 1 full-size additions of the shared map's gradient."""
 
     @staticmethod
-    def forward(ctx, x, n, cfg, *t):
+    def forward(ctx, x, n, cfg, maps, *t):
         from . import dense_conv
         w1, gam, bet, rm, rv, w2, b2 = (t[i * n:(i + 1) * n] for i in range(7))
+        maps = [None] * n if maps is None else list(maps)
         L = _lib.lib()
         B, C, H, W = x.shape
         rows, dev, tot = B * H * W, x.device, C * n
@@ -1180,8 +1204,14 @@ class _HeadBranches(torch.autograd.Function):
                 all_stats.append((dense_conv._run(x, w1[i].detach(), False, True, x_amax, None, Y, C * i)[1], 0))
         # everything the branch launches write is allocated here, on this stream; odd branches are LAUNCHED on a second one
         w2c = [w.contiguous() for w in w2]
+        sizes = [B * w2[i].shape[0] * H * W if maps[i] is not None else 0 for i in range(n)]
+        tiled = torch.zeros(sum(sizes), dtype=torch.float32, device=dev) if any(sizes) else None      # one fill for all of them
         for i in range(n):
-            outs.append(torch.empty((B, w2[i].shape[0], H, W), dtype=torch.float32, device=dev))
+            if maps[i] is not None:
+                o = sum(sizes[:i])
+                outs.append(tiled[o:o + sizes[i]].view(B, w2[i].shape[0], H, W))
+            else:
+                outs.append(torch.empty((B, w2[i].shape[0], H, W), dtype=torch.float32, device=dev))
             saved_all.append(torch.empty(2 * C, dtype=torch.float32, device=dev))
             ss_all.append(torch.empty(2 * C, dtype=torch.float32, device=dev))
         streams = _branch_streams(dev, n)
@@ -1195,8 +1225,13 @@ class _HeadBranches(torch.autograd.Function):
                 check(L.gga_bn_stats_partials_cols(_p(gam[i]), _p(bet[i]), _p(rm[i]), _p(rv[i]), rows, C, eps, momentum,
                                                    _p(saved_all[i]), _p(ss_all[i]), _p(stats), tiles, int(stats.shape[2]), col,
                                                    _stream()), 'gga_bn_stats_partials_cols')
-                check(L.gga_head_conv3x3_fwd(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(w2c[i]), _p(b2[i]), B, H, W, C,
-                                             w2[i].shape[0], _p(outs[i]), _stream()), 'gga_head_conv3x3_fwd')
+                if maps[i] is not None:
+                    check(L.gga_head_conv3x3_fwd_tiles(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(w2c[i]), _p(b2[i]), B, H, W,
+                                                       C, w2[i].shape[0], _p(maps[i]), _p(outs[i]), _stream()),
+                          'gga_head_conv3x3_fwd_tiles')
+                else:
+                    check(L.gga_head_conv3x3_fwd(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(w2c[i]), _p(b2[i]), B, H, W, C,
+                                                 w2[i].shape[0], _p(outs[i]), _stream()), 'gga_head_conv3x3_fwd')
         for st_ in streams[1:]:
             streams[0].wait_stream(st_)
         ctx.save_for_backward(x, Y, *w1, *gam, *w2, *saved_all, *ss_all)
@@ -1249,14 +1284,16 @@ class _HeadBranches(torch.autograd.Function):
         gwcat = dense_conv._wgrad(x, G, wcat, ctx.x_amax if dense_conv.PLANES == 2 else None, g_blocks, g_per_block=True)
         gw1 = list(gwcat.split(C, dim=0))
         none = [None] * n
-        return (gx, None, None, *gw1, *ggam, *gbet, *none, *none, *gw2, *gb2)
+        return (gx, None, None, None, *gw1, *ggam, *gbet, *none, *none, *gw2, *gb2)
 
 
-def head_branches(x, branches, sparse_grad=None):
+def head_branches(x, branches, sparse_grad=None, tile_maps=None):
     """Outputs of the head branches ``[(conv1, bn, conv2), ...]`` that all read ``x`` (see _HeadBranches), or
     None when a branch does not qualify for the fused kernels (the caller then runs them one by one).
     ``sparse_grad``: per branch, False where the output's gradient is known to be dense (a heat-map) - a hint for
-    ``gga_head_branch_bwd``, never a change of the result; default: every branch may be sparse."""
+    ``gga_head_branch_bwd``, never a change of the result; default: every branch may be sparse.
+    ``tile_maps``: per branch None, or a map of ``head_cell_tiles`` - that branch's output is then computed on the map's
+    active tiles only and is +0.0 elsewhere (for an output that is read at the gathered cells alone); default: all dense."""
     from . import dense_conv
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) else None
     if rc is None or x.shape[1] != 64 or not torch.is_grad_enabled() or not dense_conv.ENABLED or not dense_conv.WGRAD:
@@ -1278,7 +1315,15 @@ def head_branches(x, branches, sparse_grad=None):
     cols = ([c1.weight for c1, _, _ in branches], [bn.weight for _, bn, _ in branches], [bn.bias for _, bn, _ in branches],
             [bn.running_mean for _, bn, _ in branches], [bn.running_var for _, bn, _ in branches],
             [c2.weight for _, _, c2 in branches], [c2.bias for _, _, c2 in branches])
-    return _HeadBranches.apply(x, n, cfg, *[t for col in cols for t in col])
+    if tile_maps is not None:
+        B, _, H, W = x.shape
+        per = int(_lib.lib().gga_head_cell_tiles_count(B, H, W))
+        assert len(tile_maps) == n
+        for m in tile_maps:
+            if m is not None and not (m.dtype == torch.uint8 and m.device == x.device and m.is_contiguous() and m.numel() == per):
+                raise ValueError(f'head_branches: a tile map must be a contiguous uint8 tensor of {per} tiles on {x.device}')
+        tile_maps = tuple(tile_maps) if any(m is not None for m in tile_maps) else None
+    return _HeadBranches.apply(x, n, cfg, tile_maps, *[t for col in cols for t in col])
 
 
 def head_conv3x3(x, conv):

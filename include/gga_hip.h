@@ -663,6 +663,20 @@ int gga_bn_stats_partials_cols(const float* gamma, const float* beta, float* run
  * launched. */
 int gga_head_conv3x3_fwd(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
                          const float* bias, int B, int H, int W, int cin, int cout, float* y, void* stream);
+/* The same convolution on the 13 x 32 tiles that tile_active calls active, one byte per tile in the layout
+ * [B][ceil(H / 13)][ceil(W / 32)] (non-zero = active): those tiles of y receive exactly the values gga_head_conv3x3_fwd
+ * writes there, bit for bit, and every other element of y is left untouched. For a map that is read at a few cells only:
+ * a regression map of a CenterHead in training, which F.gather_pred reads at the object cells (gga_head_cell_tiles). */
+int gga_head_conv3x3_fwd_tiles(const float* x, int64_t x_pixel_stride, const float* in_scale_shift, const float* weight,
+                               const float* bias, int B, int H, int W, int cin, int cout, const uint8_t* tile_active, float* y,
+                               void* stream);
+/* The tile maps of gga_head_conv3x3_fwd_tiles from gather indices: ind [n_maps, K] int64, a cell index y * W + x per slot.
+ * Stores 1 into tile_active [n_maps][ceil(H / 13)][ceil(W / 32)], which the caller has zeroed, for the tile that holds
+ * each index - all K slots of a map, whatever their mask says: the gather reads the dead slots' cell (0) too. An index
+ * outside [0, H * W) marks nothing. One launch for all maps (every task of a head: n_maps = tasks x B).
+ * gga_head_cell_tiles_count: the number of tiles (= bytes) of B maps, 0 for a size below 1. */
+int64_t gga_head_cell_tiles_count(int B, int H, int W);
+int gga_head_cell_tiles(const int64_t* ind, int n_maps, int K, int H, int W, uint8_t* tile_active, void* stream);
 /* grad_weight [cout,64,3,3] and grad_bias [cout] (optional) from grad_y [B,cout,H,W]. Map size: H and W below 16384
  * (the forward's bound, kept on this side so that both directions accept the same maps) and 8 * W * x_pixel_stride
  * below 2^31 elements, else GGA_ERR_INVALID_ARG before anything is launched. workspace:
