@@ -65,6 +65,8 @@ class LiDARInstance3DBoxes:
         return self.tensor.shape[0]
 
     def __getitem__(self, item):
+        if isinstance(item, torch.Tensor):      # masks and index tensors (base_box3d.py:327-328)
+            item = item.to(self.device)
         t = self.tensor[item]
         if t.dim() == 1:
             t = t.view(1, -1)
@@ -83,6 +85,34 @@ class LiDARInstance3DBoxes:
         """base_box3d.py:488-508: a box object of the same type / device from array-like ``data``."""
         t = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) else data.to(self.device)
         return type(self)(t, box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    @classmethod
+    def cat(cls, boxes_list):
+        """base_box3d.py:342-363: the boxes of ``boxes_list`` in one object (never sharing storage with them)."""
+        assert isinstance(boxes_list, (list, tuple))
+        if len(boxes_list) == 0:
+            return cls(torch.empty(0))
+        assert all(isinstance(box, cls) for box in boxes_list)
+        return cls(torch.cat([b.tensor for b in boxes_list], dim=0), box_dim=boxes_list[0].tensor.shape[1],
+                   with_yaw=boxes_list[0].with_yaw)
+
+    def flip(self, bev_direction='horizontal'):
+        """lidar_box3d.py:143-164, in place: horizontal y -> -y, yaw -> -yaw; vertical x -> -x, yaw -> -yaw + pi. The stride
+        of 7 reaches the velocity column of a 9-column box (vy with y, vx with x)."""
+        assert bev_direction in ('horizontal', 'vertical')
+        if bev_direction == 'horizontal':
+            self.tensor[:, 1::7] = -self.tensor[:, 1::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6]
+        else:
+            self.tensor[:, 0::7] = -self.tensor[:, 0::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6] + math.pi
+
+    def scale(self, scale_factor):
+        """base_box3d.py:263-270, in place: centre, size and the columns past the yaw (velocity)."""
+        self.tensor[:, :6] *= scale_factor
+        self.tensor[:, 7:] *= scale_factor
 
     def limit_yaw(self, offset=0.5, period=math.pi):
         """base_box3d.py:272-279 / structures/utils.py:11-25: yaw -> [-offset*period, (1-offset)*period)."""

@@ -6,6 +6,7 @@ restated: the total is the sum of every entry whose key contains ``'loss'``).
 
 LiDAR-only: the GGA configs build no image branch (extract_img_feat returns None).
 """
+import os
 from collections import OrderedDict
 
 import torch
@@ -206,13 +207,16 @@ class MVXTwoStageDetector_GGA(nn.Module):
             raise ValueError(f'num of augmentations ({len(points)}) != num of image meta ({len(img_metas)})')
         if len(points) == 1:
             return self.simple_test(points[0], img_metas[0], None if img is None else img[0], **kwargs)
-        raise NotImplementedError('test-time augmentation is not on the GGA path')
+        return self.aug_test(points, img_metas, img, **kwargs)
 
     @torch.no_grad()
     def simple_test_pts(self, x, img_metas, rescale=False):
-        from .box3d import bbox3d2result
         outs = self.pts_bbox_head(x)
-        bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas, rescale=rescale)
+        return self._results_to_host(self.pts_bbox_head.get_bboxes(outs, img_metas, rescale=rescale))
+
+    @staticmethod
+    def _results_to_host(bbox_list):
+        from .box3d import bbox3d2result
         packed = getattr(bbox_list, 'packed', None)
         if packed is not None:
             # the batched post-processing left one set of batch tensors: three copies to the host for the whole batch
@@ -231,6 +235,124 @@ class MVXTwoStageDetector_GGA(nn.Module):
             for result_dict, pts_bbox in zip(bbox_list, self.simple_test_pts(pts_feats, img_metas, rescale=rescale)):
                 result_dict['pts_bbox'] = pts_bbox
         return bbox_list
+
+    # ---- test-time augmentation (centerpoint_gga.py:99-208, with samples_per_gpu > 1) ---------------------------------
+    # The V views of the F frames of a batch go through the front, the trunk and the head as ONE batch of V * F point clouds,
+    # view-major (view v of frame f is row v * F + f). One launch then undoes the flips of every task's maps and averages them
+    # per scale group (functional.tta_merge_maps), the detections of the S * F merged "frames" are decoded at once, and for
+    # S > 1 the boxes of a frame's scale groups are mapped back and merged (tta.merge_aug_bboxes_3d). GGA_TTA_MERGE=0: the
+    # maps are merged by the reference's per-view eager sequence instead (the fallback, and what the tests compare against).
+    TTA_MERGE = os.environ.get('GGA_TTA_MERGE', '1') != '0'
+
+    @torch.no_grad()
+    def aug_test(self, points, img_metas, img=None, rescale=False):
+        n_frames = len(points[0])
+        for view, metas in zip(points, img_metas):
+            if len(view) != n_frames or len(metas) != n_frames:
+                raise ValueError('aug_test: every view must hold the same frames (points[v][f], img_metas[v][f])')
+        self._tta_views(img_metas)        # a set of views that cannot be merged is refused before the trunk runs
+        flat = [p for view in points for p in view]
+        _, pts_feats = self.extract_feat(flat, img=None, img_metas=[m for metas in img_metas for m in metas])
+        bbox_list = [dict() for _ in range(n_frames)]
+        if pts_feats and self.with_pts_bbox:
+            for result_dict, pts_bbox in zip(bbox_list, self.aug_test_pts(pts_feats, img_metas, rescale=rescale)):
+                result_dict['pts_bbox'] = pts_bbox
+        return bbox_list
+
+    def _tta_views(self, img_metas):
+        """-> (group [V], hflip [V], vflip [V], first view of every group): scale groups in order of first appearance of
+        ``pcd_scale_factor``. A view's frames share one augmentation (the wrapper's loop does not depend on the frame)."""
+        scales, group, hflip, vflip, first = [], [], [], [], []
+        for v, metas in enumerate(img_metas):
+            key = lambda m: (m['pcd_scale_factor'], bool(m.get('pcd_horizontal_flip', False)), bool(m.get('pcd_vertical_flip', False)))
+            scale, h, vf = key(metas[0])
+            if any(key(m) != (scale, h, vf) for m in metas[1:]):
+                raise ValueError(f'aug_test: the frames of view {v} carry different augmentations')
+            if scale not in scales:
+                scales.append(scale)
+                first.append(v)
+            group.append(scales.index(scale))
+            hflip.append(h)
+            vflip.append(vf)
+        per_scale = [group.count(s) for s in range(len(scales))]
+        if len(set(per_scale)) != 1:
+            raise ValueError(f'aug_test: the scale groups {scales} have {per_scale} views; every scale needs the same number')
+        pcr = getattr(getattr(self, 'pts_voxel_layer', None), 'point_cloud_range', None)
+        if pcr is not None:
+            for flags, axis, lo, hi, name in ((hflip, 'y', pcr[1], pcr[4], 'horizontal'), (vflip, 'x', pcr[0], pcr[3], 'vertical')):
+                if any(flags) and lo != -hi:
+                    raise ValueError(f'aug_test: a {name} flip mirrors the {axis} axis, but point_cloud_range spans '
+                                     f'[{lo}, {hi}] on {axis}: not symmetric about 0, mirroring the head maps cannot undo it')
+        return group, hflip, vflip, first
+
+    @staticmethod
+    def _tta_merge_views_eager(views, group, hflip, vflip):
+        """centerpoint_gga.py:123-182 on ``views[v][f]`` = the head's output of view v of frame f at batch 1: flip, channel
+        fix-up, ``+=`` into the group's first view, ``/=`` views per scale; the groups' frames then form the batch
+        ``get_bboxes`` takes."""
+        n_groups, n_frames = max(group) + 1, len(views[0])
+        sums = {}
+        for v, frames in enumerate(views):
+            for f, view in enumerate(frames):
+                view = [[dict(task[0])] for task in view]
+                for task in view:
+                    for key in task[0].keys():
+                        if hflip[v]:
+                            task[0][key] = torch.flip(task[0][key], dims=[2])
+                            if key == 'reg':
+                                task[0][key][:, 1, ...] = 1 - task[0][key][:, 1, ...]
+                            elif key == 'rot':
+                                task[0][key][:, 0, ...] = -task[0][key][:, 0, ...]
+                            elif key == 'vel':
+                                task[0][key][:, 1, ...] = -task[0][key][:, 1, ...]
+                        if vflip[v]:
+                            task[0][key] = torch.flip(task[0][key], dims=[3])
+                            if key == 'reg':
+                                task[0][key][:, 0, ...] = 1 - task[0][key][:, 0, ...]
+                            elif key == 'rot':
+                                task[0][key][:, 1, ...] = -task[0][key][:, 1, ...]
+                            elif key == 'vel':
+                                task[0][key][:, 0, ...] = -task[0][key][:, 0, ...]
+                slot = (group[v], f)
+                if slot not in sums:        # (a copy: an unflipped first view is still the head's own tensor)
+                    sums[slot] = [[{key: x.clone() for key, x in task[0].items()}] for task in view]
+                else:
+                    for acc, task in zip(sums[slot], view):
+                        for key in task[0].keys():
+                            acc[0][key] += task[0][key]
+        for acc_tasks in sums.values():
+            for acc in acc_tasks:
+                for key in acc[0].keys():
+                    acc[0][key] /= len(group) / n_groups
+        first = views[0][0]
+        return [[{key: torch.cat([sums[(s, f)][t][0][key] for s in range(n_groups) for f in range(n_frames)])
+                  for key in first[t][0].keys()}] for t in range(len(first))]
+
+    @classmethod
+    def _tta_merge_maps_eager(cls, outs, group, hflip, vflip, n_frames):
+        """The eager merge on the view-major batch: every view of every frame as its [1, C, H, W] slice."""
+        views = [[[[{key: x[v * n_frames + f:v * n_frames + f + 1] for key, x in task[0].items()}] for task in outs]
+                  for f in range(n_frames)] for v in range(len(group))]
+        return cls._tta_merge_views_eager(views, group, hflip, vflip)
+
+    @torch.no_grad()
+    def aug_test_pts(self, feats, img_metas, rescale=False):
+        from . import functional as F
+        from .tta import merge_aug_bboxes_3d
+        head = self.pts_bbox_head
+        n_frames = len(img_metas[0])
+        group, hflip, vflip, first = self._tta_views(img_metas)
+        n_groups = len(first)
+        outs = head(feats)
+        merge = F.tta_merge_maps if self.TTA_MERGE else self._tta_merge_maps_eager
+        merged = merge(outs, group, hflip, vflip, n_frames)
+        bbox_list = head.get_bboxes(merged, [img_metas[v][f] for v in first for f in range(n_frames)], rescale=rescale)
+        if n_groups == 1:
+            return self._results_to_host(bbox_list)
+        # scales are merged box by box: per frame, the detections of its S groups with the metas of each group's first view
+        return [merge_aug_bboxes_3d([dict(zip(('boxes_3d', 'scores_3d', 'labels_3d'), bbox_list[s * n_frames + f]))
+                                     for s in range(n_groups)], [[img_metas[v][f]] for v in first], head.test_cfg)
+                for f in range(n_frames)]
 
     # ---- mmdet BaseDetector.train_step / _parse_losses (restated) -----------------
     def _parse_losses(self, losses):

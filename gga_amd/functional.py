@@ -1366,3 +1366,51 @@ def centerpoint_detect(boxes, scores, labels, coder_range, coder_score_threshold
                                             int(pre_max_size or 0), int(post_max_size or 0), _p(co), _p(sc), _p(out_boxes), _p(out_scores),
                                             _p(out_labels), _p(count), _p(ws), ws.numel(), _stream()), 'gga_centerpoint_detect')
     return out_boxes, out_scores, out_labels, count
+
+
+TTA_KINDS = {'reg': _lib.TTA_REG, 'rot': _lib.TTA_ROT, 'vel': _lib.TTA_VEL}       # every other key is only mirrored
+
+
+def tta_merge_maps(outs, group, hflip, vflip, n_frames):
+    """``gga_tta_merge_maps``: the head's eval output ``[[{key: [V * F, C, H, W]}], ...]`` (one entry per task, view-major
+    batch) -> the same structure with batch ``S * F``: per scale group ``group[v]`` in ``0..S-1`` the mean, in view order, of
+    the views' maps with their flips (``hflip[v]``, ``vflip[v]``) undone - all tasks, keys, groups and frames in one launch,
+    with the bits of the reference's per-view flip / add / divide sequence (centerpoint_gga.py:123-182)."""
+    V, F_ = len(group), int(n_frames)
+    if not (len(hflip) == V and len(vflip) == V):
+        raise ValueError('tta_merge_maps: group, hflip and vflip must have one entry per view')
+    if not 1 <= V <= _lib.TTA_MAX_VIEWS:
+        raise ValueError(f'tta_merge_maps: {V} views, the kernel takes 1..{_lib.TTA_MAX_VIEWS}')
+    S = max(int(g) for g in group) + 1
+    tb = _lib.TtaTable()
+    tb.n_views, tb.n_groups = V, S
+    for v in range(V):
+        tb.group[v], tb.hflip[v], tb.vflip[v] = int(group[v]), int(bool(hflip[v])), int(bool(vflip[v]))
+    merged, keep, n, shape = [], [], 0, None
+    for task in outs:
+        if len(task) != 1:
+            raise ValueError(f'tta_merge_maps: {len(task)} feature levels in a task, the head returns one')
+        new = {}
+        for key, src in task[0].items():
+            _need_cuda(src)
+            if src.dtype != torch.float32 or src.dim() != 4 or src.shape[0] != V * F_:
+                raise ValueError(f'tta_merge_maps: {key} must be float32 [{V * F_}, C, H, W], got {src.dtype} {tuple(src.shape)}')
+            if shape is None:
+                shape = tuple(src.shape[2:])
+            elif tuple(src.shape[2:]) != shape:
+                raise ValueError(f'tta_merge_maps: {key} is {tuple(src.shape[2:])}, the other maps are {shape}')
+            if n == _lib.TTA_MAX_MAPS:
+                raise ValueError(f'tta_merge_maps: more than {_lib.TTA_MAX_MAPS} maps')
+            src = src.contiguous()
+            dst = torch.empty((S * F_,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+            e = tb.map[n]
+            e.src, e.dst, e.channels, e.kind = _p(src), _p(dst), src.shape[1], TTA_KINDS.get(key, _lib.TTA_PLAIN)
+            keep.append(src)
+            new[key] = dst
+            n += 1
+        merged.append([new])
+    if shape is None:
+        raise ValueError('tta_merge_maps: no maps')
+    tb.n_maps = n
+    check(_lib.lib().gga_tta_merge_maps(C.byref(tb), F_, shape[0], shape[1], _stream()), 'gga_tta_merge_maps')
+    return merged

@@ -912,6 +912,39 @@ int gga_centerpoint_detect(const float* boxes, const float* scores, const float*
                            float* out_scores, int32_t* out_labels, int32_t* out_count, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Test-time augmentation: the head maps of all views of a batch merged per scale group in one launch. Restates the per-view
+ * torch.flip / slice-assign / `+=` / `/=` sequence of mmdet3d/models/detectors/centerpoint_gga.py:123-182 (aug_test_pts).
+ * A map is a contiguous f32 [n_views * n_frames, channels, H, W] tensor, view-major (view v of frame f is row v * n_frames + f);
+ * dst is [n_groups * n_frames, channels, H, W]. dst[s * n_frames + f] = acc / n with acc = value(first view of group s) and
+ * acc = acc + value(next view) in view order, n = the number of views of the group, a true f32 division: the bits of the
+ * reference's sequence. value() undoes the view's flips: hflip reads row H-1-h, vflip reads column W-1-w (both may apply),
+ * and by kind
+ *     GGA_TTA_REG: hflip channel 1 <- 1 - x, vflip channel 0 <- 1 - x
+ *     GGA_TTA_ROT: hflip channel 0 <- -x,    vflip channel 1 <- -x
+ *     GGA_TTA_VEL: hflip channel 1 <- -x,    vflip channel 0 <- -x
+ *     GGA_TTA_PLAIN (heatmap logits, height, dim, ...): mirrored only.
+ * GGA_ERR_INVALID_ARG before any HIP call for: a null table; n_maps outside 1..GGA_TTA_MAX_MAPS; n_views outside
+ * 1..GGA_TTA_MAX_VIEWS; n_groups outside 1..n_views; H, W or n_frames <= 0; a group index outside 0..n_groups-1; a group
+ * without a view; an unknown kind; a REG / ROT / VEL map with fewer than 2 channels; a null map pointer. Rows are read and
+ * written with 16-byte accesses when W is a multiple of 4 and every pointer is 16-byte aligned, else element by element. */
+#define GGA_TTA_MAX_VIEWS 16
+#define GGA_TTA_MAX_MAPS (GGA_MAX_TASKS * 6)
+enum { GGA_TTA_PLAIN = 0, GGA_TTA_REG = 1, GGA_TTA_ROT = 2, GGA_TTA_VEL = 3 };
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t channels;
+    int32_t kind;
+} gga_tta_map;
+typedef struct {
+    int32_t n_maps, n_views, n_groups;
+    int32_t group[GGA_TTA_MAX_VIEWS];     /* scale group of a view */
+    int32_t hflip[GGA_TTA_MAX_VIEWS];     /* pcd_horizontal_flip (y -> -y: the map's H index) */
+    int32_t vflip[GGA_TTA_MAX_VIEWS];     /* pcd_vertical_flip (x -> -x: the map's W index) */
+    gga_tta_map map[GGA_TTA_MAX_MAPS];
+} gga_tta_table;
+int gga_tta_merge_maps(const gga_tta_table* table, int n_frames, int H, int W, void* stream);
+
 /* Pseudo-label matching: image-plane IoU of every detection with the ground truths of its own
  * frame and the argmax, i.e. `calculate_iou_partly(dt_annos, gt_annos, metric=0)` followed by
  * `np.argmax(c_overlap, axis=-1)` in tools/utils_pseudo_labels_gga.py:44-59 (IoU arithmetic:

@@ -1782,6 +1782,73 @@ def golden_dynamic_voxel(ref):
     np.savez_compressed(os.path.join(OUT, 'dynamic_voxel.npz'), **out)
 
 
+TTA_VIEWS = [(1.0, False, False), (1.0, True, False), (1.0, False, True), (1.0, True, True),
+             (0.95, False, False), (0.95, True, False), (0.95, False, True), (0.95, True, True)]
+TTA_TASK_KEYS = [dict(reg=2, height=1, dim=3, rot=2, heatmap=1), dict(reg=2, height=1, dim=3, rot=2, vel=2, heatmap=2)]
+
+
+def golden_tta(ref):
+    """Test-time augmentation. (a) the reference's ``bbox3d_mapping_back`` (mmdet3d/core/bbox/transforms.py) on its own 7- and
+    9-column LiDAR boxes for the four flip combinations x three scales. (b) the merged head maps the body of the reference's
+    ``aug_test_pts`` (mmdet3d/models/detectors/centerpoint_gga.py) hands to ``get_bboxes``, per scale group: the method is
+    taken out of its class by name at run time (the module imports the detector base classes) and driven with a stub ``self``
+    whose head returns prepared random maps and records what ``get_bboxes`` receives. CPU float32. Arrays only."""
+    import ast
+    pl = import_reference_pipeline(ref)
+    tr = load('mmdet3d.core.bbox.transforms', 'mmdet3d/core/bbox/transforms.py')
+    Boxes = pl['LiDARInstance3DBoxes']
+    rng = np.random.default_rng(2024)
+    out = {}
+    for dim in (7, 9):
+        b = rng.uniform(-1, 1, size=(6, dim)).astype(np.float32)
+        b[:, :3] *= 30
+        b[:, 3:6] = np.abs(b[:, 3:6]) * 4 + 0.3
+        b[:, 6] *= 3.1
+        out[f'box{dim}'] = b
+        for h in (False, True):
+            for v in (False, True):
+                for si, scale in enumerate((0.95, 1, 1.05)):
+                    back = tr.bbox3d_mapping_back(Boxes(torch.from_numpy(b.copy()), box_dim=dim), scale, h, v)
+                    out[f'back{dim}.{int(h)}{int(v)}.{si}'] = back.tensor.numpy()
+    out['back_scales'] = np.array([0.95, 1, 1.05], np.float64)
+
+    src = open(os.path.join(REF, 'mmdet3d/models/detectors/centerpoint_gga.py')).read()
+    cls = [n for n in ast.parse(src).body if isinstance(n, ast.ClassDef)][0]
+    fns = [n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == 'aug_test_pts']
+    ns = dict(torch=torch, merge_aug_bboxes_3d=lambda *a, **k: None)
+    exec(compile(ast.Module(body=fns, type_ignores=[]), 'centerpoint_gga.py', 'exec'), ns)
+    H, W = 5, 7
+    maps = [[{k: torch.from_numpy(rng.normal(size=(1, c, H, W)).astype(np.float32)) for k, c in keys.items()} for keys in TTA_TASK_KEYS]
+            for _ in TTA_VIEWS]
+    for v, tasks in enumerate(maps):
+        for t, task in enumerate(tasks):
+            for k, x in task.items():
+                out[f'in.{v}.{t}.{k}'] = x.numpy().copy()
+    seen = []
+
+    class Head:
+        test_cfg = None
+
+        def __call__(self, x):          # `x` is the view's index; (the method writes into what it gets: hand out copies)
+            return [[{k: t.clone() for k, t in task.items()}] for task in maps[x]]
+
+        def get_bboxes(self, preds_dict, img_metas, rescale=False):
+            seen.append([{k: t.clone() for k, t in task[0].items()} for task in preds_dict])
+            return [(torch.zeros(0, 7), torch.zeros(0), torch.zeros(0, dtype=torch.long))]
+
+    fake = type('D', (), dict(pts_bbox_head=Head()))()
+    metas = [[dict(pcd_scale_factor=s, pcd_horizontal_flip=h, pcd_vertical_flip=v)] for s, h, v in TTA_VIEWS]
+    ns['aug_test_pts'](fake, list(range(len(TTA_VIEWS))), metas)
+    assert len(seen) == 2
+    for s, tasks in enumerate(seen):
+        for t, task in enumerate(tasks):
+            for k, x in task.items():
+                out[f'out.{s}.{t}.{k}'] = x.numpy()
+    out['views'] = np.array([[s, h, v] for s, h, v in TTA_VIEWS], np.float64)
+    print('  tta:', len(TTA_VIEWS), 'views ->', len(seen), 'scale groups,', sum(len(t) for t in seen[0]), 'maps each')
+    np.savez_compressed(os.path.join(OUT, 'tta.npz'), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -1806,6 +1873,7 @@ def main():
     golden_pgd(ref)
     golden_configs(ref)
     golden_dynamic_voxel(ref)
+    golden_tta(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
