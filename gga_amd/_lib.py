@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _lib = None
 
@@ -46,6 +46,7 @@ class TaskTable(C.Structure):
     _fields_ = [('n_tasks', C.c_int32), ('task', Task * MAX_TASKS)]
 
 
+MULTICLASS_NMS_MAX_CLASSES = 128    # GGA_MULTICLASS_NMS_MAX_CLASSES
 TTA_MAX_VIEWS = 16                  # GGA_TTA_MAX_VIEWS
 TTA_MAX_MAPS = MAX_TASKS * 6        # GGA_TTA_MAX_MAPS
 TTA_PLAIN, TTA_REG, TTA_ROT, TTA_VEL = range(4)
@@ -188,6 +189,8 @@ SIGNATURES = {
     'gga_indoor_eval_assign': (i32, [vp, vp, vp, vp, i64, vp, i64, i32, C.POINTER(C.c_float * 8), i32, vp, vp, sz, vp]),
     'gga_centerpoint_detect_workspace_bytes': (sz, [i32, i32]),
     'gga_centerpoint_detect': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, C.c_float, i32, C.c_float, vp, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'gga_multiclass_nms3d_workspace_bytes': (sz, [i64, i32, i32]),
+    'gga_multiclass_nms3d': (i32, [vp, vp, vp, i64, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
     'gga_tta_merge_maps': (i32, [C.POINTER(TtaTable), i32, i32, i32, vp]),
     'gga_points_in_boxes': (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     'gga_fcos3d_targets': (i32, [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), f32, vp, i32,

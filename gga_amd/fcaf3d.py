@@ -87,6 +87,54 @@ class DepthInstance3DBoxes:
         t = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) else data.to(self.tensor.device)
         return type(self)(t, box_dim=self.box_dim, with_yaw=self.with_yaw)
 
+    # ---- the moves of the train pipelines (depth_box3d.py:93-186, base_box3d.py:210-240), all in place
+    MOVES_WITH_POINTS = True          # GlobalRotScaleTrans / RandomFlip3D carry these boxes along with the points
+
+    @property
+    def corners(self):
+        """[N, 8, 3] corners (depth_box3d.py:38-91): the sizes times the unit corners about the bottom centre, turned by the
+        yaw about z, moved to the box."""
+        if self.tensor.numel() == 0:
+            return torch.empty([0, 8, 3], device=self.tensor.device)
+        dims = self.tensor[:, 3:6]
+        unit = dims.new_tensor([[0, 0, 0], [0, 0, 1], [0, 1, 1], [0, 1, 0], [1, 0, 0], [1, 0, 1], [1, 1, 1], [1, 1, 0]]) - \
+            dims.new_tensor([0.5, 0.5, 0])
+        corners = rotation_3d_in_axis_z(dims.view(-1, 1, 3) * unit.reshape(1, 8, 3), self.tensor[:, 6])
+        return corners + self.tensor[:, :3].view(-1, 1, 3)
+
+    def rotate(self, rot_mat_t):
+        """Centres times the transposed rotation about z ``rot_mat_t`` [3, 3]; boxes with a yaw turn by its angle, axis-aligned
+        boxes become the axis-aligned boxes that enclose the turned ones."""
+        rot_mat_t = self.tensor.new_tensor(rot_mat_t) if not isinstance(rot_mat_t, torch.Tensor) else rot_mat_t.to(self.tensor)
+        assert rot_mat_t.shape == torch.Size([3, 3]), f'invalid rotation shape {rot_mat_t.shape}'
+        self.tensor[:, 0:3] = self.tensor[:, 0:3] @ rot_mat_t
+        if self.with_yaw:
+            self.tensor[:, 6] += math.atan2(float(rot_mat_t[0, 1]), float(rot_mat_t[0, 0]))
+        elif len(self):
+            turned = self.corners @ rot_mat_t
+            self.tensor[:, 3] = turned[..., 0].max(dim=1)[0] - turned[..., 0].min(dim=1)[0]
+            self.tensor[:, 4] = turned[..., 1].max(dim=1)[0] - turned[..., 1].min(dim=1)[0]
+
+    def flip(self, bev_direction='horizontal'):
+        """Depth coordinates: a horizontal flip negates x (yaw -> pi - yaw), a vertical one y (yaw -> -yaw)."""
+        assert bev_direction in ('horizontal', 'vertical')
+        if bev_direction == 'horizontal':
+            self.tensor[:, 0] = -self.tensor[:, 0]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6] + math.pi
+        else:
+            self.tensor[:, 1] = -self.tensor[:, 1]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6]
+
+    def scale(self, scale_factor):
+        self.tensor[:, :6] *= scale_factor
+
+    def translate(self, trans_vector):
+        if not isinstance(trans_vector, torch.Tensor):
+            trans_vector = self.tensor.new_tensor(trans_vector)
+        self.tensor[:, :3] += trans_vector
+
     def convert_to(self, dst, rt_mat=None):
         """depth_box3d.py ``convert_to``: Depth boxes stay what they are; another mode needs Box3DMode, which is not here."""
         if dst is not None and dst not in ('Depth', 'DEPTH', 2) and getattr(dst, 'name', None) != 'DEPTH' and dst is not type(self):

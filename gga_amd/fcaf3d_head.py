@@ -24,6 +24,8 @@ Here the scenes of a batch are never looped over in the train path: locations ca
 padded [scene, box] table, pruning and the per-level pre-selection are one segmented top-k, the assignment is one
 [scene, location, box] broadcast and the per-scene loss sums are one ``index_add`` each; the two per-scene ``reduce_mean``
 collectives of the reference become two vector all-reduces."""
+import os
+
 import torch
 from torch import nn
 
@@ -34,15 +36,21 @@ from .registry import HEADS, build_loss
 _NO_BOX = 1e8          # volume standing for "no box claims this location"
 
 
+def detect_batched():
+    """The environment switch ``GGA_FCAF3D_DETECT_BATCHED=0`` sends ``FCAF3DHead.detect`` back to the per-scene, per-class loop
+    (A/B runs; read at every call)."""
+    return os.environ.get('GGA_FCAF3D_DETECT_BATCHED', '1') != '0'
+
+
 def top_per_segment(score, segment, n_segments, k):
     """Boolean mask over ``score`` [n]: the ``k`` largest entries of every segment (``segment`` [n] int64 in [0, n_segments)).
     Ties at the k-th place are broken by position (earlier rows first)."""
     n = score.numel()
     if n == 0 or k <= 0:
         return torch.zeros(n, dtype=torch.bool, device=score.device)
-    size = torch.bincount(segment, minlength=n_segments)
     if k >= n:
         return torch.ones(n, dtype=torch.bool, device=score.device)
+    size = torch.zeros(n_segments, dtype=torch.long, device=score.device).index_add_(0, segment, torch.ones_like(segment))      # (bincount reads its maximum back)
     by_score = torch.argsort(score, descending=True, stable=True)
     grouped = by_score[torch.argsort(segment[by_score], stable=True)]          # segments in order, best first inside each
     first = torch.cumsum(size, 0) - size
@@ -284,18 +292,52 @@ class FCAF3DHead(nn.Module):
         """-> per scene (boxes container, scores, labels)."""
         n_scenes, cfg = len(input_metas), self.test_cfg
         boxes, scores, scenes = [], [], []
+        batched = detect_batched()
         for l in levels:
             score = l.cls.sigmoid() * l.centre.sigmoid()
             if cfg.nms_pre > 0:
-                sel = torch.nonzero(top_per_segment(score.max(dim=1).values, l.scene, n_scenes, cfg.nms_pre)).squeeze(1)
-                boxes.append(decode_boxes(l.xyz[sel], l.box[sel])), scores.append(score[sel]), scenes.append(l.scene[sel])
+                keep = top_per_segment(score.max(dim=1).values, l.scene, n_scenes, cfg.nms_pre)
+                if batched:
+                    # the kept rows in their order, without asking the device how many there are: a fixed number of rows, the
+                    # kept ones first; the rows that only fill up carry scene -1, which multiclass_nms3d never keeps
+                    sel = torch.argsort((~keep).to(torch.uint8), stable=True)[:min(len(keep), n_scenes * cfg.nms_pre)]
+                    scene = l.scene[sel].masked_fill(~keep[sel], -1)
+                else:
+                    sel = torch.nonzero(keep).squeeze(1)
+                    scene = l.scene[sel]
+                boxes.append(decode_boxes(l.xyz[sel], l.box[sel])), scores.append(score[sel]), scenes.append(scene)
             else:
                 boxes.append(decode_boxes(l.xyz, l.box)), scores.append(score), scenes.append(l.scene)
         boxes, scores, scenes = torch.cat(boxes), torch.cat(scores), torch.cat(scenes)
+        if batched:
+            return self.nms_batched(boxes, scores, scenes, input_metas)
         out = []
         for s, meta in enumerate(input_metas):
             rows = torch.nonzero(scenes == s).squeeze(1)
             out.append(self.nms_per_class(boxes[rows], scores[rows], meta))
+        return out
+
+    def nms_batched(self, boxes, scores, scenes, input_metas):
+        """``nms_per_class`` of every scene through one ``multiclass_nms3d`` call: the kept (row, class) pairs come back
+        packed in the order the loop concatenates them, the boxes and scores are gathered by row (the same values), and the
+        per-scene counts are the one download."""
+        from . import functional as F
+        cfg = self.test_cfg
+        oriented = boxes.shape[1] == 7
+        if not oriented:
+            boxes = torch.cat([boxes, boxes.new_zeros(len(boxes), 1)], dim=1)
+        rows, classes, count = F.multiclass_nms3d(boxes, scores, scenes, len(input_metas), cfg.score_thr, cfg.iou_thr)
+        count = count.tolist()
+        total = sum(count)
+        rows, classes = rows[:total].long(), classes[:total].long()
+        b, s = boxes[rows], scores[rows, classes]
+        dim = 7 if oriented else 6
+        out, at = [], 0
+        for meta, k in zip(input_metas, count):
+            part = slice(at, at + k)
+            out.append((meta['box_type_3d'](b[part, :dim], box_dim=dim, with_yaw=oriented, origin=(.5, .5, .5)), s[part],
+                        classes[part]))
+            at += k
         return out
 
     def nms_per_class(self, boxes, scores, input_meta):

@@ -1368,6 +1368,32 @@ def centerpoint_detect(boxes, scores, labels, coder_range, coder_score_threshold
     return out_boxes, out_scores, out_labels, count
 
 
+def multiclass_nms3d(boxes, scores, scene, n_scenes, score_thr, iou_thr):
+    """``gga_multiclass_nms3d``: per-class greedy BEV NMS of every scene of a batch in a fixed number of launches.
+    boxes [n, 7] (x, y, z, dx, dy, dz, heading; heading 0 for axis-aligned boxes), scores [n, C], scene [n] int64 (rows in any
+    order) -> (rows int32 [n * C], classes int32 [n * C], count int32 [n_scenes]), all on the device: the kept detections
+    packed scene by scene, class-ascending, by descending score within a class; only the first ``count.sum()`` entries are
+    written. Nothing is read back here: the caller downloads ``count`` once."""
+    _need_cuda(boxes, scores, scene)
+    if boxes.dim() != 2 or boxes.shape[1] != 7 or scores.dim() != 2 or scores.shape[0] != boxes.shape[0] or \
+            scene.shape != (boxes.shape[0],):
+        raise ValueError(f'multiclass_nms3d: boxes [n, 7], scores [n, C], scene [n] expected, got {tuple(boxes.shape)}, '
+                         f'{tuple(scores.shape)}, {tuple(scene.shape)}')
+    n, nc = scores.shape
+    if not 1 <= nc <= _lib.MULTICLASS_NMS_MAX_CLASSES:
+        raise ValueError(f'multiclass_nms3d: {nc} classes, the kernel takes 1..{_lib.MULTICLASS_NMS_MAX_CLASSES}')
+    dev = boxes.device
+    boxes, scores, scene = boxes.float().contiguous(), scores.float().contiguous(), scene.long().contiguous()
+    rows = torch.empty(n * nc, dtype=torch.int32, device=dev)
+    classes = torch.empty(n * nc, dtype=torch.int32, device=dev)
+    count = torch.empty(int(n_scenes), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _workspace('mc_nms', L.gga_multiclass_nms3d_workspace_bytes(n, nc, int(n_scenes)), dev)
+    check(L.gga_multiclass_nms3d(_p(boxes), _p(scores), _p(scene), n, nc, int(n_scenes), float(score_thr), float(iou_thr),
+                                 _p(rows), _p(classes), _p(count), _p(ws), ws.numel(), _stream()), 'gga_multiclass_nms3d')
+    return rows, classes, count
+
+
 TTA_KINDS = {'reg': _lib.TTA_REG, 'rot': _lib.TTA_ROT, 'vel': _lib.TTA_VEL}       # every other key is only mirrored
 
 

@@ -8,7 +8,8 @@ mmcv ``collate`` / ``DataContainer`` / ``scatter``): their published behaviour i
 pieces that decide WHICH frames a rank sees are covered by tests (tests/test_loader.py: every index exactly once per epoch
 over the ranks up to the padding, disjoint shards, a new order per epoch, equal order for equal seeds).
 
-* ``RepeatDataset``: the wrapper the shipped config puts around the KITTI dataset (``times`` passes per epoch).
+* ``RepeatDataset``: the wrapper the shipped config puts around the KITTI dataset (``times`` passes per epoch);
+  ``ConcatDataset``: the S3DIS train areas one behind the other.
 * samplers: with ``shuffle`` the group samplers of mmdet (frames are grouped by the dataset's ``flag`` - all zero for the
   LiDAR datasets - and dealt in whole per-GPU batches, so that every batch holds one group only); ``GroupSampler`` draws from
   numpy's global generator, ``DistributedGroupSampler`` from a generator seeded with ``seed + epoch`` on every rank, each rank
@@ -53,15 +54,47 @@ class RepeatDataset:
         return self.times * self._ori_len
 
 
+@DATASETS.register_module()
+class ConcatDataset:
+    """Several datasets one behind the other (mmdet ``ConcatDataset``, as configs/fcaf3d/fcaf3d_8x2_s3dis-3d-5class.py puts
+    the S3DIS train areas together): item i is an item of the dataset whose range holds i, ``CLASSES`` are the first
+    dataset's, ``flag`` is the concatenation. The configs use it for the train split only: ``evaluate`` raises."""
+
+    def __init__(self, datasets, separate_eval=True):
+        self.datasets = list(datasets)
+        assert len(self.datasets) > 0, 'datasets should not be an empty iterable'
+        self.separate_eval = separate_eval
+        self.CLASSES = getattr(self.datasets[0], 'CLASSES', None)
+        self.cumulative_sizes = np.cumsum([len(d) for d in self.datasets]).tolist()
+        if all(hasattr(d, 'flag') for d in self.datasets):
+            self.flag = np.concatenate([d.flag for d in self.datasets])
+
+    def __len__(self):
+        return self.cumulative_sizes[-1]
+
+    def __getitem__(self, idx):
+        if idx < 0:
+            if -idx > len(self):
+                raise ValueError('absolute value of index should not exceed dataset length')
+            idx = len(self) + idx
+        which = int(np.searchsorted(self.cumulative_sizes, idx, side='right'))
+        return self.datasets[which][idx - (self.cumulative_sizes[which - 1] if which else 0)]
+
+    def evaluate(self, results, logger=None, **kwargs):
+        raise NotImplementedError('ConcatDataset.evaluate: the configs of this tree concatenate train splits only')
+
+
 def build_dataset(cfg, default_args=None):
-    """Config dict -> dataset: a list of configs is concatenated, ``RepeatDataset`` wraps the dataset it names, anything else
-    is looked up in ``DATASETS``."""
+    """Config dict -> dataset: a list of configs is concatenated, ``RepeatDataset`` and ``ConcatDataset`` wrap the datasets they
+    name, anything else is looked up in ``DATASETS``."""
     if isinstance(cfg, (list, tuple)):
-        from torch.utils.data import ConcatDataset
-        return ConcatDataset([build_dataset(c, default_args) for c in cfg])
+        from torch.utils.data import ConcatDataset as TorchConcat
+        return TorchConcat([build_dataset(c, default_args) for c in cfg])
     if cfg['type'] == 'RepeatDataset':
         return RepeatDataset(build_dataset(cfg['dataset'], default_args), cfg['times'])
-    if cfg['type'] in ('ConcatDataset', 'ClassBalancedDataset', 'CBGSDataset'):
+    if cfg['type'] == 'ConcatDataset':
+        return ConcatDataset([build_dataset(c, default_args) for c in cfg['datasets']], cfg.get('separate_eval', True))
+    if cfg['type'] in ('ClassBalancedDataset', 'CBGSDataset'):
         raise NotImplementedError(f'{cfg["type"]} is not used by configs/gga')
     return build_from_cfg(cfg, DATASETS, default_args)
 

@@ -96,17 +96,74 @@ class LoadPointsFromFile:
 
     def __init__(self, coord_type='LIDAR', load_dim=6, use_dim=[0, 1, 2], shift_height=False, use_color=False,
                  file_client_args=dict(backend='disk')):
-        assert coord_type in ('LIDAR', 'DEPTH') and not shift_height and not use_color
+        assert coord_type in ('LIDAR', 'DEPTH') and not shift_height
         self.coord_type = coord_type
         self.load_dim = load_dim
+        self.use_color = use_color
         self.use_dim = list(range(use_dim)) if isinstance(use_dim, int) else list(use_dim)
-        assert max(self.use_dim) < load_dim
+        assert max(self.use_dim) < load_dim, f'Expect all used dimensions < {load_dim}, got {use_dim}'
 
     def __call__(self, results):
         pts = np.fromfile(results['pts_filename'], dtype=np.float32).reshape(-1, self.load_dim)[:, self.use_dim]
+        attribute_dims = None
+        if self.use_color:          # the last three used columns are the colour (loading.py:447-455)
+            assert len(self.use_dim) >= 6
+            attribute_dims = dict(color=[pts.shape[1] - 3, pts.shape[1] - 2, pts.shape[1] - 1])
         points_class = DepthPoints if self.coord_type == 'DEPTH' else LiDARPoints
-        results['points'] = points_class(pts, points_dim=pts.shape[-1], attribute_dims=None)
+        results['points'] = points_class(pts, points_dim=pts.shape[-1], attribute_dims=attribute_dims)
         return results
+
+
+@PIPELINES.register_module()
+class NormalizePointsColor:
+    """loading.py:305-342: the colour columns minus ``color_mean`` (when given), divided by 255."""
+
+    def __init__(self, color_mean):
+        self.color_mean = color_mean
+
+    def __call__(self, results):
+        points = results['points']
+        assert points.attribute_dims is not None and 'color' in points.attribute_dims.keys(), 'Expect points have color attribute'
+        if self.color_mean is not None:
+            points.color = points.color - points.color.new_tensor(self.color_mean)
+        points.color = points.color / 255.0
+        results['points'] = points
+        return results
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}(color_mean={self.color_mean})'
+
+
+@PIPELINES.register_module()
+class GlobalAlignment:
+    """transforms_3d.py:605-683: the scene's points brought into the axis-aligned frame of its annotations by
+    ``ann_info['axis_align_matrix']`` [4, 4] - rotated by the transposed rotation block, then translated. Boxes are not
+    touched (ScanNet's ground truths are annotated in the aligned frame) and nothing is recorded for a way back."""
+
+    def __init__(self, rotation_axis):
+        self.rotation_axis = rotation_axis
+
+    def _check_rot_mat(self, rot_mat):
+        """A rotation about ``rotation_axis`` only: determinant 1, and that axis' row and column are the unit vector."""
+        is_valid = np.allclose(np.linalg.det(rot_mat), 1.0)
+        valid_array = np.zeros(3)
+        valid_array[self.rotation_axis] = 1.0
+        is_valid &= (rot_mat[self.rotation_axis, :] == valid_array).all()
+        is_valid &= (rot_mat[:, self.rotation_axis] == valid_array).all()
+        assert is_valid, f'invalid rotation matrix {rot_mat}'
+
+    def __call__(self, input_dict):
+        assert 'axis_align_matrix' in input_dict['ann_info'].keys(), 'axis_align_matrix is not provided in GlobalAlignment'
+        axis_align_matrix = input_dict['ann_info']['axis_align_matrix']
+        assert axis_align_matrix.shape == (4, 4), f'invalid shape {axis_align_matrix.shape} for axis_align_matrix'
+        rot_mat, trans_vec = axis_align_matrix[:3, :3], axis_align_matrix[:3, -1]
+        self._check_rot_mat(rot_mat)
+        input_dict['points'].rotate(rot_mat.T)
+        input_dict['points'].translate(trans_vec)
+        return input_dict
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}(rotation_axis={self.rotation_axis})'
 
 
 # ----------------------------------------------------------------------------- database sampling
@@ -475,10 +532,15 @@ def _rotate_points_z(points, angle):
     return rot_t
 
 
-def _no_boxes_to_move(d, what):
+def _move_boxes(d, what, *args):
+    """The box fields follow the points through the box structure's method ``what``, for the structures that declare
+    ``MOVES_WITH_POINTS`` (the Depth boxes of the indoor pipelines; the GGA train pipeline has no such transform, and its
+    LiDAR boxes are refused as before)."""
     for field in d.get('bbox3d_fields', []):
         if len(d[field]):
-            raise NotImplementedError(f'{what} of 3D boxes is not on the GGA path (its train pipeline has no such transform)')
+            if not getattr(d[field], 'MOVES_WITH_POINTS', False):
+                raise NotImplementedError(f'{what} of {type(d[field]).__name__} is not on the GGA path (its train pipeline has no such transform)')
+            getattr(d[field], what)(*args)
 
 
 @PIPELINES.register_module()
@@ -492,18 +554,18 @@ class GlobalRotScaleTrans:
     def __call__(self, d):
         d.setdefault('transformation_3d_flow', [])
         angle = np.random.uniform(self.rot_range[0], self.rot_range[1])          # the draws come in this order: rotation,
-        if angle != 0:
-            _no_boxes_to_move(d, 'rotation')
         d['pcd_rotation'] = _rotate_points_z(d['points'], angle)
+        if angle != 0:
+            _move_boxes(d, 'rotate', d['pcd_rotation'])
         d['pcd_rotation_angle'] = angle
         if 'pcd_scale_factor' not in d:                                        # scale (unless the test-time wrapper fixed it),
             d['pcd_scale_factor'] = np.random.uniform(self.scale_ratio_range[0], self.scale_ratio_range[1])
         if d['pcd_scale_factor'] != 1:
-            _no_boxes_to_move(d, 'scaling')
+            _move_boxes(d, 'scale', d['pcd_scale_factor'])
             d['points'].tensor[:, :3] *= d['pcd_scale_factor']
         shift = np.random.normal(scale=np.array(self.translation_std, dtype=np.float32), size=3).T      # translation
         if np.any(shift != 0):
-            _no_boxes_to_move(d, 'translation')
+            _move_boxes(d, 'translate', shift)
             d['points'].tensor[:, :3] += d['points'].tensor.new_tensor(shift)
         d['pcd_trans'] = shift
         d['transformation_3d_flow'].extend(['R', 'S', 'T'])
@@ -513,7 +575,8 @@ class GlobalRotScaleTrans:
 @PIPELINES.register_module()
 class RandomFlip3D:
     """Flips decided upstream (``flip`` / ``pcd_horizontal_flip`` / ``pcd_vertical_flip`` set by MultiScaleFlipAug3D) or drawn
-    with the given ratios; LiDAR points: horizontal = y -> -y, vertical = x -> -x."""
+    with the given ratios; LiDAR points: horizontal = y -> -y, vertical = x -> -x; Depth points: horizontal = x -> -x,
+    vertical = y -> -y (the coordinate systems' own ``flip``)."""
 
     def __init__(self, sync_2d=True, flip_ratio_bev_horizontal=0.0, flip_ratio_bev_vertical=0.0, **kwargs):
         self.sync_2d, self.h_ratio, self.v_ratio = sync_2d, flip_ratio_bev_horizontal, flip_ratio_bev_vertical
@@ -528,9 +591,10 @@ class RandomFlip3D:
             if 'pcd_vertical_flip' not in d:
                 d['pcd_vertical_flip'] = bool(np.random.rand() < self.v_ratio)
         d.setdefault('transformation_3d_flow', [])
-        for flag, axis, tag in (('pcd_horizontal_flip', 1, 'HF'), ('pcd_vertical_flip', 0, 'VF')):
+        for flag, direction, tag in (('pcd_horizontal_flip', 'horizontal', 'HF'), ('pcd_vertical_flip', 'vertical', 'VF')):
             if d[flag]:
-                _no_boxes_to_move(d, 'flipping')
+                _move_boxes(d, 'flip', direction)
+                axis = d['points'].FLIP_AXIS[direction]
                 d['points'].tensor[:, axis] = -d['points'].tensor[:, axis]
                 d['transformation_3d_flow'].append(tag)
         return d

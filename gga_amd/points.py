@@ -1,7 +1,10 @@
 """``LiDARPoints`` / ``DepthPoints`` — the slice of the reference's point structure the GGA train pipeline touches
 (mmdet3d/core/points/base_points.py:11-440, lidar_points.py): ``tensor [N, points_dim]``,
 ``coord``, ``in_range_3d`` (strict inequalities, :203-225), ``shuffle`` (``torch.randperm``,
-:135-143), ``cat`` (:356-377), indexing, ``new_point``."""
+:135-143), ``cat`` (:356-377), indexing, ``new_point``; for the indoor pipelines ``color`` (:96-128), ``rotate`` by a matrix (:151-190),
+``translate`` (:192-216)."""
+import warnings
+
 import numpy as np
 import torch
 
@@ -23,8 +26,51 @@ class BasePoints:
         return self.tensor[:, :3]
 
     @property
+    def color(self):
+        """[N, 3] colour columns named by ``attribute_dims['color']``, or None when the points carry none."""
+        if self.attribute_dims is not None and 'color' in self.attribute_dims:
+            return self.tensor[:, self.attribute_dims['color']]
+        return None
+
+    @color.setter
+    def color(self, tensor):
+        try:
+            tensor = tensor.reshape(self.shape[0], 3)
+        except (RuntimeError, ValueError):
+            raise ValueError(f'got unexpected shape {tensor.shape}')
+        if tensor.max() >= 256 or tensor.min() < 0:
+            warnings.warn('point got color value beyond [0, 255]')
+        if not isinstance(tensor, torch.Tensor):
+            tensor = self.tensor.new_tensor(tensor)
+        if self.attribute_dims is not None and 'color' in self.attribute_dims:
+            self.tensor[:, self.attribute_dims['color']] = tensor
+        else:                                   # points without colour gain three columns
+            if self.attribute_dims is None:
+                self.attribute_dims = dict()
+            first = self.shape[1]
+            self.tensor = torch.cat([self.tensor, tensor], dim=1)
+            self.attribute_dims.update(dict(color=[first, first + 1, first + 2]))
+            self.points_dim += 3
+
+    @property
     def shape(self):
         return self.tensor.shape
+
+    def rotate(self, rot_mat_t):
+        """Row vectors times the 3 x 3 matrix ``rot_mat_t`` (the transposed rotation), in place. -> the matrix as a tensor."""
+        rot_mat_t = self.tensor.new_tensor(rot_mat_t) if not isinstance(rot_mat_t, torch.Tensor) else rot_mat_t
+        assert rot_mat_t.shape == torch.Size([3, 3]), f'invalid rotation shape {rot_mat_t.shape}'
+        self.tensor[:, :3] = self.tensor[:, :3] @ rot_mat_t
+        return rot_mat_t
+
+    def translate(self, trans_vector):
+        """[3] (or [1, 3] / [N, 3]) added to the coordinates, in place."""
+        if not isinstance(trans_vector, torch.Tensor):
+            trans_vector = self.tensor.new_tensor(trans_vector)
+        trans_vector = trans_vector.squeeze(0)
+        assert trans_vector.dim() == 1 and trans_vector.numel() == 3 or trans_vector.shape == (len(self), 3), \
+            f'Unsupported translation vector of shape {trans_vector.shape}'
+        self.tensor[:, :3] += trans_vector
 
     @property
     def bev(self):
@@ -83,6 +129,8 @@ class BasePoints:
 
 
 class LiDARPoints(BasePoints):
+    FLIP_AXIS = dict(horizontal=1, vertical=0)         # lidar_points.py: a horizontal flip negates y, a vertical one x
+
     def __init__(self, tensor, points_dim=3, attribute_dims=None):
         super().__init__(tensor, points_dim=points_dim, attribute_dims=attribute_dims)
         self.rotation_axis = 2
@@ -90,6 +138,7 @@ class LiDARPoints(BasePoints):
 
 class DepthPoints(BasePoints):
     """depth_points.py: points in depth coordinates (indoor scenes); rotation about z like the LiDAR points."""
+    FLIP_AXIS = dict(horizontal=0, vertical=1)         # depth_points.py: a horizontal flip negates x, a vertical one y
 
     def __init__(self, tensor, points_dim=3, attribute_dims=None):
         super().__init__(tensor, points_dim=points_dim, attribute_dims=attribute_dims)

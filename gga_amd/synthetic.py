@@ -608,6 +608,113 @@ def write_sunrgbd_tree(root, n_frames, seed=5100, n_points=2000, n_obj_range=(0,
     return paths
 
 
+SCANNET_CLASSES = ('cabinet', 'bed', 'chair', 'sofa', 'table', 'door', 'window', 'bookshelf', 'picture', 'counter', 'desk', 'curtain',
+                   'refrigerator', 'showercurtrain', 'toilet', 'sink', 'bathtub', 'garbagebin')
+S3DIS_CLASSES = ('table', 'chair', 'sofa', 'bookcase', 'board')
+
+
+def _axis_aligned_room(rng, n_points, n_obj, n_classes):
+    """One synthetic room in its axis-aligned frame: a floor and ``n_obj`` filled axis-aligned boxes, colour in 0..255 (the
+    ScanNet / S3DIS convention). -> (cloud [n_points, 6] f64, boxes [n_obj, 6] gravity centre + sizes, labels [n_obj])."""
+    size = rng.uniform([0.4, 0.4, 0.4], [2.0, 1.6, 1.2], (n_obj, 3))
+    ctr = np.concatenate([rng.uniform(-2.0, 2.0, (n_obj, 2)), size[:, 2:] / 2 + rng.uniform(0, 0.3, (n_obj, 1))], 1)
+    labels = rng.integers(0, n_classes, n_obj)
+    n_bg = n_points // 2 if n_obj else n_points
+    pts = [np.concatenate([rng.uniform(-2.5, 2.5, (n_bg, 2)), rng.normal(0, 0.004, (n_bg, 1))], 1)]
+    for k in range(n_obj):
+        n_k = (n_points - n_bg) // n_obj if k < n_obj - 1 else n_points - n_bg - (n_points - n_bg) // n_obj * (n_obj - 1)
+        pts.append(rng.uniform(-0.5, 0.5, (n_k, 3)) * size[k] + ctr[k])
+    xyz = np.concatenate(pts)
+    cloud = np.concatenate([xyz, np.floor(rng.uniform(0, 256, (len(xyz), 3)))], 1)
+    return cloud[rng.permutation(len(cloud))], np.concatenate([ctr, size], 1), labels
+
+
+def _write_room_files(root, name, cloud, rng):
+    """points / instance_mask / semantic_mask ``.bin`` files of one room -> the three relative paths."""
+    import os
+    for sub in ('points', 'instance_mask', 'semantic_mask'):
+        os.makedirs(os.path.join(root, sub), exist_ok=True)
+    cloud.astype(np.float32).tofile(os.path.join(root, 'points', f'{name}.bin'))
+    rng.integers(0, 8, len(cloud)).astype(np.int64).tofile(os.path.join(root, 'instance_mask', f'{name}.bin'))
+    rng.integers(0, 20, len(cloud)).astype(np.int64).tofile(os.path.join(root, 'semantic_mask', f'{name}.bin'))
+    return f'points/{name}.bin', f'instance_mask/{name}.bin', f'semantic_mask/{name}.bin'
+
+
+def write_scannet_tree(root, n_frames, seed=5200, n_points=2000, n_obj_range=(0, 9), empty_frames=(1, ), no_matrix_frames=(2, )):
+    """Writes what ``ScanNetDataset`` reads (reference: tools/data_converter/scannet_data_utils.py ``get_infos``) for ``n_frames``
+    synthetic rooms under ``root``, modelled on ``write_sunrgbd_tree``:
+
+        points/scene%04d_00.bin                 [n_points,6] f32: x, y, z in the scan's own (unaligned) frame, r, g, b in 0..255
+        instance_mask/, semantic_mask/          one int64 per point
+        scannet_infos_train.pkl / _val.pkl      the info list: point_cloud, pts_path, the two mask paths, annos
+
+    ``annos``: ``gt_num``, ``name``, ``class``, ``gt_boxes_upright_depth`` [k,6] (gravity centre, sizes) in the axis-aligned
+    frame, ``location``, ``dimensions``, ``index`` and ``axis_align_matrix`` [4,4] f64: a rotation about z plus a translation
+    that takes the stored points into the boxes' frame. The frames of ``no_matrix_frames`` omit the key (their points are stored
+    aligned); the frames of ``empty_frames`` have no objects (``gt_num = 0`` and, at most, the matrix). Both pickles hold the
+    same frames. Deterministic in ``seed``. -> (train info path, val info path)."""
+    import os
+    import pickle
+    names = np.array(SCANNET_CLASSES)
+    infos = []
+    for i in range(n_frames):
+        rng = np.random.default_rng(seed + i)
+        n_obj = 0 if i in empty_frames else int(rng.integers(max(n_obj_range[0], 1), n_obj_range[1] + 1))
+        cloud, boxes, labels = _axis_aligned_room(rng, n_points, n_obj, len(SCANNET_CLASSES))
+        annos = dict(gt_num=n_obj)
+        if n_obj:
+            annos.update(name=names[labels], **{'class': labels.astype(np.int64)}, gt_boxes_upright_depth=boxes, location=boxes[:, :3],
+                         dimensions=boxes[:, 3:], index=np.arange(n_obj, dtype=np.int32))
+        if i not in no_matrix_frames:
+            angle, shift = rng.uniform(0.3, 2.8), rng.uniform(-3, 3, 3)
+            c, s_ = np.cos(angle), np.sin(angle)
+            matrix = np.eye(4)
+            matrix[:3, :3], matrix[:3, 3] = [[c, -s_, 0], [s_, c, 0], [0, 0, 1]], shift
+            cloud[:, :3] = (cloud[:, :3] - shift) @ matrix[:3, :3]         # aligned = stored @ R.T + t
+            annos['axis_align_matrix'] = matrix
+        name = f'scene{i:04d}_00'
+        pts_path, inst_path, sem_path = _write_room_files(root, name, cloud, rng)
+        infos.append(dict(point_cloud=dict(num_features=6, lidar_idx=name), pts_path=pts_path, pts_instance_mask_path=inst_path,
+                          pts_semantic_mask_path=sem_path, annos=annos))
+    paths = tuple(os.path.join(root, f'scannet_infos_{split}.pkl') for split in ('train', 'val'))
+    for path in paths:
+        with open(path, 'wb') as f:
+            pickle.dump(infos, f)
+    return paths
+
+
+def write_s3dis_tree(root, rooms_per_area, areas=(1, 2, 5), seed=5300, n_points=2000, n_obj_range=(0, 9), empty_rooms=((1, 1), )):
+    """Writes what ``S3DISDataset`` reads (reference: tools/data_converter/s3dis_data_utils.py ``get_infos``): for every area of
+    ``areas`` ``rooms_per_area`` synthetic rooms and one info file,
+
+        points/Area_%d_room_%d.bin              [n_points,6] f32: x, y, z, r, g, b in 0..255
+        instance_mask/, semantic_mask/          one int64 per point
+        s3dis_infos_Area_%d.pkl                 the area's info list: point_cloud, pts_path, the two mask paths, annos
+
+    ``annos``: ``gt_num``, ``class``, ``gt_boxes_upright_depth`` [k,6] (gravity centre, sizes); the (area, room) pairs of
+    ``empty_rooms`` have no objects. Deterministic in ``seed``. -> {area: info path}."""
+    import os
+    import pickle
+    paths = {}
+    for area in areas:
+        infos = []
+        for r in range(rooms_per_area):
+            rng = np.random.default_rng(seed + 100 * area + r)
+            n_obj = 0 if (area, r) in empty_rooms else int(rng.integers(max(n_obj_range[0], 1), n_obj_range[1] + 1))
+            cloud, boxes, labels = _axis_aligned_room(rng, n_points, n_obj, len(S3DIS_CLASSES))
+            annos = dict(gt_num=n_obj)
+            if n_obj:
+                annos.update(gt_boxes_upright_depth=boxes, **{'class': labels.astype(np.int64)})
+            name = f'Area_{area}_room_{r}'
+            pts_path, inst_path, sem_path = _write_room_files(root, name, cloud, rng)
+            infos.append(dict(point_cloud=dict(num_features=6, lidar_idx=name), pts_path=pts_path, pts_instance_mask_path=inst_path,
+                              pts_semantic_mask_path=sem_path, annos=annos))
+        paths[area] = os.path.join(root, f's3dis_infos_Area_{area}.pkl')
+        with open(paths[area], 'wb') as f:
+            pickle.dump(infos, f)
+    return paths
+
+
 def make_indoor_eval_case(seed, n_frames, n_classes=10, gt_range=(0, 9), dt_range=(0, 40)):
     """Seeded SUN RGB-D-shaped ground truths and detections for ``indoor_eval``: per frame ``gt_range`` boxes of random classes
     and ``dt_range`` detections - most of them a jittered copy of a ground truth of the frame with its class (so every IoU level

@@ -912,6 +912,28 @@ int gga_centerpoint_detect(const float* boxes, const float* scores, const float*
                            float* out_scores, int32_t* out_labels, int32_t* out_count, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Per-class 3D NMS of a whole batch in a fixed number of launches: the loop of FCAF3DHead._nms
+ * (mmdet3d/models/dense_heads/fcaf3d_head.py: per scene, per class, mmcv's nms3d / nms3d_normal) for every (scene, class)
+ * pair at once, with nothing read back in between. boxes [n,7] f32 = (x, y, z, dx, dy, dz, heading), heading 0 for an
+ * axis-aligned head; scores [n, n_classes] f32; scene [n] i64, rows in any order (the rows of a scene need not be contiguous).
+ * Per scene, for each class c in ascending order: the candidates are the scene's rows with scores[., c] > score_thr (strict;
+ * a NaN score is no candidate), taken by descending score with ties in input order (a stable sort); greedy NMS on the BEV
+ * rectangle (x, y, dx, dy, heading): a kept box suppresses every later one whose rotated IoU with it (the exact polygon overlap
+ * of gga_box_iou_rotated, the same float operations as gga_nms_rotated_sorted, the earlier box first) is > iou_thr. No cap on
+ * the number kept. out_row / out_class [n * n_classes] i32: the input row and the class of every kept detection, packed scene
+ * by scene, within a scene class-ascending, within a class by descending score; out_count [n_scenes] i32: the detections of
+ * each scene (scene s begins at the sum of the counts before it). Entries behind the last detection are not written. A row
+ * whose scene lies outside [0, n_scenes) is never kept. n == 0 writes zero counts.
+ * GGA_ERR_INVALID_ARG before any launch for: n < 0; n_classes outside 1..GGA_MULTICLASS_NMS_MAX_CLASSES; n_scenes outside
+ * 1..2^20; n * n_classes >= 2^31; a null out_count; any other null pointer while n > 0; a workspace smaller than
+ * gga_multiclass_nms3d_workspace_bytes (0 for sizes it refuses). Launches: one memset, the key kernel, rocPRIM's radix sort,
+ * the segment, NMS and pack kernels - their number does not depend on n_scenes or n_classes. */
+#define GGA_MULTICLASS_NMS_MAX_CLASSES 128
+size_t gga_multiclass_nms3d_workspace_bytes(int64_t n, int n_classes, int n_scenes);
+int gga_multiclass_nms3d(const float* boxes, const float* scores, const int64_t* scene, int64_t n, int n_classes, int n_scenes,
+                         float score_thr, float iou_thr, int32_t* out_row, int32_t* out_class, int32_t* out_count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Test-time augmentation: the head maps of all views of a batch merged per scale group in one launch. Restates the per-view
  * torch.flip / slice-assign / `+=` / `/=` sequence of mmdet3d/models/detectors/centerpoint_gga.py:123-182 (aug_test_pts).
  * A map is a contiguous f32 [n_views * n_frames, channels, H, W] tensor, view-major (view v of frame f is row v * n_frames + f);

@@ -1849,6 +1849,139 @@ def golden_tta(ref):
     np.savez_compressed(os.path.join(OUT, 'tta.npz'), **out)
 
 
+INDOOR_CONFIG_SECTIONS = ('model', 'optimizer', 'optimizer_config', 'lr_config', 'runner', 'checkpoint_config', 'custom_hooks', 'data',
+                          'train_pipeline', 'test_pipeline')
+INDOOR_CONFIGS = ('configs/fcaf3d/fcaf3d_8x2_scannet-3d-18class.py', 'configs/fcaf3d/fcaf3d_8x2_s3dis-3d-5class.py')
+INDOOR_TREE = dict(scannet=dict(n_frames=4, n_points=300), s3dis=dict(rooms_per_area=2, n_points=300))
+
+
+def _reference_class(relpath, name, namespace):
+    """One class of a reference file, taken out by name at run time (the file's own imports need packages that are absent)."""
+    import ast
+    src = open(os.path.join(REF, relpath)).read()
+    node = [n for n in ast.parse(src).body if isinstance(n, ast.ClassDef) and n.name == name]
+    node[0].decorator_list = []
+    ns = dict(namespace)
+    exec(compile(ast.Module(body=node, type_ignores=[]), os.path.basename(relpath), 'exec'), ns)
+    return ns[name]
+
+
+def golden_indoor_datasets(ref):
+    """The reference's ``ScanNetDataset`` / ``S3DISDataset`` (mmdet3d/datasets/scannet_dataset.py, s3dis_dataset.py over
+    custom_3d.py) and its ``GlobalAlignment`` / ``NormalizePointsColor`` steps on the synthetic trees of
+    ``synthetic.write_scannet_tree`` / ``write_s3dis_tree``: ``get_ann_info``, ``get_data_info`` (train mode: which frames
+    ``filter_empty_gt`` drops), ``prepare_test_data`` through [load, align, normalise], and the two steps alone (the
+    normalisation also with a colour mean). Paths are stored relative to the tree's root. Arrays and lists of names only.
+    Also writes reference_configs_indoor.json: the two reference configs resolved by ``golden_configs``' recipe."""
+    import json
+    import pickle
+    import tempfile
+    import warnings
+    from gga_amd import Config
+    import_reference_pipeline(ref)
+    dp = load('mmdet3d.core.points.depth_points', 'mmdet3d/core/points/depth_points.py')
+    for name in ('cam_box3d', 'depth_box3d', 'box_3d_mode'):
+        load(f'mmdet3d.core.bbox.structures.{name}', f'mmdet3d/core/bbox/structures/{name}.py')
+    cb = sys.modules['mmdet3d.core.bbox']
+    cb.DepthInstance3DBoxes = sys.modules['mmdet3d.core.bbox.structures.depth_box3d'].DepthInstance3DBoxes
+    cb.get_box_type = ref['su'].get_box_type
+    core = sys.modules['mmdet3d.core']
+    core.instance_seg_eval = core.show_result = core.show_seg_result = None
+    core.bbox = cb
+
+    def pkl_load(path, file_format='pkl'):
+        with open(path, 'rb') as f:
+            return pickle.load(f)
+
+    sys.modules['mmcv'].FileClient = lambda **kw: None
+    sys.modules['mmcv'].load = pkl_load
+    _mod('mmseg')
+    _mod('mmseg.datasets', DATASETS=_Reg())
+    sys.modules['mmdet3d.datasets.builder'].DATASETS = _Reg()
+
+    class Compose:                               # (mmdet's: the steps in turn; here they are given as callables)
+        def __init__(self, transforms):
+            self.transforms = transforms
+
+        def __call__(self, data):
+            for t in self.transforms:
+                data = t(data)
+            return data
+
+    sys.modules['mmdet3d.datasets.pipelines'].Compose = Compose
+    _mod('mmdet3d.datasets.utils', extract_result_dict=None, get_loading_pipeline=None)
+    load('mmdet3d.datasets.custom_3d', 'mmdet3d/datasets/custom_3d.py')
+    _mod('mmdet3d.datasets.custom_3d_seg', Custom3DSegDataset=object)
+    sd = load('mmdet3d.datasets.scannet_dataset', 'mmdet3d/datasets/scannet_dataset.py')
+    s3 = load('mmdet3d.datasets.s3dis_dataset', 'mmdet3d/datasets/s3dis_dataset.py')
+    GlobalAlignment = _reference_class('mmdet3d/datasets/pipelines/transforms_3d.py', 'GlobalAlignment', dict(np=np))
+    NormalizePointsColor = _reference_class('mmdet3d/datasets/pipelines/loading.py', 'NormalizePointsColor', dict(np=np))
+
+    def load_points(results):                    # LoadPointsFromFile(coord_type='DEPTH', use_color=True, load_dim=6, use_dim=6)
+        pts = np.fromfile(results['pts_filename'], dtype=np.float32).reshape(-1, 6)
+        results['points'] = dp.DepthPoints(pts, points_dim=6, attribute_dims=dict(color=[3, 4, 5]))
+        return results
+
+    out = {}
+
+    def record(tag, ds_train, ds_test, root, with_matrix):
+        rel = lambda path: os.path.relpath(path, root)
+        out[f'{tag}.classes'] = np.array(ds_train.CLASSES)
+        out[f'{tag}.n'] = np.int64(len(ds_train))
+        kept = []
+        for i in range(len(ds_train)):
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                ann, info, test = ds_train.get_ann_info(i), ds_train.get_data_info(i), ds_test.prepare_test_data(i)
+            kept.append(info is not None)
+            out[f'{tag}.{i}.boxes'] = ann['gt_bboxes_3d'].tensor.numpy()
+            out[f'{tag}.{i}.labels'] = ann['gt_labels_3d']
+            out[f'{tag}.{i}.mask_paths'] = np.array([rel(ann['pts_instance_mask_path']), rel(ann['pts_semantic_mask_path'])])
+            if with_matrix:
+                out[f'{tag}.{i}.matrix'] = ann['axis_align_matrix']
+            if info is not None:
+                out[f'{tag}.{i}.info_keys'] = np.array(sorted(info))
+                out[f'{tag}.{i}.pts_filename'] = np.array(rel(info['pts_filename']))
+                if 'sample_idx' in info:
+                    out[f'{tag}.{i}.sample_idx'] = np.array(info['sample_idx'])
+            out[f'{tag}.{i}.test_keys'] = np.array(sorted(k for k in test if k != 'points'))
+            out[f'{tag}.{i}.test_points'] = test['points'].tensor.numpy()
+        out[f'{tag}.kept'] = np.array(kept)
+
+    with tempfile.TemporaryDirectory() as root:
+        train, val = synthetic.write_scannet_tree(root, **INDOOR_TREE['scannet'])
+        steps = [load_points, GlobalAlignment(rotation_axis=2), NormalizePointsColor(color_mean=None)]
+        record('scannet', sd.ScanNetDataset(root, train, pipeline=steps), sd.ScanNetDataset(root, val, pipeline=steps, test_mode=True), root, True)
+        # the two steps alone, on the first scan
+        d = load_points(dict(pts_filename=os.path.join(root, 'points', 'scene0000_00.bin')))
+        out['align.in'] = d['points'].tensor.numpy().copy()
+        out['align.matrix'] = out['scannet.0.matrix']
+        d['ann_info'] = dict(axis_align_matrix=out['align.matrix'])
+        out['align.out'] = GlobalAlignment(rotation_axis=2)(d)['points'].tensor.numpy().copy()
+        mean = [120.5, 110.25, 98.0]
+        out['color.mean'] = np.array(mean)
+        out['color.out_mean'] = NormalizePointsColor(color_mean=mean)(load_points(dict(pts_filename=d['pts_filename'])))['points'].tensor.numpy()
+        out['color.out'] = NormalizePointsColor(color_mean=None)(load_points(dict(pts_filename=d['pts_filename'])))['points'].tensor.numpy()
+    with tempfile.TemporaryDirectory() as root:
+        paths = synthetic.write_s3dis_tree(root, **INDOOR_TREE['s3dis'])
+        steps = [load_points, NormalizePointsColor(color_mean=None)]
+        for area, path in paths.items():
+            record(f's3dis{area}', s3.S3DISDataset(root, path, pipeline=steps), s3.S3DISDataset(root, path, pipeline=steps, test_mode=True), root,
+                   False)
+        out['s3dis.areas'] = np.array(sorted(paths), np.int64)
+    np.savez_compressed(os.path.join(OUT, 'indoor_datasets.npz'), **out)
+    print('  indoor datasets:', len(out), 'arrays; scannet frames kept by filter_empty_gt:', out['scannet.kept'].tolist())
+
+    cfgs = {}
+    for relpath in INDOOR_CONFIGS:
+        cfg = Config.fromfile(os.path.join(REF, relpath))
+        cfgs[relpath] = {k: plain_config(cfg[k]) for k in INDOOR_CONFIG_SECTIONS}
+    assert json.loads(json.dumps(cfgs)) == cfgs, 'a config section does not survive JSON'
+    with open(os.path.join(OUT, 'reference_configs_indoor.json'), 'w') as f:
+        json.dump(cfgs, f, indent=1, sort_keys=True)
+        f.write('\n')
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -1874,6 +2007,7 @@ def main():
     golden_configs(ref)
     golden_dynamic_voxel(ref)
     golden_tta(ref)
+    golden_indoor_datasets(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
