@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _lib = None
 
@@ -139,18 +139,16 @@ SIGNATURES = {
     'gga_dense_wgrad3x3_block_amax': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, i32, i32, vp, i32, vp, i32, vp, sz, vp]),
     'gga_dense_conv3x3_tile_rows': (i32, [i32, i32, i32, i32, i32]),
     'gga_dense_conv3x3_stat_rows': (i64, [i32, i32, i32, i32, i32, i32]),
-    'gga_bn_stats_partials': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, i32, vp]),
-    'gga_bn_stats_partials_cols': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
     'gga_bn_relu_workspace_bytes': (sz, [i64, i32]),
     'gga_bn_relu_mask_bytes': (sz, [i64, i32]),
-    'gga_bn_relu_fwd_ex': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, sz, vp]),
-    'gga_bn_relu_bwd_ex': (i32, [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'gga_bn_relu_fwd': (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, sz, vp]),
+    'gga_bn_relu_bwd': (i32, [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_column_sums': (i32, [vp, i64, i32, vp, vp, sz, vp]),
     'gga_bn_relu_bwd_partials': (i32, [vp, i64, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     'gga_gn_relu_workspace_bytes': (sz, [i32, i32]),
     'gga_gn_relu_fwd': (i32, [vp, vp, vp, i32, i64, i32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'gga_gn_relu_bwd': (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    'gga_bn_stats': (i32, [vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, vp, vp, vp, sz, vp]),
+    'gga_bn_stats': (i32, [vp, vp, vp, vp, vp, i64, i32, f32, f32, i32, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     'gga_head_conv3x3_fwd': (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     'gga_head_conv3x3_fwd_tiles': (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     'gga_head_cell_tiles_count': (i64, [i32, i32, i32]),

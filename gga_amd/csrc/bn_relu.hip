@@ -368,144 +368,156 @@ static int bn_check(const char* fn, int64_t rows, int C) {
     return GGA_OK;
 }
 
-static int bn_fwd_impl(const float* x, const float* residual, const float* gamma, const float* beta,
-                       float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                       float momentum, int training, int relu, float* y, int64_t y_row_stride,
-                       void* mask_bits, float* saved, const double* given_partials, int n_given, void* workspace,
-                       size_t workspace_bytes, void* stream_, uint32_t* amax_y = nullptr) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_relu_fwd_ex", rows, channels)) return rc;
-    GGA_REQUIRE(y_row_stride >= channels && y_row_stride % 4 == 0 && ((uintptr_t)y & 15) == 0,
-                "gga_bn_relu_fwd_ex: y row stride %lld must be a multiple of 4 floats >= channels, y 16 B aligned",
-                (long long)y_row_stride);
-    GGA_REQUIRE(x && y && saved && workspace && running_mean && running_var && (!relu || mask_bits),
-                "gga_bn_relu_fwd_ex: null pointer argument");
+// the strided operand (y in forward, grad_y in backward) of the entry point `fn`
+static int bn_check_strided(const char* fn, const char* what, const void* p, int64_t row_stride, int channels) {
+    GGA_REQUIRE(row_stride >= channels && row_stride % 4 == 0 && ((uintptr_t)p & 15) == 0,
+                "%s: %s row stride %lld must be a multiple of 4 floats >= channels, %s 16 B aligned", fn, what,
+                (long long)row_stride, what);
+    return GGA_OK;
+}
+
+static int bn_check_workspace(const char* fn, int64_t rows, int channels, size_t workspace_bytes) {
     if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_relu_fwd_ex: workspace too small");
+        gga_set_error("%s: workspace too small", fn);
         return GGA_ERR_WORKSPACE;
     }
+    return GGA_OK;
+}
+
+// workspace: [BN_MAX_BLOCKS][2][C] f64 partial sums, then 3 * C floats (forward: scale / shift; backward: the coefficient table)
+static float* bn_workspace_floats(void* workspace, int channels) {
+    return (float*)((char*)workspace + (size_t)BN_MAX_BLOCKS * 2 * channels * sizeof(double));
+}
+
+// ---- the three steps, forward and backward: every kernel of this file is launched from one place
+static int bn_reduce_fwd(const float* x, const BnGeom& g, int nb, double* partials, hipStream_t stream) {
+    hipLaunchKernelGGL(bn_reduce_kernel<false>, dim3(nb), dim3(256), 0, stream, (const float4*)x, (const float4*)nullptr,
+                       (const unsigned long long*)nullptr, (const float*)nullptr, g, 0, partials);
+    GGA_CHECK_LAUNCH("bn_reduce_kernel<fwd>");
+    return GGA_OK;
+}
+
+// Statistics of x [rows, channels] into saved / scale_shift: from `partials` (batch statistics whatever `training` says;
+// columns off .. of rows Cw wide, Cw = 0: channels wide) or, without them, from a reduce pass over x into the workspace
+// (training) or from the running statistics.
+static int bn_stats_run(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                        int64_t rows, int channels, float eps, float momentum, int training, float* saved, float* scale_shift,
+                        const double* partials, int n_partials, int Cw, int off, void* workspace, const BnGeom& g, int nb,
+                        hipStream_t stream) {
+    if (!partials && training)
+        if (int rc = bn_reduce_fwd(x, g, nb, (double*)workspace, stream)) return rc;
+    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream,
+                       partials ? partials : (const double*)workspace, partials ? n_partials : nb, channels, (double)rows, gamma,
+                       beta, eps, momentum, partials ? 1 : training, running_mean, running_var, saved, scale_shift, Cw, off);
+    GGA_CHECK_LAUNCH("bn_fwd_final_kernel");
+    return GGA_OK;
+}
+
+// Library-internal: fold [nblocks][2][C] partial sums into grad_gamma / grad_beta and the coefficient table the apply passes
+// read (returned in *coef, inside the workspace). training = 0: the statistics did not depend on x (see bn_bwd_final_kernel).
+int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64_t rows, const float* gamma,
+                        const float* saved, float* grad_gamma, float* grad_beta, int training, void* workspace, float** coef,
+                        hipStream_t stream) {
+    *coef = bn_workspace_floats(workspace, channels);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, nblocks, channels,
+                       (double)rows, gamma, saved, grad_gamma, grad_beta, *coef, training);
+    GGA_CHECK_LAUNCH("bn_bwd_final_kernel");
+    return GGA_OK;
+}
+
+static int bn_bwd_apply(const float* grad_y, const float* x, const void* mask_bits, const float* saved, const float* coef,
+                        const BnGeom& g, int nb, int relu, float* grad_x, float* grad_residual, uint32_t* amax_grad_x,
+                        hipStream_t stream) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)grad_y, (const float4*)x,
+                       (const unsigned long long*)mask_bits, saved, coef, g, relu, (float4*)grad_x, (float4*)grad_residual,
+                       amax_grad_x);
+    GGA_CHECK_LAUNCH("bn_bwd_apply_kernel");
+    return GGA_OK;
+}
+
+// ---- entry points
+extern "C" int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            int64_t rows, int channels, float eps, float momentum, int training, float* saved,
+                            float* scale_shift, const double* partials, int n_partials, int partials_width, int column_offset,
+                            void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* fn = "gga_bn_stats";
+    if (int rc = bn_check(fn, rows, channels)) return rc;
+    GGA_REQUIRE(x || partials, "%s: x and partials are both null", fn);
+    GGA_REQUIRE(saved && scale_shift && running_mean && running_var, "%s: null pointer argument", fn);
+    if (partials) {
+        GGA_REQUIRE(n_partials >= 1, "%s: n_partials %d < 1", fn, n_partials);
+        GGA_REQUIRE(column_offset >= 0 && partials_width >= column_offset + channels, "%s: columns %d .. %d of rows %d wide", fn,
+                    column_offset, column_offset + channels, partials_width);
+    } else {
+        GGA_REQUIRE(workspace, "%s: null pointer argument", fn);
+        if (int rc = bn_check_workspace(fn, rows, channels, workspace_bytes)) return rc;
+        partials_width = column_offset = 0;
+    }
+    const BnGeom g = bn_geom(rows, channels, channels);
+    return bn_stats_run(x, gamma, beta, running_mean, running_var, rows, channels, eps, momentum, training, saved, scale_shift,
+                        partials, n_partials, partials_width, column_offset, workspace, g, bn_grid(g.n4), (hipStream_t)stream_);
+}
+
+extern "C" int gga_bn_relu_fwd(const float* x, const float* residual, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, int64_t rows, int channels, float eps,
+                               float momentum, int training, int relu, float* y, int64_t y_row_stride, void* mask_bits,
+                               float* saved, const double* partials, int n_partials, uint32_t* amax_y, void* workspace,
+                               size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* fn = "gga_bn_relu_fwd";
+    if (int rc = bn_check(fn, rows, channels)) return rc;
+    if (int rc = bn_check_strided(fn, "y", y, y_row_stride, channels)) return rc;
+    GGA_REQUIRE(x && y && saved && workspace && running_mean && running_var && (!relu || mask_bits),
+                "%s: null pointer argument", fn);
+    if (int rc = bn_check_workspace(fn, rows, channels, workspace_bytes)) return rc;
     const BnGeom g = bn_geom(rows, channels, y_row_stride);
     const int nb = bn_grid(g.n4);
-    const double* partials = given_partials ? given_partials : (const double*)workspace;
-    float* scale_shift = (float*)((char*)workspace + (size_t)BN_MAX_BLOCKS * 2 * channels * sizeof(double));
-    if (training && !given_partials) {
-        hipLaunchKernelGGL(bn_reduce_kernel<false>, dim3(nb), dim3(256), 0, stream, (const float4*)x, (const float4*)nullptr,
-                           (const unsigned long long*)nullptr, (const float*)nullptr, g, 0, (double*)workspace);
-        GGA_CHECK_LAUNCH("bn_reduce_kernel<fwd>");
-    }
-    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials,
-                       given_partials ? n_given : nb, channels,
-                       (double)rows, gamma, beta, eps, momentum, training, running_mean, running_var, saved,
-                       scale_shift);
-    GGA_CHECK_LAUNCH("bn_fwd_final_kernel");
+    float* scale_shift = bn_workspace_floats(workspace, channels);
+    if (int rc = bn_stats_run(x, gamma, beta, running_mean, running_var, rows, channels, eps, momentum, training, saved,
+                              scale_shift, partials, n_partials, 0, 0, workspace, g, nb, stream)) return rc;
     hipLaunchKernelGGL(bn_apply_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)x, (const float4*)residual,
                        scale_shift, g, relu, (float4*)y, (unsigned long long*)mask_bits, amax_y);
     GGA_CHECK_LAUNCH("bn_apply_kernel");
     return GGA_OK;
 }
 
-extern "C" int gga_bn_relu_fwd_ex(const float* x, const float* residual, const float* gamma, const float* beta,
-                                  float* running_mean, float* running_var, int64_t rows, int channels, float eps,
-                                  float momentum, int training, int relu, float* y, int64_t y_row_stride, void* mask_bits,
-                                  float* saved, const double* partials, int n_partials, uint32_t* amax_y, void* workspace,
-                                  size_t workspace_bytes, void* stream_) {
-    return bn_fwd_impl(x, residual, gamma, beta, running_mean, running_var, rows, channels, eps, momentum,
-                       partials ? 1 : training, relu, y, y_row_stride, mask_bits, saved, partials, n_partials, workspace,
-                       workspace_bytes, stream_, amax_y);
-}
-
-extern "C" int gga_bn_stats_partials_cols(const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                          int64_t rows, int channels, float eps, float momentum, float* saved,
-                                          float* scale_shift, const double* partials, int n_partials, int partials_width,
-                                          int column_offset, void* stream_) {
+extern "C" int gga_bn_relu_bwd(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
+                               const float* gamma, const float* saved, int64_t rows, int channels, int relu, int training,
+                               float* grad_x, float* grad_residual, float* grad_gamma, float* grad_beta,
+                               uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_stats_partials_cols", rows, channels)) return rc;
-    GGA_REQUIRE(saved && scale_shift && running_mean && running_var && partials && n_partials >= 1,
-                "gga_bn_stats_partials_cols: null pointer argument");
-    GGA_REQUIRE(column_offset >= 0 && partials_width >= column_offset + channels,
-                "gga_bn_stats_partials_cols: columns %d .. %d of rows %d wide", column_offset, column_offset + channels, partials_width);
-    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, n_partials, channels,
-                       (double)rows, gamma, beta, eps, momentum, 1, running_mean, running_var, saved, scale_shift, partials_width,
-                       column_offset);
-    GGA_CHECK_LAUNCH("bn_fwd_final_kernel");
-    return GGA_OK;
-}
-
-extern "C" int gga_bn_stats_partials(const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                     int64_t rows, int channels, float eps, float momentum, float* saved,
-                                     float* scale_shift, const double* partials, int n_partials, void* stream_) {
-    return gga_bn_stats_partials_cols(gamma, beta, running_mean, running_var, rows, channels, eps, momentum, saved, scale_shift,
-                                      partials, n_partials, channels, 0, stream_);
-}
-
-extern "C" int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* running_mean,
-                            float* running_var, int64_t rows, int channels, float eps, float momentum, int training,
-                            float* saved, float* scale_shift, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_stats", rows, channels)) return rc;
-    GGA_REQUIRE(x && saved && scale_shift && workspace && running_mean && running_var, "gga_bn_stats: null pointer argument");
-    if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_stats: workspace too small");
-        return GGA_ERR_WORKSPACE;
-    }
-    const BnGeom g = bn_geom(rows, channels, channels);
-    const int nb = bn_grid(g.n4);
-    double* partials = (double*)workspace;
-    if (training) {
-        hipLaunchKernelGGL(bn_reduce_kernel<false>, dim3(nb), dim3(256), 0, stream, (const float4*)x, (const float4*)nullptr,
-                           (const unsigned long long*)nullptr, (const float*)nullptr, g, 0, partials);
-        GGA_CHECK_LAUNCH("bn_reduce_kernel<fwd>");
-    }
-    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, nb, channels,
-                       (double)rows, gamma, beta, eps, momentum, training, running_mean, running_var, saved,
-                       scale_shift);
-    GGA_CHECK_LAUNCH("bn_fwd_final_kernel");
-    return GGA_OK;
-}
-
-// Library-internal: fold [nblocks][2][C] partial sums (at the head of `workspace`) into grad_gamma / grad_beta and
-// the coefficient table the apply passes read (returned in *coef, inside the workspace).
-int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64_t rows, const float* gamma,
-                        const float* saved, float* grad_gamma, float* grad_beta, void* workspace, float** coef,
-                        hipStream_t stream) {
-    *coef = (float*)((char*)workspace + (size_t)BN_MAX_BLOCKS * 2 * channels * sizeof(double));
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, nblocks, channels,
-                       (double)rows, gamma, saved, grad_gamma, grad_beta, *coef, 1);
-    GGA_CHECK_LAUNCH("bn_bwd_final_kernel");
-    return GGA_OK;
-}
-
-extern "C" int gga_bn_relu_bwd_ex(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
-                                  const float* gamma, const float* saved, int64_t rows, int channels, int relu, int training,
-                                  float* grad_x,
-                                  float* grad_residual, float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x,
-                                  void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_relu_bwd_ex", rows, channels)) return rc;
-    GGA_REQUIRE(grad_y_row_stride >= channels && grad_y_row_stride % 4 == 0 && ((uintptr_t)grad_y & 15) == 0,
-                "gga_bn_relu_bwd_ex: grad_y row stride %lld must be a multiple of 4 floats >= channels, grad_y 16 B aligned",
-                (long long)grad_y_row_stride);
-    GGA_REQUIRE(grad_y && x && saved && grad_x && workspace && (!relu || mask_bits),
-                "gga_bn_relu_bwd_ex: null pointer argument");
-    if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_relu_bwd_ex: workspace too small");
-        return GGA_ERR_WORKSPACE;
-    }
+    const char* fn = "gga_bn_relu_bwd";
+    if (int rc = bn_check(fn, rows, channels)) return rc;
+    if (int rc = bn_check_strided(fn, "grad_y", grad_y, grad_y_row_stride, channels)) return rc;
+    GGA_REQUIRE(grad_y && x && saved && grad_x && workspace && (!relu || mask_bits), "%s: null pointer argument", fn);
+    if (int rc = bn_check_workspace(fn, rows, channels, workspace_bytes)) return rc;
     const BnGeom g = bn_geom(rows, channels, grad_y_row_stride);
     const int nb = bn_grid(g.n4);
     double* partials = (double*)workspace;
-    float* coef = (float*)((char*)workspace + (size_t)BN_MAX_BLOCKS * 2 * channels * sizeof(double));
+    float* coef = nullptr;
     hipLaunchKernelGGL(bn_reduce_kernel<true>, dim3(nb), dim3(256), 0, stream, (const float4*)grad_y, (const float4*)x,
                        (const unsigned long long*)mask_bits, saved, g, relu, partials);
     GGA_CHECK_LAUNCH("bn_reduce_kernel<bwd>");
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, nb, channels,
-                       (double)rows, gamma, saved, grad_gamma, grad_beta, coef, training);
-    GGA_CHECK_LAUNCH("bn_bwd_final_kernel");
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)grad_y, (const float4*)x,
-                       (const unsigned long long*)mask_bits, saved, coef, g, relu, (float4*)grad_x,
-                       (float4*)grad_residual, amax_grad_x);
-    GGA_CHECK_LAUNCH("bn_bwd_apply_kernel");
-    return GGA_OK;
+    if (int rc = gga_bn_bwd_finalize(partials, nb, channels, rows, gamma, saved, grad_gamma, grad_beta, training, workspace, &coef,
+                                     stream)) return rc;
+    return bn_bwd_apply(grad_y, x, mask_bits, saved, coef, g, nb, relu, grad_x, grad_residual, amax_grad_x, stream);
+}
+
+extern "C" int gga_bn_relu_bwd_partials(const float* grad_masked, int64_t grad_row_stride, const float* x, const float* gamma,
+                                        const float* saved, int64_t rows, int channels, int training, const double* partials,
+                                        int n_partials, float* grad_x, float* grad_gamma, float* grad_beta,
+                                        uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* fn = "gga_bn_relu_bwd_partials";
+    if (int rc = bn_check(fn, rows, channels)) return rc;
+    if (int rc = bn_check_strided(fn, "grad", grad_masked, grad_row_stride, channels)) return rc;
+    GGA_REQUIRE(grad_masked && x && saved && grad_x && workspace && partials && n_partials >= 1, "%s: null pointer argument", fn);
+    if (int rc = bn_check_workspace(fn, rows, channels, workspace_bytes)) return rc;
+    const BnGeom g = bn_geom(rows, channels, grad_row_stride);
+    float* coef = nullptr;
+    if (int rc = gga_bn_bwd_finalize(partials, n_partials, channels, rows, gamma, saved, grad_gamma, grad_beta, training, workspace,
+                                     &coef, stream)) return rc;
+    return bn_bwd_apply(grad_masked, x, nullptr, saved, coef, g, bn_grid(g.n4), 0, grad_x, nullptr, amax_grad_x, stream);
 }
 
 // per-channel sums of a [rows, C] matrix (the bias gradient of a convolution: sum of the output gradient over batch and
@@ -523,46 +535,15 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(const double* __rest
 extern "C" int gga_column_sums(const float* x, int64_t rows, int channels, float* sums, void* workspace, size_t workspace_bytes,
                                void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_column_sums", rows, channels)) return rc;
-    GGA_REQUIRE(x && sums && workspace && ((uintptr_t)x & 15) == 0, "gga_column_sums: null or misaligned pointer argument");
-    if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_column_sums: workspace too small");
-        return GGA_ERR_WORKSPACE;
-    }
+    const char* fn = "gga_column_sums";
+    if (int rc = bn_check(fn, rows, channels)) return rc;
+    GGA_REQUIRE(x && sums && workspace && ((uintptr_t)x & 15) == 0, "%s: null or misaligned pointer argument", fn);
+    if (int rc = bn_check_workspace(fn, rows, channels, workspace_bytes)) return rc;
     const BnGeom g = bn_geom(rows, channels, channels);
     const int nb = bn_grid(g.n4);
-    hipLaunchKernelGGL(bn_reduce_kernel<false>, dim3(nb), dim3(256), 0, stream, (const float4*)x, (const float4*)nullptr,
-                       (const unsigned long long*)nullptr, (const float*)nullptr, g, 0, (double*)workspace);
-    GGA_CHECK_LAUNCH("bn_reduce_kernel<fwd>");
+    if (int rc = bn_reduce_fwd(x, g, nb, (double*)workspace, stream)) return rc;
     hipLaunchKernelGGL(colsum_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, (const double*)workspace, nb, channels,
                        sums);
     GGA_CHECK_LAUNCH("colsum_final_kernel");
-    return GGA_OK;
-}
-
-extern "C" int gga_bn_relu_bwd_partials(const float* grad_masked, int64_t grad_row_stride, const float* x, const float* gamma,
-                                        const float* saved, int64_t rows, int channels, int training, const double* partials,
-                                        int n_partials, float* grad_x, float* grad_gamma, float* grad_beta,
-                                        uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = bn_check("gga_bn_relu_bwd_partials", rows, channels)) return rc;
-    GGA_REQUIRE(grad_row_stride >= channels && grad_row_stride % 4 == 0 && ((uintptr_t)grad_masked & 15) == 0,
-                "gga_bn_relu_bwd_partials: grad row stride %lld must be a multiple of 4 floats >= channels, grad 16 B aligned",
-                (long long)grad_row_stride);
-    GGA_REQUIRE(grad_masked && x && saved && grad_x && workspace && partials && n_partials >= 1,
-                "gga_bn_relu_bwd_partials: null pointer argument");
-    if (workspace_bytes < gga_bn_relu_workspace_bytes(rows, channels)) {
-        gga_set_error("gga_bn_relu_bwd_partials: workspace too small");
-        return GGA_ERR_WORKSPACE;
-    }
-    const BnGeom g = bn_geom(rows, channels, grad_row_stride);
-    const int nb = bn_grid(g.n4);
-    float* coef = (float*)((char*)workspace + (size_t)BN_MAX_BLOCKS * 2 * channels * sizeof(double));
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((channels + 7) / 8), dim3(1024), 0, stream, partials, n_partials, channels,
-                       (double)rows, gamma, saved, grad_gamma, grad_beta, coef, training);
-    GGA_CHECK_LAUNCH("bn_bwd_final_kernel");
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)grad_masked, (const float4*)x,
-                       (const unsigned long long*)nullptr, saved, coef, g, 0, (float4*)grad_x, (float4*)nullptr, amax_grad_x);
-    GGA_CHECK_LAUNCH("bn_bwd_apply_kernel");
     return GGA_OK;
 }

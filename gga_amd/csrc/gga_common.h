@@ -19,7 +19,7 @@ hipEvent_t* gga_timing_acquire(int site, int64_t key);
 
 // bn_relu.hip, for the kernels that produce BatchNorm-backward partial sums themselves
 int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64_t rows, const float* gamma,
-                        const float* saved, float* grad_gamma, float* grad_beta, void* workspace, float** coef,
+                        const float* saved, float* grad_gamma, float* grad_beta, int training, void* workspace, float** coef,
                         hipStream_t stream);
 
 #define GGA_REQUIRE(cond, ...)                      \

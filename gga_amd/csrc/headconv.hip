@@ -859,7 +859,7 @@ static int headtail_bwd_run(const char* fn, const float* grad_y, const float* x,
 #define HT_SW(AP) switch (cout) { case 1: HT_GO(1, AP); break; case 2: HT_GO(2, AP); break; case 3: HT_GO(3, AP); break; default: HT_GO(4, AP); break; }
     HT_SW(false)
     GGA_CHECK_LAUNCH("headtail_bwd_kernel<reduce>");
-    if (int rc = gga_bn_bwd_finalize(partials, nb, HC_CIN, rows, gamma, saved, grad_gamma, grad_beta, workspace, &coef, stream)) return rc;
+    if (int rc = gga_bn_bwd_finalize(partials, nb, HC_CIN, rows, gamma, saved, grad_gamma, grad_beta, 1, workspace, &coef, stream)) return rc;
     HT_SW(true)
     GGA_CHECK_LAUNCH("headtail_bwd_kernel<apply>");
 #undef HT_SW

@@ -172,7 +172,7 @@ def set_amax(t, amax):
     """Remember the absmax bits a producer kernel left for ``t`` (valid while ``t`` is not written again and the pool
     slot has not been recycled)."""
     if amax is not None:
-        t._gga_amax = (t._version, t.data_ptr(), t.numel(), amax, AMAX_POOL.generation)
+        t._gga_amax = (F.stamp(t), amax, AMAX_POOL.generation)
     return t
 
 
@@ -181,15 +181,19 @@ def new_amax(device, n=1):
     return AMAX_POOL.take(device, n) if PLANES == 2 else None
 
 
+def remembered_amax(t):
+    """The absmax slot ``set_amax`` left on ``t`` if ``t`` has not been written since and the slot is of this pool
+    generation, else None."""
+    c = getattr(t, '_gga_amax', None)
+    return c[1] if (c is not None and c[0] == F.stamp(t) and c[2] == AMAX_POOL.generation) else None
+
+
 def tensor_amax(t):
     """Absmax bits of ``t``: what its producer left (``set_amax``) if ``t`` has not been modified since, one
     ``gga_absmax_bits`` pass otherwise."""
     RANGE_GUARD.record(t)
-    c = getattr(t, '_gga_amax', None)
-    if (c is not None and c[0] == t._version and c[1] == t.data_ptr() and c[2] == t.numel()
-            and c[4] == AMAX_POOL.generation):
-        return c[3]
-    return _amax_bits(t)
+    c = remembered_amax(t)
+    return c if c is not None else _amax_bits(t)
 
 
 class BnSource:
@@ -199,11 +203,11 @@ class BnSource:
     ``bn_relu_cat`` and valid while ``z`` has not been written again."""
 
     def __init__(self, z, parts):
-        self.key = (z._version, z.data_ptr(), z.numel())
+        self.key = F.stamp(z)
         self.parts = parts
 
     def valid_for(self, z):
-        return self.key == (z._version, z.data_ptr(), z.numel())
+        return self.key == F.stamp(z)
 
     def part(self, c0, width):
         """(x pointer, x pixel stride, gamma, beta, mean, invstd pointers) of channels [c0, c0 + width), or None when
@@ -244,13 +248,13 @@ class BnPartials:
     masked by the ReLU and ``parts`` = [(first channel, channels, [tiles, 2, channels] f64 sums)]."""
 
     def __init__(self, g, parts, tokens):
-        self.key = (g._version, g.data_ptr(), g.numel())
+        self.key = F.stamp(g)
         self.parts, self.tokens = parts, tokens
 
     def take(self, g, token, c0, C):
         """The partial sums of channels [c0, c0 + C) if ``g`` is still the tensor the convolution wrote and ``token``
         (data pointer of the BatchNorm's saved statistics) is the one it masked with."""
-        if self.key != (g._version, g.data_ptr(), g.numel()) or token not in self.tokens:
+        if self.key != F.stamp(g) or token not in self.tokens:
             return None
         hit = [p for s, w, p in self.parts if c0 <= s and s + w <= c0 + C]
         if sum(p.shape[2] for p in hit) != C:

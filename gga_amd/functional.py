@@ -62,6 +62,12 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def stamp(t):
+    """What side data attached to ``t`` by its producer (per-channel sums, absmax, ``BnSource``, ``BnPartials``) is keyed
+    by: it changes when ``t`` is written again or is made to stand for other memory."""
+    return (t._version, t.data_ptr(), t.numel())
+
+
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -722,69 +728,108 @@ def box_losses(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_off
 
 
 # ----------------------------------------------------------------------------- fused BN (+res) (+ReLU)
-class _BNAct(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, eps, momentum, training, relu, rows, C,
-                partials=None):
-        L = _lib.lib()
-        dev = x.device
-        y = torch.empty_like(x)                       # same strides (channels-last stays channels-last)
-        saved = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        bits = torch.empty(L.gga_bn_relu_mask_bytes(rows, C), dtype=torch.uint8, device=dev) if relu else None
-        ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
-        from . import dense_conv
-        amax = dense_conv.new_amax(dev)              # the apply pass leaves max |y| for the convolution that reads y
-        use = partials is not None and training      # the producer of x already reduced the per-channel sums
-        check(L.gga_bn_relu_fwd_ex(_p(x), _p(residual), _p(gamma), _p(beta), _p(running_mean), _p(running_var), rows, C,
-                                   eps, momentum, int(training), int(relu), _p(y), C, _p(bits), _p(saved),
-                                   _p(partials) if use else None, int(partials.shape[0]) if use else 0, _p(amax), _p(ws),
-                                   ws.numel(), _stream()), 'gga_bn_relu_fwd_ex')
-        ctx.save_for_backward(x, gamma, saved, bits)
-        ctx.cfg = (rows, C, relu, residual is not None, bool(training))
-        if amax is None:
-            amax = torch.empty(0, dtype=torch.int32, device=dev)
-        ctx.mark_non_differentiable(amax, saved)
-        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
-        return y, amax, saved
+class _BNActBlocks(torch.autograd.Function):
+    """``cat([act_i(bn_i(x_i) + residual_i)], dim=1)`` over ``n >= 1`` column blocks (gga_bn_relu_fwd / gga_bn_relu_bwd, whose
+    row strides let a block write its columns of the concatenated map and read its columns of the gradient in place).
+    ``n = 1`` (``bn_act``): a [rows, C] or channels-last ``x``, optional residual and ReLU, the layer's own mode.
+    ``n >= 2`` (``bn_relu_cat``): channels-last inputs of equal [B, ., H, W].
+    ``cfg[i]`` = (eps, momentum, training, relu); tensors: the n inputs, then per block the residual, gamma, beta, running
+    mean, running variance and the producer's per-channel sums of x (or None)."""
 
     @staticmethod
-    def backward(ctx, gy, _gamax=None, _gsaved=None):
-        x, gamma, saved, bits = ctx.saved_tensors
-        rows, C, relu, has_res, training = ctx.cfg
+    def forward(ctx, n, cfg, *args):
+        xs, res, gammas, betas, rms, rvs, partials = (args[i * n:(i + 1) * n] for i in range(7))
         L = _lib.lib()
+        x0 = xs[0]
+        dev = x0.device
+        chans = [int(x.shape[1]) for x in xs]
+        tot = sum(chans)
+        rows = x0.numel() // chans[0]
+        if n == 1:
+            out = torch.empty_like(x0)                # same strides (channels-last stays channels-last)
+        else:
+            B, _, H, W = x0.shape
+            out = torch.empty((B, tot, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        saved_all, bits_all = [], []
+        off = 0
         from . import dense_conv
-        done = getattr(gy, '_gga_bn_bwd', None)      # the convolution that produced gy masked it and reduced the sums
-        partials = done.take(gy, saved.data_ptr(), 0, C) if (done is not None and relu and not has_res) else None
-        # the incoming gradient must have the memory layout of x ([rows, C] row major)
-        gy = gy.contiguous(memory_format=torch.channels_last) if x.dim() == 4 else gy.contiguous()
-        gx = torch.empty_like(x)
-        gres = torch.empty_like(x) if has_res else None
-        gg, gb = torch.empty(C, dtype=torch.float32, device=x.device), torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), x.device)
-        amax = dense_conv.new_amax(x.device)         # max |gx| for the convolution backward that reads gx
-        if partials is not None:
-            check(L.gga_bn_relu_bwd_partials(_p(gy), C, _p(x), _p(gamma), _p(saved), rows, C, int(training), _p(partials),
-                                             int(partials.shape[0]), _p(gx), _p(gg), _p(gb), _p(amax), _p(ws), ws.numel(),
-                                             _stream()), 'gga_bn_relu_bwd_partials')
+        amax = dense_conv.new_amax(dev)               # max |out| over all blocks, for the convolution that reads out
+        for i in range(n):
+            eps, momentum, training, relu = cfg[i]
+            C = chans[i]
+            saved = torch.empty(2 * C, dtype=torch.float32, device=dev)
+            bits = torch.empty(L.gga_bn_relu_mask_bytes(rows, C), dtype=torch.uint8, device=dev) if relu else None
+            ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
+            pt = partials[i] if (training and partials[i] is not None) else None      # the producer of x already reduced the sums
+            check(L.gga_bn_relu_fwd(_p(xs[i]), _p(res[i]), _p(gammas[i]), _p(betas[i]), _p(rms[i]), _p(rvs[i]), rows, C,
+                                    eps, momentum, int(training), int(relu), out.data_ptr() + 4 * off, tot, _p(bits),
+                                    _p(saved), _p(pt), int(pt.shape[0]) if pt is not None else 0, _p(amax), _p(ws), ws.numel(),
+                                    _stream()), 'gga_bn_relu_fwd')
+            saved_all.append(saved)
+            bits_all.append(bits)
+            off += C
+        ctx.save_for_backward(*xs, *gammas, *saved_all, *bits_all)
+        ctx.n, ctx.chans, ctx.rows, ctx.cfg = n, chans, rows, cfg
+        ctx.has_res = [r is not None for r in res]
+        if amax is None:
+            amax = torch.empty(0, dtype=torch.int32, device=dev)
+        ctx.mark_non_differentiable(amax, *saved_all)
+        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
+        return (out, amax, *saved_all)
+
+    @staticmethod
+    def backward(ctx, g, _gamax=None, *_gsaved):
+        from . import dense_conv
+        n, chans, rows, cfg, has_res = ctx.n, ctx.chans, ctx.rows, ctx.cfg, ctx.has_res
+        t = ctx.saved_tensors
+        xs, gammas, saved_all, bits_all = t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n]
+        L = _lib.lib()
+        done = getattr(g, '_gga_bn_bwd', None)       # the convolution that produced g masked it and reduced the sums
+        given, off = [], 0
+        for i in range(n):
+            use = done is not None and cfg[i][3] and not has_res[i]
+            given.append(done.take(g, saved_all[i].data_ptr(), off, chans[i]) if use else None)
+            off += chans[i]
+        # the incoming gradient must have the memory layout of the output ([rows, tot] row major)
+        g = g.contiguous(memory_format=torch.channels_last) if g.dim() == 4 else g.contiguous()
+        tot = off
+        gxs, gres, ggs, gbs = [], [], [], []
+        off = 0
+        for i in range(n):
+            C = chans[i]
+            x = xs[i]
+            training, relu = cfg[i][2:]
+            gx = torch.empty_like(x)
+            gr = torch.empty_like(x) if has_res[i] else None
+            gg = torch.empty(C, dtype=torch.float32, device=x.device)
+            gb = torch.empty(C, dtype=torch.float32, device=x.device)
+            ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), x.device)
+            amax = dense_conv.new_amax(x.device)         # max |gx| for the convolution backward that reads gx
+            if given[i] is not None:
+                check(L.gga_bn_relu_bwd_partials(g.data_ptr() + 4 * off, tot, _p(x), _p(gammas[i]), _p(saved_all[i]), rows, C,
+                                                 int(training), _p(given[i]), int(given[i].shape[0]), _p(gx), _p(gg), _p(gb),
+                                                 _p(amax), _p(ws), ws.numel(), _stream()), 'gga_bn_relu_bwd_partials')
+            else:
+                check(L.gga_bn_relu_bwd(g.data_ptr() + 4 * off, tot, _p(x), _p(bits_all[i]), _p(gammas[i]), _p(saved_all[i]),
+                                        rows, C, int(relu), int(training), _p(gx), _p(gr), _p(gg), _p(gb), _p(amax), _p(ws),
+                                        ws.numel(), _stream()), 'gga_bn_relu_bwd')
             dense_conv.set_amax(gx, amax)
-            return gx, None, gg, gb, None, None, None, None, None, None, None, None, None
-        check(L.gga_bn_relu_bwd_ex(_p(gy), C, _p(x), _p(bits), _p(gamma), _p(saved), rows, C, int(relu), int(training), _p(gx),
-                                   _p(gres), _p(gg), _p(gb), _p(amax), _p(ws), ws.numel(), _stream()), 'gga_bn_relu_bwd_ex')
-        dense_conv.set_amax(gx, amax)
-        return gx, gres, gg, gb, None, None, None, None, None, None, None, None, None
+            gxs.append(gx), gres.append(gr), ggs.append(gg), gbs.append(gb)
+            off += C
+        return (None, None, *gxs, *gres, *ggs, *gbs) + (None,) * (3 * n)
 
 
 def attach_bn_partials(y, stats):
     """Remember the per-channel sums a convolution kernel left for its output ``y`` (valid while ``y`` is not written again)."""
     y.bn_partials = stats
-    y._bn_partials_version = y._version
+    y._bn_partials_stamp = stamp(y)
     return y
 
 
 def bn_partials_of(x):
     """The producer's per-channel sums of ``x`` ([tiles, 2, C] f64) if ``x`` still holds what the producer wrote, else None."""
     p = getattr(x, 'bn_partials', None)
-    if p is None or getattr(x, '_bn_partials_version', x._version) != x._version:
+    if p is None or getattr(x, '_bn_partials_stamp', None) != stamp(x):
         return None
     return p if (p.dim() == 3 and p.shape[0] >= 1 and p.shape[2] == x.shape[1]) else None
 
@@ -794,7 +839,7 @@ def channel_sums(x):
     bias gradient) - ``gga_column_sums`` where the layout allows it, the framework's reduction otherwise."""
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32) else None
     C = x.shape[1]
-    if rc is None or rc[0] < 1 or C % 4 or C // 4 > 256 or 256 % (C // 4) or x.data_ptr() % 16:
+    if rc is None or rc[0] < 1 or not _bn_channels_ok(C) or x.data_ptr() % 16:
         return x.sum(tuple(d for d in range(x.dim()) if d != 1))
     L = _lib.lib()
     out = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -812,14 +857,24 @@ def _rows_channels(x):
     return None
 
 
+def _bn_channels_ok(C):
+    """The channel counts the BatchNorm / GroupNorm kernels take (``bn_check`` of csrc/bn_relu.hip): a thread owns 4 channels
+    and the channel groups tile a 256-thread workgroup."""
+    return C >= 4 and C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0
+
+
+def _bn_module_ok(bn):
+    """A BatchNorm module the fused kernels stand for: affine, with running statistics and a fixed momentum."""
+    return bn.affine and bn.track_running_stats and bn.momentum is not None
+
+
 def bn_act(x, bn, relu=True, residual=None):
     """``relu(bn(x) + residual)`` (each part optional) — one fused HIP pass pair when ``x`` is a CUDA
     f32 [rows, C] / channels-last tensor: training mode (batch statistics) or evaluation mode (running statistics,
     also under autograd: a frozen ``norm_eval`` backbone); the eager ops otherwise."""
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32) else None
     C = x.shape[1]
-    ok = (rc is not None and rc[0] >= 1 and C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and bn.affine
-          and bn.track_running_stats and bn.momentum is not None
+    ok = (rc is not None and rc[0] >= 1 and _bn_channels_ok(C) and _bn_module_ok(bn)
           and (residual is None or (residual.shape == x.shape and residual.stride() == x.stride())))
     if not ok:
         y = bn(x)
@@ -829,8 +884,8 @@ def bn_act(x, bn, relu=True, residual=None):
     if bn.training:
         count_batch(bn)
     partials = bn_partials_of(x) if bn.training else None
-    y, amax, saved = _BNAct.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps),
-                                  float(bn.momentum), bool(bn.training), bool(relu), int(rc[0]), int(C), partials)
+    cfg = ((float(bn.eps), float(bn.momentum), bool(bn.training), bool(relu)),)
+    y, amax, saved = _BNActBlocks.apply(1, cfg, x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, partials)
     from . import dense_conv
     if amax.numel():
         dense_conv.set_amax(y, amax)
@@ -888,7 +943,7 @@ def gn_act(x, gn, relu=True):
     size is a multiple of 4 channels, the eager ops otherwise (``torch.nn.GroupNorm`` returns NCHW memory)."""
     C = x.shape[1] if x.dim() == 4 else 0
     ok = (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
-          and C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and C % gn.num_groups == 0
+          and _bn_channels_ok(C) and C % gn.num_groups == 0
           and (C // gn.num_groups) % 4 == 0 and gn.affine and x.shape[2] * x.shape[3] >= 1)
     if not ok:
         y = gn(x)
@@ -900,89 +955,6 @@ def gn_act(x, gn, relu=True):
     return y
 
 
-class _BNActCat(torch.autograd.Function):
-    """``cat([relu(bn_i(x_i))], dim=1)`` for channels-last inputs of equal [B, ., H, W]: every
-    branch writes its column block of the concatenated map and reads its block of the gradient in
-    place (the row strides of gga_bn_relu_fwd_ex / gga_bn_relu_bwd_ex)."""
-
-    @staticmethod
-    def forward(ctx, n, cfg, *args):
-        xs, gammas, betas = args[:n], args[n:2 * n], args[2 * n:3 * n]
-        rms, rvs = args[3 * n:4 * n], args[4 * n:5 * n]
-        partials = args[5 * n:6 * n]                  # per branch: the producer's per-channel sums of x, or None
-        L = _lib.lib()
-        x0 = xs[0]
-        dev = x0.device
-        B, _, H, W = x0.shape
-        rows = B * H * W
-        chans = [int(x.shape[1]) for x in xs]
-        tot = sum(chans)
-        out = torch.empty((B, tot, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        saved_all, bits_all = [], []
-        off = 0
-        from . import dense_conv
-        amax = dense_conv.new_amax(dev)               # max over all branches' outputs = max of the concatenated map
-        for i in range(n):
-            eps, momentum, training = cfg[i]
-            C = chans[i]
-            saved = torch.empty(2 * C, dtype=torch.float32, device=dev)
-            bits = torch.empty(L.gga_bn_relu_mask_bytes(rows, C), dtype=torch.uint8, device=dev)
-            ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
-            pt = partials[i] if (training and partials[i] is not None) else None
-            check(L.gga_bn_relu_fwd_ex(_p(xs[i]), None, _p(gammas[i]), _p(betas[i]), _p(rms[i]), _p(rvs[i]), rows, C,
-                                       eps, momentum, int(training), 1, out.data_ptr() + 4 * off, tot, _p(bits),
-                                       _p(saved), _p(pt), int(pt.shape[0]) if pt is not None else 0, _p(amax), _p(ws), ws.numel(),
-                                       _stream()), 'gga_bn_relu_fwd_ex')
-            saved_all.append(saved)
-            bits_all.append(bits)
-            off += C
-        ctx.save_for_backward(*xs, *gammas, *saved_all, *bits_all)
-        ctx.n, ctx.chans, ctx.rows = n, chans, rows
-        if amax is None:
-            amax = torch.empty(0, dtype=torch.int32, device=dev)
-        ctx.mark_non_differentiable(amax, *saved_all)
-        ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
-        return (out, amax, *saved_all)
-
-    @staticmethod
-    def backward(ctx, g, _gamax=None, *_gsaved):
-        from . import dense_conv
-        n, chans, rows = ctx.n, ctx.chans, ctx.rows
-        t = ctx.saved_tensors
-        xs, gammas, saved_all, bits_all = t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n]
-        L = _lib.lib()
-        done = getattr(g, '_gga_bn_bwd', None)       # the convolution that produced g masked it and reduced the sums
-        if done is not None:
-            offs = [sum(chans[:i]) for i in range(n)]
-            given = [done.take(g, saved_all[i].data_ptr(), offs[i], chans[i]) for i in range(n)]
-        else:
-            given = [None] * n
-        g = g.contiguous(memory_format=torch.channels_last)
-        tot = sum(chans)
-        gxs, ggs, gbs = [], [], []
-        off = 0
-        for i in range(n):
-            C = chans[i]
-            x = xs[i]
-            gx = torch.empty_like(x)
-            gg = torch.empty(C, dtype=torch.float32, device=x.device)
-            gb = torch.empty(C, dtype=torch.float32, device=x.device)
-            ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), x.device)
-            amax = dense_conv.new_amax(x.device)
-            if given[i] is not None:
-                check(L.gga_bn_relu_bwd_partials(g.data_ptr() + 4 * off, tot, _p(x), _p(gammas[i]), _p(saved_all[i]), rows, C, 1,
-                                                 _p(given[i]), int(given[i].shape[0]), _p(gx), _p(gg), _p(gb), _p(amax), _p(ws),
-                                                 ws.numel(), _stream()), 'gga_bn_relu_bwd_partials')
-            else:
-                check(L.gga_bn_relu_bwd_ex(g.data_ptr() + 4 * off, tot, _p(x), _p(bits_all[i]), _p(gammas[i]),
-                                           _p(saved_all[i]), rows, C, 1, 1, _p(gx), None, _p(gg), _p(gb), _p(amax), _p(ws),
-                                           ws.numel(), _stream()), 'gga_bn_relu_bwd_ex')
-            dense_conv.set_amax(gx, amax)
-            gxs.append(gx), ggs.append(gg), gbs.append(gb)
-            off += C
-        return (None, None, *gxs, *ggs, *gbs) + (None,) * (3 * n)
-
-
 def bn_relu_cat(xs, bns):
     """``torch.cat([relu(bn(x)) for x, bn in zip(xs, bns)], dim=1)`` without the concat copy (and
     without the split copies in backward) when every branch qualifies for the fused BatchNorm
@@ -990,8 +962,8 @@ def bn_relu_cat(xs, bns):
     def fusable(x, bn):
         rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32) else None
         C = x.shape[1]
-        return (rc is not None and C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and bn.affine
-                and bn.track_running_stats and bn.momentum is not None and (bn.training or not torch.is_grad_enabled()))
+        return (rc is not None and _bn_channels_ok(C) and _bn_module_ok(bn)
+                and (bn.training or not torch.is_grad_enabled()))
     same = all(x.shape[0] == xs[0].shape[0] and x.shape[2:] == xs[0].shape[2:] for x in xs)
     if len(xs) < 2 or not same or not all(fusable(x, bn) for x, bn in zip(xs, bns)):
         return torch.cat([bn_act(x, bn, relu=True) for x, bn in zip(xs, bns)], dim=1) if len(xs) > 1 \
@@ -1000,11 +972,11 @@ def bn_relu_cat(xs, bns):
         if bn.training:
             count_batch(bn)
     n = len(xs)
-    cfg = tuple((float(bn.eps), float(bn.momentum), bool(bn.training)) for bn in bns)
+    cfg = tuple((float(bn.eps), float(bn.momentum), bool(bn.training), True) for bn in bns)
     # the producers' per-channel sums (dense_conv / strided_conv / sparse convolutions), where they left them
-    out, amax, *saved = _BNActCat.apply(n, cfg, *xs, *[bn.weight for bn in bns], *[bn.bias for bn in bns],
-                                        *[bn.running_mean for bn in bns], *[bn.running_var for bn in bns],
-                                        *[bn_partials_of(x) for x in xs])
+    out, amax, *saved = _BNActBlocks.apply(n, cfg, *xs, *[None] * n, *[bn.weight for bn in bns], *[bn.bias for bn in bns],
+                                           *[bn.running_mean for bn in bns], *[bn.running_var for bn in bns],
+                                           *[bn_partials_of(x) for x in xs])
     from . import dense_conv
     if amax.numel():
         dense_conv.set_amax(out, amax)
@@ -1052,6 +1024,46 @@ class _HeadConv3x3(torch.autograd.Function):
         return gx, gw, gb
 
 
+def _head_out_conv_ok(conv):
+    """An output conv of a head branch that the gga_head_conv3x3_* kernels take (the caller checks its 64 input channels)."""
+    return (conv.out_channels <= 4 and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros')
+
+
+def _head_tail_fwd(x_ptr, x_stride, stats, ws, bn, eps, momentum, training, saved, ss, w, bias, geom, y, tile_map=None):
+    """The tail of one head branch on the current stream: the BatchNorm statistics (gga_bn_stats: ``saved`` = mean / invstd,
+    ``ss`` = scale / shift), then the output conv, which normalises while it loads, into ``y``. ``x_ptr``, ``x_stride``: the
+    BatchNorm input, its C channels every ``x_stride`` floats. ``stats``: (partial sums, their row width, this BatchNorm's
+    first column) left by the producer of x, or None - a reduce pass over x (dense) with the workspace ``ws``.
+    ``tile_map``: compute the map's active tiles only (gga_head_conv3x3_fwd_tiles)."""
+    L = _lib.lib()
+    gamma, beta, running_mean, running_var = bn
+    B, H, W, C = geom
+    pt, width, col = stats if stats is not None else (None, 0, 0)
+    check(L.gga_bn_stats(x_ptr if pt is None else None, _p(gamma), _p(beta), _p(running_mean), _p(running_var), B * H * W, C, eps,
+                         momentum, int(training), _p(saved), _p(ss), _p(pt), int(pt.shape[0]) if pt is not None else 0, width, col,
+                         _p(ws), ws.numel() if ws is not None else 0, _stream()), 'gga_bn_stats')
+    if tile_map is not None:
+        check(L.gga_head_conv3x3_fwd_tiles(x_ptr, x_stride, _p(ss), _p(w), _p(bias), B, H, W, C, w.shape[0], _p(tile_map), _p(y),
+                                           _stream()), 'gga_head_conv3x3_fwd_tiles')
+    else:
+        check(L.gga_head_conv3x3_fwd(x_ptr, x_stride, _p(ss), _p(w), _p(bias), B, H, W, C, w.shape[0], _p(y), _stream()),
+              'gga_head_conv3x3_fwd')
+
+
+def _head_tail_bwd(gy, x_ptr, x_stride, ss, gamma, saved, w, geom, gw, gb, gx_ptr, gx_stride, gg, gbeta, amax, sparse_grad):
+    """Backward of ``_head_tail_fwd`` on the current stream (gga_head_branch_bwd): the output conv's weight / bias gradient
+    ``gw`` / ``gb`` and the BatchNorm + ReLU backward ``gg`` / ``gbeta`` and, at ``gx_ptr`` with ``gx_stride`` floats between
+    pixels, the gradient of the BatchNorm input; ``amax``: the absmax slot of that gradient, or None."""
+    L = _lib.lib()
+    B, H, W, C = geom
+    cout = w.shape[0]
+    ws = _workspace('headbranch', L.gga_head_branch_bwd_workspace_bytes(B, H, W, cout), gy.device)       # (scratch buffers are per stream)
+    check(L.gga_head_branch_bwd(_p(gy), x_ptr, x_stride, _p(ss), _p(gamma), _p(saved), _p(w), B, H, W, C, cout, _p(gw), _p(gb),
+                                gx_ptr, gx_stride, _p(gg), _p(gbeta), _p(amax), int(sparse_grad), _p(ws), ws.numel(), _stream()),
+          'gga_head_branch_bwd')
+
+
 class _BnReluHeadConv3x3(torch.autograd.Function):
     """``conv(relu(bn(x)))`` for the tail of a head branch without materialising the normalised
     activation: batch statistics (gga_bn_stats), then the output conv applies scale/shift + ReLU
@@ -1069,17 +1081,11 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
         w = weight.contiguous()
         saved = torch.empty(2 * C, dtype=torch.float32, device=dev)
         ss = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        if partials is not None:                    # sums left by the convolution that produced x
-            check(L.gga_bn_stats_partials(_p(gamma), _p(beta), _p(running_mean), _p(running_var), rows, C, eps, momentum,
-                                          _p(saved), _p(ss), _p(partials), int(partials.shape[0]), _stream()),
-                  'gga_bn_stats_partials')
-        else:
-            ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev)
-            check(L.gga_bn_stats(_p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), rows, C, eps, momentum,
-                                 int(training), _p(saved), _p(ss), _p(ws), ws.numel(), _stream()), 'gga_bn_stats')
+        # sums left by the convolution that produced x, or a reduce pass over x
+        ws = _workspace('bn', L.gga_bn_relu_workspace_bytes(rows, C), dev) if partials is None else None
         y = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev)
-        check(L.gga_head_conv3x3_fwd(_p(x), C, _p(ss), _p(w), _p(bias), B, H, W, C, cout, _p(y), _stream()),
-              'gga_head_conv3x3_fwd')
+        _head_tail_fwd(x.data_ptr(), C, (partials, C, 0) if partials is not None else None, ws,
+                       (gamma, beta, running_mean, running_var), eps, momentum, training, saved, ss, w, bias, (B, H, W, C), y)
         ctx.save_for_backward(x, gamma, saved, ss, w)
         ctx.has_bias, ctx.sparse_grad = bias is not None, bool(sparse_grad)
         return y
@@ -1087,10 +1093,9 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, gamma, saved, ss, w = ctx.saved_tensors
-        L = _lib.lib()
         gy = gy.contiguous()
         B, C, H, W = x.shape
-        rows, cout = B * H * W, w.shape[0]
+        cout = w.shape[0]
         dev = x.device
         gw = torch.empty_like(w)
         gb = torch.empty(cout, dtype=torch.float32, device=dev) if ctx.has_bias else None
@@ -1099,12 +1104,10 @@ class _BnReluHeadConv3x3(torch.autograd.Function):
         gx = torch.empty_like(x)
         gg = torch.empty(C, dtype=torch.float32, device=dev)
         gbeta = torch.empty(C, dtype=torch.float32, device=dev)
-        ws = _workspace('headbranch', L.gga_head_branch_bwd_workspace_bytes(B, H, W, cout), dev)
         from . import dense_conv
         amax = dense_conv.new_amax(dev)
-        check(L.gga_head_branch_bwd(_p(gy), _p(x), C, _p(ss), _p(gamma), _p(saved), _p(w), B, H, W, C, cout, _p(gw), _p(gb), _p(gx), C,
-                                    _p(gg), _p(gbeta), _p(amax), int(ctx.sparse_grad), _p(ws), ws.numel(), _stream()),
-              'gga_head_branch_bwd')
+        _head_tail_bwd(gy, x.data_ptr(), C, ss, gamma, saved, w, (B, H, W, C), gw, gb, gx.data_ptr(), C, gg, gbeta, amax,
+                       ctx.sparse_grad)
         dense_conv.set_amax(gx, amax)
         return gx, gg, gbeta, None, None, gw, gb, None, None, None, None, None
 
@@ -1115,10 +1118,8 @@ def bn_relu_head_conv3x3(x, bn, conv, sparse_grad=True):
     ``sparse_grad``: a hint for the backward, never a change of its result - False when the output's gradient is
     known to be dense (a heat-map), see ``gga_head_branch_bwd``."""
     rc = _rows_channels(x) if (x.is_cuda and x.dtype == torch.float32) else None
-    ok = (rc is not None and x.dim() == 4 and x.shape[1] == 64 and bn.affine and bn.track_running_stats
-          and bn.momentum is not None and bn.training and torch.is_grad_enabled() and conv.out_channels <= 4
-          and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-          and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros')
+    ok = (rc is not None and x.dim() == 4 and x.shape[1] == 64 and _bn_module_ok(bn) and bn.training and torch.is_grad_enabled()
+          and _head_out_conv_ok(conv))
     if not ok:
         return head_conv3x3(bn_act(x, bn, relu=True), conv)
     count_batch(bn)
@@ -1183,10 +1184,8 @@ class _HeadBranches(torch.autograd.Function):
         from . import dense_conv
         w1, gam, bet, rm, rv, w2, b2 = (t[i * n:(i + 1) * n] for i in range(7))
         maps = [None] * n if maps is None else list(maps)
-        L = _lib.lib()
         B, C, H, W = x.shape
-        rows, dev, tot = B * H * W, x.device, C * n
-        tr = dense_conv._transposed(H, W)
+        dev, tot = x.device, C * n
         Y = torch.empty((B, tot, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
         outs, saved_all, ss_all = [], [], []
         x_amax = dense_conv.tensor_amax(x) if dense_conv.PLANES == 2 else None     # from x's producer, for all n convolutions
@@ -1220,18 +1219,10 @@ class _HeadBranches(torch.autograd.Function):
         for i in range(n):
             eps, momentum = cfg[i][:2]
             stats, col = all_stats[i]
-            tiles = int(stats.shape[0])
             with torch.cuda.stream(streams[i % len(streams)]):
-                check(L.gga_bn_stats_partials_cols(_p(gam[i]), _p(bet[i]), _p(rm[i]), _p(rv[i]), rows, C, eps, momentum,
-                                                   _p(saved_all[i]), _p(ss_all[i]), _p(stats), tiles, int(stats.shape[2]), col,
-                                                   _stream()), 'gga_bn_stats_partials_cols')
-                if maps[i] is not None:
-                    check(L.gga_head_conv3x3_fwd_tiles(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(w2c[i]), _p(b2[i]), B, H, W,
-                                                       C, w2[i].shape[0], _p(maps[i]), _p(outs[i]), _stream()),
-                          'gga_head_conv3x3_fwd_tiles')
-                else:
-                    check(L.gga_head_conv3x3_fwd(Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(w2c[i]), _p(b2[i]), B, H, W, C,
-                                                 w2[i].shape[0], _p(outs[i]), _stream()), 'gga_head_conv3x3_fwd')
+                _head_tail_fwd(Y.data_ptr() + 4 * C * i, tot, (stats, int(stats.shape[2]), col), None,
+                               (gam[i], bet[i], rm[i], rv[i]), eps, momentum, True, saved_all[i], ss_all[i], w2c[i], b2[i],
+                               (B, H, W, C), outs[i], maps[i])
         for st_ in streams[1:]:
             streams[0].wait_stream(st_)
         ctx.save_for_backward(x, Y, *w1, *gam, *w2, *saved_all, *ss_all)
@@ -1247,9 +1238,8 @@ class _HeadBranches(torch.autograd.Function):
         t = ctx.saved_tensors
         x, Y = t[0], t[1]
         w1, gam, w2, saved_all, ss_all = (t[2 + i * n:2 + (i + 1) * n] for i in range(5))
-        L = _lib.lib()
         B, C, H, W = x.shape
-        rows, dev, tot = B * H * W, x.device, C * n
+        dev, tot = x.device, C * n
         G = torch.empty_like(Y)
         # the tail kernels leave max |G_i| of their column block: the weight gradient scales every branch's block by its own
         # maximum (a regression branch's gradient lives on a few object cells, orders of magnitude below a heat-map branch's:
@@ -1269,13 +1259,10 @@ class _HeadBranches(torch.autograd.Function):
         for st_ in streams[1:]:
             st_.wait_stream(streams[0])
         for i in range(n):
-            cout = w2[i].shape[0]
             with torch.cuda.stream(streams[i % len(streams)]):
-                ws = _workspace('headbranch', L.gga_head_branch_bwd_workspace_bytes(B, H, W, cout), dev)       # (scratch buffers are per stream)
-                check(L.gga_head_branch_bwd(_p(gyc[i]), Y.data_ptr() + 4 * C * i, tot, _p(ss_all[i]), _p(gam[i]), _p(saved_all[i]),
-                                            _p(w2c[i]), B, H, W, C, cout, _p(gw2[i]), _p(gb2[i]), G.data_ptr() + 4 * C * i, tot,
-                                            _p(ggam[i]), _p(gbet[i]), _p(g_blocks[i:i + 1] if g_blocks is not None else None),
-                                            ctx.sparse_grad[i], _p(ws), ws.numel(), _stream()), 'gga_head_branch_bwd')
+                _head_tail_bwd(gyc[i], Y.data_ptr() + 4 * C * i, tot, ss_all[i], gam[i], saved_all[i], w2c[i], (B, H, W, C),
+                               gw2[i], gb2[i], G.data_ptr() + 4 * C * i, tot, ggam[i], gbet[i],
+                               g_blocks[i:i + 1] if g_blocks is not None else None, ctx.sparse_grad[i])
         for st_ in streams[1:]:
             streams[0].wait_stream(st_)
         wcat = [w.detach() for w in w1]            # stands for the [64n, 64, 3, 3] concatenation (weight bank: never made)
@@ -1299,11 +1286,8 @@ def head_branches(x, branches, sparse_grad=None, tile_maps=None):
     if rc is None or x.shape[1] != 64 or not torch.is_grad_enabled() or not dense_conv.ENABLED or not dense_conv.WGRAD:
         return None
     for conv1, bn, conv2 in branches:
-        ok = (dense_conv.eligible(conv1, x) and conv1.bias is None and conv1.out_channels == 64 and bn.affine
-              and bn.track_running_stats and bn.momentum is not None and bn.training and conv2.out_channels <= 4
-              and type(conv2) is torch.nn.Conv2d and conv2.in_channels == 64 and conv2.kernel_size == (3, 3)
-              and conv2.stride == (1, 1) and conv2.padding == (1, 1) and conv2.dilation == (1, 1) and conv2.groups == 1
-              and conv2.padding_mode == 'zeros')
+        ok = (dense_conv.eligible(conv1, x) and conv1.bias is None and conv1.out_channels == 64 and _bn_module_ok(bn)
+              and bn.training and type(conv2) is torch.nn.Conv2d and conv2.in_channels == 64 and _head_out_conv_ok(conv2))
         if not ok:
             return None
     for _, bn, _ in branches:
@@ -1330,9 +1314,7 @@ def head_conv3x3(x, conv):
     """``conv(x)`` for the output convs of the head branches (64 -> 1..4 channels, 3x3, pad 1): the
     HBM-bound HIP kernels when ``x`` is a CUDA f32 channels-last activation, MIOpen otherwise."""
     ok = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 64
-          and x.is_contiguous(memory_format=torch.channels_last) and conv.out_channels <= 4
-          and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-          and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros')
+          and x.is_contiguous(memory_format=torch.channels_last) and _head_out_conv_ok(conv))
     if not ok:
         return conv(x)
     return _HeadConv3x3.apply(x, conv.weight, conv.bias)

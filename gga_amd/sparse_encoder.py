@@ -134,10 +134,9 @@ class SparseEncoder(nn.Module):
             from . import functional as F, dense_conv
             D, H, W = out.spatial_shape
             spatial_features = F.sparse_bev_channels_last(f, out.indices, out.batch_size, D, H, W)
-            c = getattr(f, '_gga_amax', None)           # (version, pointer, size, absmax slot, pool generation) left by f's producer
-            if (c is not None and dense_conv.PLANES == 2 and c[0] == f._version and c[1] == f.data_ptr() and c[2] == f.numel()
-                    and c[4] == dense_conv.AMAX_POOL.generation):
-                dense_conv.set_amax(spatial_features, c[3])     # the same values plus zeros: the features' absmax is the map's
+            c = dense_conv.remembered_amax(f) if dense_conv.PLANES == 2 else None       # the absmax slot f's producer left
+            if c is not None:
+                dense_conv.set_amax(spatial_features, c)     # the same values plus zeros: the features' absmax is the map's
             return spatial_features
         spatial_features = out.dense()
         N, C, D, H, W = spatial_features.shape

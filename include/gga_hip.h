@@ -384,7 +384,7 @@ size_t gga_sparse_split_weight_bytes(int kvol, int cin, int cout);
  * all nine taps.
  * The convolution can also leave the batch statistics of its output for the BatchNorm
  * that follows: stats [gga_dense_conv3x3_stat_rows(B,H,W,cout,planes,1)][2][cout] f64 = partial sums and sums of
- * squares per channel - the `partials` of gga_bn_relu_fwd_ex / gga_bn_stats_partials, so
+ * squares per channel - the `partials` of gga_bn_relu_fwd / gga_bn_stats, so
  * the BatchNorm does not read y a second time for its reduction.
  * Rows of `stats` (per slice) for a launch of this arithmetic over n_slices 128-channel output slices: the two-plane launches
  * run the producer / consumer form (dense_conv_ws.hip: tiles of 8 x 32 pixels at 128 output channels, 16 x 32 at 64, one row
@@ -447,7 +447,7 @@ int gga_sparse_pack_weight_planes(const float* weight, int kvol, int cin, int co
  * stats (NULL: none) receives the per-channel sums of the output for the BatchNorm that follows
  * (ops/sparse_block.py:117-134, backbones/second.py:49-57, necks/second_fpn.py:52-69: conv -> BN -> ReLU): stats
  * [gga_sparse_conv_apply_tiles(n_rows)][2][cout] f64 = per workgroup of 128 rows the sum and the sum of squares - the
- * partials gga_bn_relu_fwd_ex takes. */
+ * partials gga_bn_relu_fwd takes. */
 int64_t gga_sparse_conv_apply_tiles(int64_t n_rows);
 int gga_sparse_conv_apply_stats(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
                                 const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip, float* y,
@@ -580,15 +580,23 @@ int gga_dense_wgrad3x3_block_amax(const float* x, const float* grad_y, int B, in
 /* ------------------------------------------------------------------------- */
 size_t gga_bn_relu_workspace_bytes(int64_t rows, int channels);
 size_t gga_bn_relu_mask_bytes(int64_t rows, int channels);   /* 1 bit / element ReLU sign */
-/* Batch statistics only (no normalised output): saved [2*channels] = mean / invstd, scale_shift
+/* Statistics only (no normalised output): saved [2*channels] = mean / invstd, scale_shift
  * [2*channels] = gamma*invstd, beta - mean*gamma*invstd; running stats updated when training. For
  * consumers that apply the affine + ReLU themselves while loading (gga_head_conv3x3_* with
  * in_scale_shift), so the normalised activation is never written. Its backward is
- * gga_bn_relu_bwd_ex with relu = 2 and mask_bits = scale_shift: the ReLU mask is
- * recomputed as fma(x, scale, shift) > 0 instead of read from stored bits. */
+ * gga_bn_relu_bwd with relu = 2 and mask_bits = scale_shift: the ReLU mask is
+ * recomputed as fma(x, scale, shift) > 0 instead of read from stored bits.
+ * partials != NULL: batch statistics (whatever `training` says) from per-channel sums already reduced by the producer of x:
+ * n_partials >= 1 rows [2][partials_width] f64 (sum, sum of squares over disjoint row sets that together cover all `rows`), of
+ * which this BatchNorm's channels are columns column_offset .. column_offset + channels (partials_width = channels,
+ * column_offset = 0: rows of its own; wider: a convolution launch that computed the inputs of several BatchNorms side by
+ * side, the head's paired first convolutions). x and workspace may then be NULL.
+ * partials == NULL: a reduce pass over x (training) or the running statistics; x and workspace required, partials_width and
+ * column_offset ignored. */
 int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                  int64_t rows, int channels, float eps, float momentum, int training, float* saved,
-                 float* scale_shift, void* workspace, size_t workspace_bytes, void* stream);
+                 float* scale_shift, const double* partials, int n_partials, int partials_width, int column_offset,
+                 void* workspace, size_t workspace_bytes, void* stream);
 /* Forward: saved [2*channels] f32 receives mean / invstd; running stats are updated when training. relu != 0 also writes
  * mask_bits (gga_bn_relu_mask_bytes). y may be a column block of a wider row-major matrix:
  * row r starts at y + r * y_row_stride (floats; a multiple of 4, >= channels; the
@@ -605,15 +613,15 @@ int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* r
  * amax_y / amax_grad_x (NULL: none): the bits of the largest finite magnitude written (y /
  * grad_x), max-combined into *amax (the caller zeroes it; several calls may share it) - what the two-fp16-plane
  * convolution kernels that consume the tensor derive their scale from, without a pass of their own. */
-int gga_bn_relu_fwd_ex(const float* x, const float* residual, const float* gamma, const float* beta,
-                       float* running_mean, float* running_var, int64_t rows, int channels, float eps, float momentum,
-                       int training, int relu, float* y, int64_t y_row_stride, void* mask_bits, float* saved,
-                       const double* partials, int n_partials, uint32_t* amax_y, void* workspace, size_t workspace_bytes,
-                       void* stream);
-int gga_bn_relu_bwd_ex(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
-                       const float* gamma, const float* saved, int64_t rows, int channels, int relu, int training, float* grad_x,
-                       float* grad_residual, float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x, void* workspace,
-                       size_t workspace_bytes, void* stream);
+int gga_bn_relu_fwd(const float* x, const float* residual, const float* gamma, const float* beta,
+                    float* running_mean, float* running_var, int64_t rows, int channels, float eps, float momentum,
+                    int training, int relu, float* y, int64_t y_row_stride, void* mask_bits, float* saved,
+                    const double* partials, int n_partials, uint32_t* amax_y, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int gga_bn_relu_bwd(const float* grad_y, int64_t grad_y_row_stride, const float* x, const void* mask_bits,
+                    const float* gamma, const float* saved, int64_t rows, int channels, int relu, int training, float* grad_x,
+                    float* grad_residual, float* grad_gamma, float* grad_beta, uint32_t* amax_grad_x, void* workspace,
+                    size_t workspace_bytes, void* stream);
 /* sums[c] = sum over the rows of x [rows, channels] (row major; channels / 4 must divide 256) - the bias gradient of a
  * convolution from its output gradient in channels-last memory. Workspace: gga_bn_relu_workspace_bytes(rows, channels). */
 int gga_column_sums(const float* x, int64_t rows, int channels, float* sums, void* workspace, size_t workspace_bytes,
@@ -629,7 +637,7 @@ int gga_bn_relu_bwd_partials(const float* grad_masked, int64_t grad_row_stride, 
  * group of channels / groups channels): replaces the GN + ReLU of the ConvModules in the PGD / FCOS3D head
  * (mmdet3d/models/dense_heads/anchor_free_mono3d_head.py:160-250, norm_cfg type 'GN'), whose framework kernels need NCHW
  * memory. stat [B][groups][2] = mean, rstd; scale_shift [B][2][channels]; both are kept for the backward, which
- * recomputes the ReLU mask from x. channels/4 must divide 256, channels per group % 4 == 0. amax_* as in gga_bn_relu_*_ex. */
+ * recomputes the ReLU mask from x. channels/4 must divide 256, channels per group % 4 == 0. amax_* as in gga_bn_relu_fwd / _bwd. */
 size_t gga_gn_relu_workspace_bytes(int B, int channels);
 int gga_gn_relu_fwd(const float* x, const float* gamma, const float* beta, int B, int64_t rows_per_sample, int channels,
                     int groups, float eps, int relu, float* y, float* stat, float* scale_shift, uint32_t* amax_y,
@@ -637,18 +645,6 @@ int gga_gn_relu_fwd(const float* x, const float* gamma, const float* beta, int B
 int gga_gn_relu_bwd(const float* grad_y, const float* x, const float* gamma, const float* stat, const float* scale_shift,
                     int B, int64_t rows_per_sample, int channels, int groups, int relu, float* grad_x, float* grad_gamma,
                     float* grad_beta, uint32_t* amax_grad_x, void* workspace, size_t workspace_bytes, void* stream);
-
-/* gga_bn_stats in training mode with the per-channel sums already reduced by the producer of
- * x: partials [n_partials][2][channels] f64 (sum, sum of squares over disjoint row sets that
- * together cover all `rows`), as for gga_bn_relu_fwd_ex. */
-int gga_bn_stats_partials(const float* gamma, const float* beta, float* running_mean, float* running_var,
-                          int64_t rows, int channels, float eps, float momentum, float* saved, float* scale_shift,
-                          const double* partials, int n_partials, void* stream);
-/* The same for a BatchNorm whose channels are columns column_offset .. + channels of partial rows [2][partials_width] (a
- * convolution launch that computed the inputs of several BatchNorms side by side: the head's paired first convolutions). */
-int gga_bn_stats_partials_cols(const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t rows,
-                               int channels, float eps, float momentum, float* saved, float* scale_shift, const double* partials,
-                               int n_partials, int partials_width, int column_offset, void* stream);
 
 /* a5 (output convs of the head branches): 3x3 conv, 64 input channels -> 1..4 output channels,
  * stride 1, pad 1, + bias. Replaces the last layer of each SeparateHead branch,

@@ -57,6 +57,30 @@ def test_argument_validation_without_gpu():
     assert rc == -1 and b'multiple of 4' in L.gga_last_error()
 
 
+def test_batchnorm_entry_points_validate_without_gpu():
+    # the three BatchNorm compute entry points refuse before any HIP call, under their own names (which also shows that the
+    # ctypes signatures line up with the C ones up to the point of validation)
+    L = _lib.lib()
+    rows, C, p = 100, 64, 4096          # p: a non-null, 16 B aligned stand-in for a device pointer; nothing here dereferences it
+
+    def stats(x, channels, partials, n_partials, width, col):
+        return L.gga_bn_stats(x, p, p, p, p, rows, channels, 1e-3, 0.01, 1, p, p, partials, n_partials, width, col, p, 1 << 30, None)
+
+    def refused(name):
+        return L.gga_last_error().decode().startswith(name + ':')
+
+    assert stats(None, C, None, 0, 0, 0) == -1 and refused('gga_bn_stats') and 'both null' in L.gga_last_error().decode()
+    assert stats(None, C, p, 0, C, 0) == -1 and refused('gga_bn_stats')                     # n_partials < 1
+    assert stats(None, C, p, 8, 2 * C, C + 4) == -1 and refused('gga_bn_stats')             # partials_width < column_offset + channels
+    assert 'columns' in L.gga_last_error().decode()
+    assert stats(None, C, p, 8, 2 * C, -4) == -1 and refused('gga_bn_stats')                # column_offset < 0
+    assert stats(p, 6, None, 0, 0, 0) == -1 and refused('gga_bn_stats') and 'channels' in L.gga_last_error().decode()
+    rc = L.gga_bn_relu_fwd(p, None, p, p, p, p, rows, 6, 1e-3, 0.01, 1, 1, p, 6, p, p, None, 0, None, p, 1 << 30, None)
+    assert rc == -1 and refused('gga_bn_relu_fwd')
+    rc = L.gga_bn_relu_bwd(p, 6, p, p, p, p, rows, 6, 1, 1, p, None, p, p, None, p, 1 << 30, None)
+    assert rc == -1 and refused('gga_bn_relu_bwd')
+
+
 def test_loss_stages_validate_their_task_table_without_gpu():
     # the head-loss entry points take a gga_task_table: a null table and a task count outside 1..GGA_MAX_TASKS are rejected
     # before any HIP call, and the message names the entry point (the two workspace-size functions take no table: they are

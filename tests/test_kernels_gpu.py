@@ -285,9 +285,9 @@ def test_box_loss_terms_are_the_box_losses_with_scalar_outputs():
 
 
 def test_bn_statistics_from_a_column_block_of_wider_partial_rows():
-    """gga_bn_stats_partials_cols (the head's paired first convolutions: one [tiles, 2, 128] statistics array, two BatchNorms of
-    64 channels) against gga_bn_stats_partials on contiguous copies of the halves: the same saved statistics, scale / shift and
-    running buffers, bit for bit."""
+    """gga_bn_stats on a column block of wider partial rows (the head's paired first convolutions: one [tiles, 2, 128] statistics
+    array, two BatchNorms of 64 channels) against the same entry point on contiguous copies of the halves: the same saved
+    statistics, scale / shift and running buffers, bit for bit."""
     from gga_amd import _lib
     L = _lib.lib()
     tiles, C, rows = 200, 64, 16 * 248 * 216
@@ -300,13 +300,9 @@ def test_bn_statistics_from_a_column_block_of_wider_partial_rows():
         for form in ('cols', 'copy'):
             rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
             saved, ss = torch.empty(2 * C, device=DEV), torch.empty(2 * C, device=DEV)
-            if form == 'cols':
-                rc = L.gga_bn_stats_partials_cols(F._p(gam), F._p(bet), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, F._p(saved), F._p(ss),
-                                                  F._p(st), tiles, 2 * C, col, F._stream())
-            else:
-                half = st[:, :, col:col + C].contiguous()
-                rc = L.gga_bn_stats_partials(F._p(gam), F._p(bet), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, F._p(saved), F._p(ss),
-                                             F._p(half), tiles, F._stream())
+            part, width, first = (st, 2 * C, col) if form == 'cols' else (st[:, :, col:col + C].contiguous(), C, 0)
+            rc = L.gga_bn_stats(None, F._p(gam), F._p(bet), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, 1, F._p(saved), F._p(ss),
+                                F._p(part), tiles, width, first, None, 0, F._stream())
             assert rc == 0
             out.append((rm, rv, saved, ss))
         for a, b in zip(*out):
@@ -495,7 +491,8 @@ def test_bn_relu_cat_vs_torch():
     xa = [x.clone().requires_grad_(True) for x in xs]
     xb = [x.clone().requires_grad_(True) for x in xs]
     y = F.bn_relu_cat(xa, bns)
-    assert 'BNActCat' in type(y.grad_fn).__name__ and y.is_contiguous(memory_format=torch.channels_last)
+    # one node for the three blocks (the plain composition would end in a CatBackward)
+    assert 'BNAct' in type(y.grad_fn).__name__ and y.is_contiguous(memory_format=torch.channels_last)
     ref = torch.cat([torch.relu(bn(x)) for bn, x in zip(refs, xb)], dim=1)
     torch.testing.assert_close(y, ref, rtol=1e-4, atol=1e-4)
     g = torch.randn_like(ref)
@@ -512,6 +509,42 @@ def test_bn_relu_cat_vs_torch():
     # a single branch / an NCHW input take the plain composition
     z = F.bn_relu_cat([xs[0].contiguous()], [bns[0]])
     assert z.shape == xs[0].shape
+
+
+@pytest.mark.parametrize('chans,B,H,W', [((64, 128), 2, 7, 5), ((128, 128, 128), 2, 132, 124), ((128, 128, 128), 2, 132, 125)])
+def test_bn_relu_cat_is_bn_act_per_block_bit_for_bit(chans, B, H, W, monkeypatch):
+    """``bn_relu_cat(xs, bns)`` against ``torch.cat([bn_act(x, bn) ...], 1)``: one autograd Function over n column blocks and the
+    same Function once per block run the same kernels per block; only the row stride of the output and of its gradient
+    differs, and the reduce pass walks a dense element index whatever that stride is (``bn_strided``). Output, running
+    statistics, batch counters and every gradient are equal bit for bit.
+    (64, 128) at 2 x 7 x 5: unequal widths, a second block at a non-zero offset, fewer than 512 float4 per block (one workgroup
+    with a partial last run). (128, 128, 128) at 2 x 132 x 124: 1 047 552 float4 per block, 2046 workgroups - 1024 float4 short
+    of the BN_MAX_BLOCKS x 512 at which the grid is capped, every thread takes exactly one full run; at 2 x 132 x 125
+    (1 056 000 float4) the grid is capped at 2048 workgroups and the threads take a second, partial run."""
+    import copy
+    from gga_amd import dense_conv
+    monkeypatch.setattr(dense_conv, 'BN_BWD_FUSED', False)      # the plain kernels: the gradient below carries no BnPartials anyway
+    g = torch.Generator().manual_seed(17)
+    bns = [torch.nn.BatchNorm2d(c, eps=1e-3, momentum=0.01).to(DEV).train() for c in chans]
+    for bn in bns:
+        with torch.no_grad():
+            bn.weight.copy_(torch.rand(bn.num_features, generator=g) + 0.5), bn.bias.copy_(torch.rand(bn.num_features, generator=g) - 0.5)
+    twins = copy.deepcopy(bns)
+    xs = [(torch.randn(B, c, H, W, generator=g) * 2 + 0.3).to(DEV).contiguous(memory_format=torch.channels_last) for c in chans]
+    xa = [x.clone().requires_grad_(True) for x in xs]
+    xb = [x.clone().requires_grad_(True) for x in xs]
+    grad = torch.randn(B, sum(chans), H, W, generator=g).to(DEV).contiguous(memory_format=torch.channels_last)
+    y = F.bn_relu_cat(xa, bns)
+    assert 'BNAct' in type(y.grad_fn).__name__
+    ref = torch.cat([F.bn_act(x, bn, relu=True) for x, bn in zip(xb, twins)], dim=1)
+    assert torch.equal(y, ref)
+    y.backward(grad)
+    ref.backward(grad)
+    for a_, b_, bn, tw in zip(xa, xb, bns, twins):
+        assert torch.equal(bn.running_mean, tw.running_mean) and torch.equal(bn.running_var, tw.running_var)
+        assert torch.equal(bn.num_batches_tracked, tw.num_batches_tracked) and int(bn.num_batches_tracked) == 1
+        assert torch.equal(a_.grad, b_.grad)
+        assert torch.equal(bn.weight.grad, tw.weight.grad) and torch.equal(bn.bias.grad, tw.bias.grad)
 
 
 @pytest.mark.parametrize('cout,bias', [(1, True), (2, True), (3, True), (4, False)])

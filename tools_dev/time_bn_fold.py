@@ -13,7 +13,7 @@ for C, H, W in ((64, 248, 216), (128, 124, 108), (256, 62, 54)):
     saved, ss = torch.empty(2 * C, device=dev), torch.empty(2 * C, device=dev)
     ws = torch.empty(L.gga_bn_relu_workspace_bytes(rows, C), dtype=torch.uint8, device=dev)
     def stats():
-        _lib.check(L.gga_bn_stats(F._p(x), F._p(gamma), F._p(beta), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, 1, F._p(saved), F._p(ss), F._p(ws), ws.numel(), F._stream()), 'stats')
+        _lib.check(L.gga_bn_stats(F._p(x), F._p(gamma), F._p(beta), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, 1, F._p(saved), F._p(ss), None, 0, 0, 0, F._p(ws), ws.numel(), F._stream()), 'stats')
     for _ in range(3): stats()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

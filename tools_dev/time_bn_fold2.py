@@ -15,7 +15,7 @@ for C in (64, 128, 256):
         rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
         saved, ss = torch.empty(2 * C, device=dev), torch.empty(2 * C, device=dev)
         def go():
-            L.gga_bn_stats_partials(F._p(gam), F._p(bet), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, F._p(saved), F._p(ss), F._p(st), tiles, F._stream())
+            L.gga_bn_stats(None, F._p(gam), F._p(bet), F._p(rm), F._p(rv), rows, C, 1e-3, 0.01, 1, F._p(saved), F._p(ss), F._p(st), tiles, C, 0, None, 0, F._stream())
         for _ in range(20):
             go()
         torch.cuda.synchronize()
