@@ -127,6 +127,9 @@ SIGNATURES = {
     'gga_sparse_halo_build': (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp]),
     'gga_sparse_conv_apply_halo': (i32, [vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
     'gga_sparse_conv_wgrad_planes': (i32, [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    'gga_deconv_stream_tiles': (i64, [i64, i32, i32]),
+    'gga_deconv_stream_fwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    'gga_deconv_stream_bwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     'gga_absmax_bits': (i32, [vp, i64, i32, i64, vp, vp]),
     'gga_dense_conv3x3_pack_planes': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp]),
     'gga_dense_conv3x3_levels': (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp]),

@@ -502,6 +502,24 @@ int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride, const flo
                                  const int32_t* nbr, int64_t n_rows, int kvol, int cin, int cout, float* grad_weight,
                                  int planes, const uint32_t* amax_x, const uint32_t* amax_grad_out, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* The kernel = stride transposed convolution of SECONDFPN (necks/second_fpn.py:52-69; s = 1: the 1x1 product) as a streaming
+ * GEMM over the coarse pixels - no rule book, mask or permutation: every address is arithmetic on the pixel index
+ * (csrc/deconv_stream.hip). Two fp16 planes only, fp32 in and out; y and gx are bit for bit what the gather-GEMM over the
+ * arithmetic rule book gives (gga_sparse_conv_apply_stats, gga_amd/strided_conv.py).
+ *   forward        x [B*h*w, cin] -> y [B, s*h, s*w, cout] channels-last (every element written exactly once);
+ *                  stats (NULL: none) [gga_deconv_stream_tiles(B*h*w, cin, s)][2][cout] f64: sum and sum of squares per
+ *                  (tap, pixel tile) - the partials gga_bn_relu_fwd takes; fp32 inside a 32-pixel block, as the gather kernel.
+ *   backward-data  gy [B, s*h, s*w, cout] -> gx [B*h*w, cin]; all cin columns from one pass over gy.
+ * weight_blocks: HOST array of device pointers to the packed operands (gga_pack_weights_table, gather layout) of the
+ * 128-column blocks - forward: W[ky][kx][cin][cout block], cout / 128 of them; backward-data: W[ky][kx][cout][cin block],
+ * one of min(cin, 128) columns per 128 input channels. amax_*: the operands' absmax bits. cin 64, 128 or 256; cout a
+ * multiple of 128 (backward-data: 128, 256 or 512); 1 <= s <= 4; B * h * w * s * s < 2^31. */
+int64_t gga_deconv_stream_tiles(int64_t n_pixels, int cin, int s);
+int gga_deconv_stream_fwd(const float* x, const void* const* weight_blocks, const uint32_t* amax_x,
+                          const uint32_t* amax_weight, int B, int h, int w, int cin, int cout, int s, float* y, double* stats,
+                          void* stream);
+int gga_deconv_stream_bwd(const float* gy, const void* const* weight_blocks, const uint32_t* amax_gy,
+                          const uint32_t* amax_weight, int B, int h, int w, int cin, int cout, int s, float* gx, void* stream);
 /* split_weight of the dense 3x3 kernels straight from the framework's [cout, cin, 3, 3] parameter with
  * arbitrary element strides (channels-last parameters included): size
  * gga_sparse_split_weight_bytes(9, cin, cout); backward != 0 packs the operand of the
