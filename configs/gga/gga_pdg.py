@@ -33,16 +33,41 @@ model = dict(
     test_cfg=dict(use_rotate_nms=True, nms_across_levels=False, nms_pre=100, nms_thr=0.05, score_thr=0.001, min_bbox_size=0,
                   max_per_img=20))
 
-# KITTI mono3d data on the GGA pseudo labels (dataset / pipeline classes of the image branch are not built here)
+# KITTI mono3d data on the GGA pseudo labels (gga_amd/kitti_mono.py, gga_amd/image_pipelines.py)
 dataset_type = 'KittiMonoDataset'
 data_root = 'data/kitti/'
 input_modality = dict(use_lidar=False, use_camera=True)
 img_norm_cfg = dict(mean=[103.530, 116.280, 123.675], std=[1.0, 1.0, 1.0], to_rgb=False)
+train_pipeline = [
+    dict(type='LoadImageFromFileMono3D'),
+    dict(type='LoadAnnotations3D', with_bbox=True, with_label=True, with_attr_label=False, with_bbox_3d=True, with_label_3d=True,
+         with_bbox_depth=True),
+    dict(type='Resize', img_scale=(1242, 375), keep_ratio=True),
+    dict(type='RandomFlip3D', flip_ratio_bev_horizontal=0.5),
+    dict(type='Normalize', **img_norm_cfg),
+    dict(type='Pad', size_divisor=32),
+    dict(type='DefaultFormatBundle3D', class_names=class_names),
+    dict(type='Collect3D', keys=['img', 'gt_bboxes', 'gt_labels', 'gt_bboxes_3d', 'gt_labels_3d', 'centers2d', 'depths']),
+]
+test_pipeline = [
+    dict(type='LoadImageFromFileMono3D'),
+    dict(type='MultiScaleFlipAug', scale_factor=1.0, flip=False,
+         transforms=[dict(type='RandomFlip3D'), dict(type='Normalize', **img_norm_cfg), dict(type='Pad', size_divisor=32),
+                     dict(type='DefaultFormatBundle3D', class_names=class_names, with_label=False),
+                     dict(type='Collect3D', keys=['img'])]),
+]
 data = dict(samples_per_gpu=12, workers_per_gpu=3,
             train=dict(type=dataset_type, data_root=data_root,
                        ann_file=data_root + 'kitti_infos_trainval_GGA_pseudo_mono3d.coco.json',
                        info_file=data_root + 'kitti_infos_trainval_GGA_pseudo.pkl', img_prefix=data_root,
                        classes=class_names, modality=input_modality, test_mode=False, box_type_3d='Camera'))
+data['train']['pipeline'] = train_pipeline
+data['val'] = dict(type=dataset_type, data_root=data_root, ann_file=data_root + 'kitti_infos_trainval_GGA_pseudo_mono3d.coco.json',
+                   info_file=data_root + 'kitti_infos_trainval_GGA_pseudo.pkl', img_prefix=data_root, classes=class_names,
+                   pipeline=test_pipeline, modality=input_modality, test_mode=True, box_type_3d='Camera')
+data['test'] = dict(type=dataset_type, data_root=data_root, ann_file=data_root + 'kitti_infos_test_mono3d.coco.json',
+                    info_file=data_root + 'kitti_infos_test.pkl', img_prefix=data_root, classes=class_names,
+                    pipeline=test_pipeline, modality=input_modality, test_mode=True, box_type_3d='Camera')
 
 optimizer = dict(type='SGD', lr=0.001, momentum=0.9, weight_decay=0.0001, paramwise_cfg=dict(bias_lr_mult=2., bias_decay_mult=0.))
 optimizer_config = dict(grad_clip=dict(max_norm=35, norm_type=2))

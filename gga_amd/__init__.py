@@ -27,5 +27,6 @@ from .config import Config  # noqa: E402,F401
 from .registry import build_detector, build_model  # noqa: E402,F401
 from .pseudo_labels import pseudo_label_matching_kitti  # noqa: E402,F401
 from . import datasets  # noqa: E402,F401  (registers KittiDataset_GGA_train / LoadAnnotations3D)
+from . import image_pipelines, kitti_mono  # noqa: E402,F401  (registers KittiMonoDataset and the image transforms of configs/gga/gga_pdg.py)
 from . import indoor_datasets  # noqa: E402,F401  (registers SUNRGBDDataset, ScanNetDataset, S3DISDataset)
 from . import weight_bank  # noqa: E402,F401  (registers the process-wide optimizer-step hook that invalidates packed weights)

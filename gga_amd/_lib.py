@@ -62,6 +62,15 @@ class TtaTable(C.Structure):
                 ('hflip', C.c_int32 * TTA_MAX_VIEWS), ('vflip', C.c_int32 * TTA_MAX_VIEWS), ('map', TtaMap * TTA_MAX_MAPS)]
 
 
+IMAGE_BATCH_MAX = 64                # GGA_IMAGE_BATCH_MAX
+
+
+class ImageDesc(C.Structure):
+    """gga_image_desc: where one image of a batch lies in the source buffer, its size there and in the output, its flip."""
+    _fields_ = [('src_offset', C.c_int64), ('src_h', C.c_int32), ('src_w', C.c_int32), ('dst_h', C.c_int32), ('dst_w', C.c_int32),
+                ('flip', C.c_int32), ('reserved', C.c_int32)]
+
+
 class LossParams(C.Structure):
     _fields_ = [('B', C.c_int32), ('K', C.c_int32), ('fm_w', C.c_int32),
                 ('voxel_size', C.c_float * 2), ('out_size_factor', C.c_float),
@@ -185,6 +194,8 @@ SIGNATURES = {
     'gga_kitti_eval_stats': (i32, [vp, i32, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32,
                                    i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_kitti_format_dets': (i32, [vp, vp, vp, i64, vp, i32, vp, vp, vp, C.POINTER(C.c_float * 6), vp, vp, vp, vp, vp]),
+    'gga_kitti_format_dets_cam': (i32, [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+    'gga_image_batch': (i32, [vp, i64, C.POINTER(ImageDesc), i32, vp, i32, i32, i32, i32, vp, vp]),
     'gga_indoor_eval_match': (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]),
     'gga_indoor_eval_workspace_bytes': (sz, [i64, i32]),
     'gga_indoor_eval_assign': (i32, [vp, vp, vp, vp, i64, vp, i64, i32, C.POINTER(C.c_float * 8), i32, vp, vp, sz, vp]),

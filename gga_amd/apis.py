@@ -14,8 +14,9 @@ from .loader import build_dataloader, build_dataset, chunks_in, to_step_inputs
 from .registry import build_detector
 
 
-def single_gpu_test(model, data_loader, device=None, progress=None, planes=None):
-    """``model(return_loss=False, rescale=True, **batch)`` over the loader -> list with one result dict per frame.
+def single_gpu_test(model, data_loader, device=None, progress=None, planes=None, channels_last=False):
+    """``model(return_loss=False, rescale=True, **batch)`` over the loader -> list with one result dict per frame. Image
+    batches (the mono3d branch) are built on ``device`` (``loader.to_step_inputs``), ``channels_last``: in that memory format.
     ``planes``: arithmetic of the matrix kernels for the run (``dense_conv.PLANES``: 2 = the two-fp16-plane form a guarded
     training run stayed on - ``generate_pseudo_labels`` passes what the checkpoint records -, 3 / None = the library default)."""
     from . import dense_conv
@@ -29,7 +30,7 @@ def single_gpu_test(model, data_loader, device=None, progress=None, planes=None)
         for batch in data_loader:
             for chunk in range(chunks_in(batch)):      # the loader may deliver several per-GPU chunks: one after the other here
                 # test-time layout: every key is a list over augmentations of a list over frames
-                data = to_step_inputs(batch, device, chunk)
+                data = to_step_inputs(batch, device, chunk, channels_last=channels_last)
                 with torch.no_grad():
                     out = model(return_loss=False, rescale=True, **data)
                 results.extend(out)
@@ -91,11 +92,11 @@ def collect_results(part, size, tmpdir=None, gpu_collect=False):
     return ordered[:size]
 
 
-def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=False, device=None, progress=None, planes=None):
+def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=False, device=None, progress=None, planes=None, channels_last=False):
     """mmdet ``multi_gpu_test`` (tools/generate_pseudo_labels_gga.py:242 of the reference, started per GPU by
     tools/dist_pseudo.sh:11-22): every rank tests its shard of the loader, rank 0 returns the results of the whole dataset in
     dataset order."""
-    part = single_gpu_test(model, data_loader, device, progress, planes)
+    part = single_gpu_test(model, data_loader, device, progress, planes, channels_last)
     return collect_results(part, len(data_loader.dataset), tmpdir, gpu_collect)
 
 
@@ -110,7 +111,7 @@ def load_weights(model, filename, map_location='cpu', strict=False):
 
 
 def generate_pseudo_labels(cfg, checkpoint, out=None, eval_metrics=('mAP',), eval_options=None, device='cuda:0', model=None,
-                           channels_last=True, progress=None, distributed=False, tmpdir=None, gpu_collect=False):
+                           channels_last=True, progress=None, distributed=False, tmpdir=None, gpu_collect=False, format_only=False):
     """The flow of the reference's tool for one process: dataset ``cfg.data.test`` in test mode, loader
     (``cfg.data.test_dataloader`` over the defaults samples_per_gpu=1, workers_per_gpu=2, no shuffling), detector from
     ``cfg.model`` with the checkpoint's weights (``model``: an already built detector instead), ``single_gpu_test``, the raw
@@ -118,7 +119,9 @@ def generate_pseudo_labels(cfg, checkpoint, out=None, eval_metrics=('mAP',), eva
     dataset writes the pseudo-label file there (``pseudo_label_file`` in ``eval_options`` names it). -> (outputs, what
     ``evaluate`` returned or None). ``distributed`` (one process per GPU, process group initialised - ``train.init_dist``):
     the frames are sharded over the ranks (``multi_gpu_test``), rank 0 collects, writes and evaluates; the other ranks
-    return (None, None)."""
+    return (None, None). ``format_only`` (tools/test.py ``--format-only`` of the reference): no evaluation -
+    ``dataset.format_results(outputs, **eval_options)`` writes the result / submission files (``pklfile_prefix``,
+    ``submission_prefix``), formatting on ``device`` where the dataset takes one; -> (outputs, None)."""
     device = torch.device(device)
     test_cfg = cfg.data['test']
     test_cfg['test_mode'] = True
@@ -144,17 +147,26 @@ def generate_pseudo_labels(cfg, checkpoint, out=None, eval_metrics=('mAP',), eva
             from .cnn import to_channels_last
             model = to_channels_last(model)
     if distributed:
-        outputs = multi_gpu_test(model, loader, tmpdir, gpu_collect, device, progress, planes)
+        outputs = multi_gpu_test(model, loader, tmpdir, gpu_collect, device, progress, planes, channels_last)
         if outputs is None:                    # not rank 0
             return None, None
     else:
-        outputs = single_gpu_test(model, loader, device, progress, planes)
+        outputs = single_gpu_test(model, loader, device, progress, planes, channels_last)
     if out:
         if not out.endswith(('.pkl', '.pickle')):
             raise ValueError('The output file must be a pkl file.')
         with open(out, 'wb') as f:
             pickle.dump(outputs, f)
     result = None
+    if format_only:
+        import inspect
+        kwargs = dict(eval_options or {})
+        if 'device' in inspect.signature(dataset.format_results).parameters:
+            kwargs.setdefault('device', str(device))
+        _, tmp_dir = dataset.format_results(outputs, **kwargs)
+        if tmp_dir is not None:
+            tmp_dir.cleanup()
+        return outputs, None
     if eval_metrics:
         kwargs = dict(cfg.get('evaluation', {}))
         for key in ('interval', 'tmpdir', 'start', 'gpu_collect', 'save_best', 'rule'):          # hook arguments, not evaluate()'s

@@ -254,6 +254,18 @@ class CameraInstance3DBoxes:
     def to(self, device):
         return CameraInstance3DBoxes(self.tensor.to(device), box_dim=self.box_dim, with_yaw=self.with_yaw)
 
+    def flip(self, bev_direction='horizontal'):
+        """cam_box3d.py:218-239, in place: horizontal x -> -x, yaw -> -yaw + pi; vertical z -> -z, yaw -> -yaw."""
+        assert bev_direction in ('horizontal', 'vertical')
+        if bev_direction == 'horizontal':
+            self.tensor[:, 0::7] = -self.tensor[:, 0::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6] + np.pi
+        else:
+            self.tensor[:, 2::7] = -self.tensor[:, 2::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6]
+
     @property
     def corners(self):
         if self.tensor.numel() == 0:

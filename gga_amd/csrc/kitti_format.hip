@@ -127,3 +127,95 @@ extern "C" int gga_kitti_format_dets(const float* boxes, const float* scores, co
     GGA_CHECK_LAUNCH("gga_kitti_format_dets");
     return GGA_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The camera-box variant (mmdet3d/datasets/kitti_mono_dataset.py `convert_valid_bboxes` :497-561 + `bbox2result_kitti`
+// :302-334): the detections of the image branch are camera boxes already, so there is no yaw limit, no change of frame and no
+// LiDAR range test - corners, projection by P2, min / max, valid = the 2D box meets the image, the clip, and
+// alpha = -atan2(x, z) + rotation_y. The reference also converts the boxes to the LiDAR frame and never reads the result;
+// that is left out. Same compaction and the same arithmetic rules as above.
+#define KFC_COLS 13           // GGA_KITTI_FORMAT_CAM_COLS
+
+__global__ __launch_bounds__(KF_WAVES * GGA_WAVE) void kitti_format_cam_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int64_t* __restrict__ labels, int64_t n_dets,
+    const int64_t* __restrict__ frame_offsets, int n_frames, const float* __restrict__ p2, const int32_t* __restrict__ image_hw,
+    float* __restrict__ out_cols, int64_t* __restrict__ out_labels, int32_t* __restrict__ valid_counts) {
+    const int lane = threadIdx.x & (GGA_WAVE - 1);
+    const int frame = blockIdx.x * KF_WAVES + (threadIdx.x >> 6);        // wave-uniform
+    if (frame >= n_frames) return;
+    const int64_t begin = frame_offsets[frame], end = frame_offsets[frame + 1];
+    if (begin < 0 || end < begin || end > n_dets) {                      // offsets that do not fit the totals: nothing written
+        if (lane == 0) valid_counts[frame] = 0;
+        return;
+    }
+    const float* pm = p2 + (int64_t)frame * 16;
+    const float img_h = (float)image_hw[2 * frame], img_w = (float)image_hw[2 * frame + 1];
+    int base = 0;
+    for (int64_t chunk = begin; chunk < end; chunk += GGA_WAVE) {        // trip count is the same for all lanes of the wave
+        const int64_t i = chunk + lane;
+        const bool live = i < end;
+        bool valid = false;
+        float col[KFC_COLS];
+        int64_t label = 0;
+        if (live) {
+            const float* b = boxes + i * 7;
+            const float x = b[0], y = b[1], z = b[2], sx = b[3], sy = b[4], sz = b[5], ry = b[6];
+            // corners: dims * (a - 0.5, b - 1, c - 0.5), rotated about the camera's y axis, moved to the centre; projected by P2
+            const float cs = (float)cos((double)ry), sn = (float)sin((double)ry);
+            float minx = INFINITY, miny = INFINITY, maxx = -INFINITY, maxy = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float px = sx * ((k & 4) ? 0.5f : -0.5f);
+                const float py = sy * ((k & 2) ? 0.f : -1.f);
+                const float pz = sz * ((k & 1) ? 0.5f : -0.5f);
+                const float qx = px * cs + pz * sn + x;
+                const float qy = py + y;
+                const float qz = px * -sn + pz * cs + z;
+                const float u = qx * pm[0] + qy * pm[1] + qz * pm[2] + pm[3];
+                const float v = qx * pm[4] + qy * pm[5] + qz * pm[6] + pm[7];
+                const float w = qx * pm[8] + qy * pm[9] + qz * pm[10] + pm[11];
+                const float iu = u / w, iv = v / w;
+                minx = fminf(minx, iu);
+                maxx = fmaxf(maxx, iu);
+                miny = fminf(miny, iv);
+                maxy = fmaxf(maxy, iv);
+            }
+            valid = minx < img_w && miny < img_h && maxx > 0.f && maxy > 0.f;
+            col[0] = fmaxf(minx, 0.f);
+            col[1] = fmaxf(miny, 0.f);
+            col[2] = fminf(maxx, img_w);
+            col[3] = fminf(maxy, img_h);
+            col[4] = sx; col[5] = sy; col[6] = sz;
+            col[7] = x; col[8] = y; col[9] = z;
+            col[10] = ry;
+            col[11] = -(float)atan2((double)x, (double)z) + ry;
+            col[12] = scores[i];
+            label = labels[i];
+        }
+        const unsigned long long mask = __ballot(valid);
+        if (valid) {
+            const int64_t row = begin + base + __popcll(mask & ((1ull << lane) - 1ull));     // < end <= n_dets
+            float* o = out_cols + row * KFC_COLS;
+#pragma unroll
+            for (int k = 0; k < KFC_COLS; ++k) o[k] = col[k];
+            out_labels[row] = label;
+        }
+        base += __popcll(mask);
+    }
+    if (lane == 0) valid_counts[frame] = base;
+}
+
+extern "C" int gga_kitti_format_dets_cam(const float* boxes, const float* scores, const int64_t* labels, int64_t n_dets,
+                                         const int64_t* frame_offsets, int n_frames, const float* p2, const int32_t* image_hw,
+                                         float* out_cols, int64_t* out_labels, int32_t* valid_counts, void* stream) {
+    GGA_REQUIRE(n_dets >= 0 && n_frames >= 0, "gga_kitti_format_dets_cam: negative size (n_dets %lld, n_frames %d)", (long long)n_dets, n_frames);
+    if (n_frames == 0) return GGA_OK;
+    GGA_REQUIRE(frame_offsets && p2 && image_hw && valid_counts, "gga_kitti_format_dets_cam: null pointer (per-frame arrays)");
+    GGA_REQUIRE(n_dets == 0 || (boxes && scores && labels && out_cols && out_labels),
+                "gga_kitti_format_dets_cam: null pointer (per-detection arrays)");
+    const int blocks = (n_frames + KF_WAVES - 1) / KF_WAVES;
+    hipLaunchKernelGGL(kitti_format_cam_kernel, dim3(blocks), dim3(KF_WAVES * GGA_WAVE), 0, (hipStream_t)stream, boxes, scores, labels,
+                       n_dets, frame_offsets, n_frames, p2, image_hw, out_cols, out_labels, valid_counts);
+    GGA_CHECK_LAUNCH("gga_kitti_format_dets_cam");
+    return GGA_OK;
+}

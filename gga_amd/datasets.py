@@ -344,11 +344,11 @@ class LoadAnnotations3D:
                  with_bbox=False, with_label=False, with_mask=False, with_seg=False, with_bbox_depth=False, with_gga=False,
                  poly2mask=True, seg_3d_dtype=np.int64, file_client_args=dict(backend='disk')):
         for flag, name in ((with_attr_label, 'with_attr_label'), (with_mask_3d, 'with_mask_3d'), (with_seg_3d, 'with_seg_3d'),
-                           (with_mask, 'with_mask'), (with_seg, 'with_seg'), (with_bbox_depth, 'with_bbox_depth')):
+                           (with_mask, 'with_mask'), (with_seg, 'with_seg')):
             if flag:
-                raise NotImplementedError(f'LoadAnnotations3D({name}=True) is not on the GGA LiDAR path')
+                raise NotImplementedError(f'LoadAnnotations3D({name}=True) is not on the GGA paths')
         self.with_bbox_3d, self.with_label_3d, self.with_bbox, self.with_label = with_bbox_3d, with_label_3d, with_bbox, with_label
-        self.with_gga = with_gga
+        self.with_gga, self.with_bbox_depth = with_gga, with_bbox_depth
 
     def _load_bboxes_3d(self, results):
         results['gt_bboxes_3d'] = results['ann_info']['gt_bboxes_3d']
@@ -374,11 +374,17 @@ class LoadAnnotations3D:
     def __call__(self, results):
         if self.with_bbox:          # mmdet LoadAnnotations._load_bboxes for plain arrays
             results['gt_bboxes'] = results['ann_info']['bboxes'].copy()
+            if results['ann_info'].get('bboxes_ignore') is not None:
+                results['gt_bboxes_ignore'] = results['ann_info']['bboxes_ignore'].copy()
+                results['bbox_fields'].append('gt_bboxes_ignore')
             results['bbox_fields'].append('gt_bboxes')
         if self.with_label:
             results['gt_labels'] = results['ann_info']['labels'].copy()
         if self.with_bbox_3d:
             results = self._load_bboxes_3d(results)
+        if self.with_bbox_depth:          # _load_bboxes_depth (loading.py:561-572)
+            results['centers2d'] = results['ann_info']['centers2d']
+            results['depths'] = results['ann_info']['depths']
         if self.with_label_3d:
             results = self._load_labels_3d(results)
         if self.with_gga:

@@ -114,3 +114,75 @@ def format_kitti_dets(net_outputs, data_infos, class_names, pcd_limit_range, dev
                           dimensions=c[:, 4:7].copy(), location=c[:, 7:10].copy(), rotation_y=c[:, 10].copy(),
                           score=c[:, 12].copy(), sample_idx=np.array([info['image']['image_idx']] * k, dtype=np.int64)))
     return annos
+
+
+# ----------------------------------------------------------------------------- camera boxes (the image branch)
+CAM_COLS = 13      # GGA_KITTI_FORMAT_CAM_COLS: bbox 4, dimensions 3, location 3, rotation_y, alpha, score
+
+
+def format_columns_cam(boxes, scores, labels, frame_offsets, p2, image_hw, device):
+    """The raw call of the camera-box variant: boxes [N,7] f32 camera boxes, scores [N] f32, labels [N] i64, frame_offsets
+    [F+1] i64, p2 [F,4,4] f32, image_hw [F,2] i32 -> (columns [N, CAM_COLS] f32, labels [N] i64, counts [F] i32), rows as in
+    ``format_columns``. One upload, one launch of ``gga_kitti_format_dets_cam``, one download."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('gga_amd ops run on the GPU only; there is no CPU fallback in the product path')
+    n, f = int(boxes.shape[0]), int(len(frame_offsets) - 1)
+    ins = [np.ascontiguousarray(boxes, np.float32).reshape(n, 7), np.ascontiguousarray(scores, np.float32).reshape(n),
+           np.ascontiguousarray(labels, np.int64).reshape(n), np.ascontiguousarray(frame_offsets, np.int64).reshape(f + 1),
+           np.ascontiguousarray(p2, np.float32).reshape(f, 16), np.ascontiguousarray(image_hw, np.int32).reshape(f, 2)]
+    in_off, in_bytes = _section([a.nbytes for a in ins])
+    out_sizes = [n * CAM_COLS * 4, n * 8, f * 4]
+    out_off, out_bytes = _section(out_sizes)
+    host = np.zeros(max(in_bytes, 8), np.uint8)
+    for a, o in zip(ins, in_off):
+        host[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    with torch.cuda.device(dev):
+        d_in = torch.from_numpy(host).to(dev)
+        d_out = torch.zeros(max(out_bytes, 8), dtype=torch.uint8, device=dev)
+        pi = [C.c_void_p(d_in.data_ptr() + o) for o in in_off]
+        po = [C.c_void_p(d_out.data_ptr() + o) for o in out_off]
+        check(_lib.lib().gga_kitti_format_dets_cam(pi[0], pi[1], pi[2], n, pi[3], f, pi[4], pi[5], po[0], po[1], po[2], F._stream()),
+              'gga_kitti_format_dets_cam')
+        back = d_out.cpu().numpy()
+    cut = lambda k, dt: back[out_off[k]:out_off[k] + out_sizes[k]].view(dt)
+    return cut(0, np.float32).reshape(n, CAM_COLS), cut(1, np.int64), cut(2, np.int32)
+
+
+def format_kitti_dets_cam(net_outputs, anno_infos, class_names, device='cuda:0'):
+    """``KittiMonoDataset.bbox2result_kitti`` (mmdet3d/datasets/kitti_mono_dataset.py:271-384) for all frames at once ->
+    the list of KITTI anno dicts its host loop builds (same keys, dtypes, shapes, empty-frame placeholders).
+    ``net_outputs``: per frame a dict with ``boxes_3d`` (camera boxes), ``scores_3d``, ``labels_3d``."""
+    assert len(net_outputs) == len(anno_infos), 'invalid list length of network outputs'
+    nf = len(net_outputs)
+    tensors = [o['boxes_3d'].tensor for o in net_outputs]
+    counts = np.array([t.shape[0] for t in tensors], np.int64)
+    offsets = np.zeros(nf + 1, np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    if int(offsets[-1]):
+        boxes = torch.cat(tensors, 0)[:, :7].to('cpu', torch.float32).numpy()
+        scores = torch.cat([o['scores_3d'].reshape(-1) for o in net_outputs], 0).to('cpu', torch.float32).numpy()
+        labels_in = torch.cat([o['labels_3d'].reshape(-1) for o in net_outputs], 0).to('cpu', torch.int64).numpy()
+    else:
+        boxes, scores, labels_in = np.zeros((0, 7), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64)
+    p2, hw = np.zeros((nf, 4, 4), np.float32), np.zeros((nf, 2), np.int32)
+    for i, info in enumerate(anno_infos):
+        proj = info['calib']['P2'].astype(np.float32)
+        p2[i] = np.eye(4, dtype=np.float32)             # points_cam2img pads a 3 x 4 matrix with the identity's last row
+        p2[i, :proj.shape[0], :proj.shape[1]] = proj
+        hw[i] = info['image']['image_shape'][:2]
+    cols, labels, valid = format_columns_cam(boxes, scores, labels_in, offsets, p2, hw, device)
+    names = np.asarray(list(class_names))
+    name_len = np.array([len(c) for c in class_names], np.int64)
+    annos = []
+    for i, info in enumerate(anno_infos):
+        b, k = int(offsets[i]), int(valid[i])
+        if k == 0:
+            annos.append(_empty_anno())
+            continue
+        c, lab = cols[b:b + k], labels[b:b + k]
+        annos.append(dict(name=names[lab].astype(f'<U{int(name_len[lab].max())}'), truncated=np.zeros(k),
+                          occluded=np.zeros(k, dtype=np.int64), alpha=c[:, 11].copy(), bbox=c[:, 0:4].copy(),
+                          dimensions=c[:, 4:7].copy(), location=c[:, 7:10].copy(), rotation_y=c[:, 10].copy(),
+                          score=c[:, 12].copy(), sample_idx=np.array([info['image']['image_idx']] * k, dtype=np.int64)))
+    return annos

@@ -369,6 +369,7 @@ def into_arena(payloads, align=64):
 def pack_collated(collated, arena=True):
     """Replaces the per-frame lists inside a collated batch's containers by ``PackedFrames`` (in place; what cannot be packed
     - stacked payloads, meta dicts - stays); ``arena``: all of them in one byte buffer (``into_arena``)."""
+    from .image_pipelines import DeferredImage, PackedImages
     made = []
     for key, value in collated.items():
         if isinstance(value, DataContainer) and not value.stack and isinstance(value.data, list):
@@ -377,6 +378,13 @@ def pack_collated(collated, arena=True):
                 if packed is not None:
                     value.data[c] = packed
                     made.append(packed)
+        # deferred images (the mono3d branch), at train time and inside the test-time list over augmentations: the sources of
+        # a chunk as one uint8 buffer of their own
+        for container in (value if isinstance(value, list) else [value]):
+            if isinstance(container, DataContainer) and not container.stack and isinstance(container.data, list):
+                for c, chunk in enumerate(container.data):
+                    if isinstance(chunk, list) and chunk and all(isinstance(f, DeferredImage) for f in chunk):
+                        container.data[c] = PackedImages(chunk)
     if arena:
         into_arena(made)
     return collated
@@ -508,14 +516,36 @@ def _to_device(value, device, non_blocking):
     return value.to(device, non_blocking=non_blocking) if torch.is_tensor(value) else value
 
 
-def to_step_inputs(collated, device=None, chunk=0, non_blocking=True, uploader=None):
+def _image_tensor(value, device, channels_last):
+    """The ``img`` entry of a chunk -> the detector's image tensor: deferred images (``PackedImages`` or a list of
+    ``DeferredImage``) through ``image_pipelines.image_batch``, a stacked tensor of the eager path moved to the device."""
+    from .image_pipelines import DeferredImage, PackedImages, image_batch
+    if device is not None and torch.device(device).type != 'cuda':          # no GPU: the host arithmetic, the tensor stays where it is
+        device = None
+    if isinstance(value, PackedImages) or (isinstance(value, list) and value and all(isinstance(v, DeferredImage) for v in value)):
+        return image_batch(value, device, channels_last)
+    if isinstance(value, list):             # test-time: one entry per augmentation
+        return [_image_tensor(v, device, channels_last) for v in value]
+    if torch.is_tensor(value) and device is not None:
+        value = value.to(device, non_blocking=True)
+        return value.contiguous(memory_format=torch.channels_last) if channels_last else value
+    return value
+
+
+def to_step_inputs(collated, device=None, chunk=0, non_blocking=True, uploader=None, channels_last=False):
     """A collated batch -> the keyword inputs of the detector's ``forward_train`` (or ``forward_test``) for this rank's
     device: chunk ``chunk`` of every container, ``points`` on ``device`` (uploads from pinned memory are asynchronous:
     announce them with ``Runner.inputs_ready``), everything else as it left the pipeline. ``uploader``: a ``PointUploader``
-    that takes packed points to the device without stalling the calling thread (``Runner.train_epochs`` passes one)."""
+    that takes packed points to the device without stalling the calling thread (``Runner.train_epochs`` passes one).
+    An ``img`` entry becomes the image tensor [B, 3, Hp, Wp] on ``device`` (``channels_last``: in that memory format): built
+    there from the batch's uint8 buffer in one launch when the pipeline deferred the pixel work, on the host without a
+    device."""
     out = {}
     for key, value in collated.items():
         value = _take_chunk(value, chunk)
+        if key == 'img':
+            out[key] = _image_tensor(value, device, channels_last)
+            continue
         on_device = device is not None and key in DEVICE_KEYS
         if isinstance(value, PackedFrames):                 # one upload for the whole chunk, then per-frame views
             value = _unpack_frames(value, device if on_device else None, non_blocking, uploader)

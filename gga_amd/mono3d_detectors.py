@@ -274,6 +274,8 @@ class SingleStageMono3DDetector(nn.Module):
     def forward(self, return_loss=True, **kwargs):
         if return_loss:
             return self.forward_train(**kwargs)
+        if 'img' in kwargs:          # mmdet's BaseDetector.forward(img, img_metas, ...): the loader's ``img`` is forward_test's ``imgs``
+            kwargs['imgs'] = kwargs.pop('img')
         return self.forward_test(**kwargs)
 
     def _parse_losses(self, losses):

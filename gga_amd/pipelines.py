@@ -576,12 +576,46 @@ class GlobalRotScaleTrans:
 class RandomFlip3D:
     """Flips decided upstream (``flip`` / ``pcd_horizontal_flip`` / ``pcd_vertical_flip`` set by MultiScaleFlipAug3D) or drawn
     with the given ratios; LiDAR points: horizontal = y -> -y, vertical = x -> -x; Depth points: horizontal = x -> -x,
-    vertical = y -> -y (the coordinate systems' own ``flip``)."""
+    vertical = y -> -y (the coordinate systems' own ``flip``).
+
+    A sample with an image (``img_fields`` non-empty: the mono3d branch) goes through mmdet's ``RandomFlip`` first, as the
+    reference's class does by inheritance: ``flip`` is drawn with one ``np.random.choice(['horizontal', None])`` unless it is
+    set, the image and the ``bbox_fields`` are mirrored, and then transforms_3d.py:106-145 - the camera boxes, ``centers2d``
+    and the principal point of ``cam2img`` (width from ``ori_shape``, as the reference has it). Samples without an image
+    draw nothing here: the LiDAR pipelines keep their random stream."""
 
     def __init__(self, sync_2d=True, flip_ratio_bev_horizontal=0.0, flip_ratio_bev_vertical=0.0, **kwargs):
         self.sync_2d, self.h_ratio, self.v_ratio = sync_2d, flip_ratio_bev_horizontal, flip_ratio_bev_vertical
 
+    def _flip_image_sample(self, d):
+        from . import image_pipelines
+        if 'flip' not in d:
+            r = float(self.h_ratio or 0.0)
+            d['flip'] = np.random.choice(['horizontal', None], p=[r, 1 - r]) is not None
+        d.setdefault('flip_direction', 'horizontal' if d['flip'] else None)
+        if d['flip']:
+            assert d['flip_direction'] == 'horizontal' and self.sync_2d, 'Only support sync_2d=True and horizontal flip with images'
+            image_pipelines.flip_image(d)
+            image_pipelines.flip_bboxes(d)
+        d['pcd_horizontal_flip'], d['pcd_vertical_flip'] = d['flip'], False
+        d.setdefault('transformation_3d_flow', [])
+        if d['flip']:
+            if len(d['bbox3d_fields']) == 0:           # test mode
+                d['bbox3d_fields'].append('empty_box3d')
+                d['empty_box3d'] = d['box_type_3d'](np.array([], dtype=np.float32))
+            assert len(d['bbox3d_fields']) == 1
+            for key in d['bbox3d_fields']:
+                d[key].flip('horizontal')
+            if 'centers2d' in d:
+                w = d['ori_shape'][1]
+                d['centers2d'][..., 0] = w - d['centers2d'][..., 0]
+                d['cam2img'][0][2] = w - d['cam2img'][0][2]
+            d['transformation_3d_flow'].append('HF')
+        return d
+
     def __call__(self, d):
+        if d.get('img_fields'):
+            return self._flip_image_sample(d)
         d.setdefault('flip', False)
         if self.sync_2d:
             d['pcd_horizontal_flip'], d['pcd_vertical_flip'] = d['flip'], False
@@ -685,6 +719,12 @@ class DefaultFormatBundle3D:
         if 'points' in d:
             assert isinstance(d['points'], BasePoints)
             d['points'] = DC(d['points'].tensor)
+        if 'img' in d:              # the image branch (formating.py:42-74): the image, its 2D boxes / labels, centres, depths
+            from .image_pipelines import format_image
+            format_image(d)
+            for k in ('gt_bboxes', 'gt_bboxes_ignore', 'gt_labels', 'centers2d', 'depths'):
+                if k in d:
+                    d[k] = DC(to_tensor(d[k]))
         if self.with_gt and self.with_label:
             if 'gt_names_3d' in d:
                 d['gt_labels_3d'] = np.array([self.class_names.index(n) for n in d['gt_names_3d']], dtype=np.int64)

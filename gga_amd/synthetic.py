@@ -960,3 +960,92 @@ def make_kitti_eval_case(seed, n_frames, n_gt=10, n_dt=15, dt_dtype=np.float32):
             alpha=(d_rot_ - np.arctan2(d_loc_[:, 0], d_loc_[:, 2])).astype(dt_dtype), bbox=as_dt(d_bbox, (n, 4)),
             dimensions=as_dt(d_dims, (n, 3)), location=d_loc_, rotation_y=d_rot_, score=score.astype(dt_dtype)))
     return gt_annos, dt_annos
+
+
+# ---- KITTI mono3d tree (configs/gga/gga_pdg.py from a data root): images, the pseudo-labelled info file, the test info file
+def _tree_is_ours(root):
+    """An existing tree is only reused when this user owns it and nobody else can write to it (its pickles are loaded)."""
+    import os
+    import stat
+    try:
+        st = os.stat(root)
+    except OSError:
+        return False
+    return st.st_uid == os.getuid() and not (st.st_mode & (stat.S_IWGRP | stat.S_IWOTH))
+
+
+def write_kitti_mono_tree(root, n_frames, img_hw=(96, 320), seed=4300, n_obj_range=(2, 6), n_test=None, info_prefix='kitti'):
+    """Writes what steps 3-5 of the GGA recipe read for ``n_frames`` synthetic frames under ``root``:
+
+        training/image_2/%06d.png                     uint8 RGB noise images (PIL), a few pixels smaller than ``img_hw`` from
+                                                      frame to frame, as KITTI's are
+        testing/image_2/%06d.png                      ``n_test`` (default ``n_frames``) images of the test split
+        <prefix>_infos_trainval_GGA_pseudo.pkl        infos with ``annos`` (camera-frame objects in view, one ``DontCare``)
+        <prefix>_infos_test.pkl                       infos without ``annos``
+
+    -> (pseudo info path, test info path). ``kitti_converter_mono.export_2d_annotation`` turns either into the coco file
+    ``KittiMonoDataset`` reads. Deterministic in ``seed``; a tree written with the same arguments by this user is left alone
+    (stamp file ``synthetic_mono_tree.json``)."""
+    import json
+    import os
+    import pickle
+    from PIL import Image
+    n_test = n_frames if n_test is None else n_test
+    stamp = dict(n_frames=n_frames, img_hw=list(img_hw), seed=seed, n_obj_range=list(n_obj_range), n_test=n_test, prefix=info_prefix, v=1)
+    info_path = os.path.join(root, f'{info_prefix}_infos_trainval_GGA_pseudo.pkl')
+    test_path = os.path.join(root, f'{info_prefix}_infos_test.pkl')
+    stamp_path = os.path.join(root, 'synthetic_mono_tree.json')
+    if (_tree_is_ours(root) and os.path.exists(stamp_path) and json.load(open(stamp_path)) == stamp and os.path.exists(info_path)
+            and os.path.exists(test_path)):
+        return info_path, test_path
+    os.makedirs(root, mode=0o700, exist_ok=True)
+    names = np.array(['Pedestrian', 'Cyclist', 'Car'])
+    H0, W0 = img_hw
+
+    def frame(split, i, rng, with_annos):
+        H, W = H0 - int(rng.integers(0, 4)), W0 - int(rng.integers(0, 6))
+        os.makedirs(os.path.join(root, split, 'image_2'), exist_ok=True)
+        path = f'{split}/image_2/{i:06d}.png'
+        Image.fromarray(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)).save(os.path.join(root, path))
+        f = 721.5377 * W0 / 1242.0
+        P2 = np.array([[f, 0.0, W / 2.0, 44.85728 * W0 / 1242.0], [0.0, f, H / 2.0, 0.2163791], [0.0, 0.0, 1.0, 0.002745884],
+                       [0.0, 0.0, 0.0, 1.0]])
+        P0 = P2.copy()
+        P0[:3, 3] = 0.0
+        calib = dict(P0=P0, P2=P2, R0_rect=KITTI_CALIB['R0_rect'].copy(), Tr_velo_to_cam=KITTI_CALIB['Tr_velo_to_cam'].copy(),
+                     Tr_imu_to_velo=np.eye(4))
+        info = dict(image=dict(image_idx=i, image_shape=np.array([H, W], np.int32), image_path=path), calib=calib)
+        if not with_annos:
+            return info
+        n = int(rng.integers(n_obj_range[0], n_obj_range[1] + 1))
+        labels = rng.integers(0, 3, n)
+        dims = _MONO_DIMS[labels].astype(np.float64) * rng.uniform(0.9, 1.1, (n, 3))          # (l, h, w)
+        depth = rng.uniform(8.0, 40.0, n)
+        u, v = rng.uniform(0.15 * W, 0.85 * W, n), rng.uniform(0.45 * H, 0.75 * H, n)
+        loc = np.stack([(u - P2[0, 2]) * depth / f, (v - P2[1, 2]) * depth / f + dims[:, 1] / 2, depth], 1)        # bottom centre
+        rot = rng.uniform(-np.pi, np.pi, n)
+        bbox = np.zeros((n, 4))
+        for j in range(n):
+            c, s = np.cos(rot[j]), np.sin(rot[j])
+            k = np.array([[a, b, d] for a in (-0.5, 0.5) for b in (-1.0, 0.0) for d in (-0.5, 0.5)]) * dims[j]
+            pts = np.stack([k[:, 0] * c + k[:, 2] * s, k[:, 1], -k[:, 0] * s + k[:, 2] * c], 1) + loc[j]
+            q = np.concatenate([pts, np.ones((8, 1))], 1) @ P2.T
+            uu, vv = q[:, 0] / q[:, 2], q[:, 1] / q[:, 2]
+            bbox[j] = [max(uu.min(), 0.0), max(vv.min(), 0.0), min(uu.max(), W - 1.0), min(vv.max(), H - 1.0)]
+        pad = lambda a, fill: np.concatenate([a, np.full((1,) + a.shape[1:], fill, a.dtype)], 0)
+        info['annos'] = dict(
+            name=np.concatenate([names[labels], ['DontCare']]), truncated=pad(np.zeros(n), -1.0), occluded=pad(np.zeros(n, np.int64), -1),
+            alpha=pad(-np.arctan2(loc[:, 0], loc[:, 2]) + rot, -10.0), bbox=pad(bbox, 0.0), dimensions=pad(dims, -1.0),
+            location=pad(loc, -1000.0), rotation_y=pad(rot, -10.0), score=np.zeros(n + 1),
+            index=np.concatenate([np.arange(n), [-1]]).astype(np.int32), group_ids=np.arange(n + 1, dtype=np.int32),
+            difficulty=pad(np.zeros(n, np.int32), -1), num_points_in_gt=pad(rng.integers(20, 400, n).astype(np.int32), -1))
+        return info
+
+    infos = [frame('training', i, np.random.default_rng(seed + i), True) for i in range(n_frames)]
+    tests = [frame('testing', i, np.random.default_rng(seed + 100000 + i), False) for i in range(n_test)]
+    with open(info_path, 'wb') as fh:
+        pickle.dump(infos, fh)
+    with open(test_path, 'wb') as fh:
+        pickle.dump(tests, fh)
+    json.dump(stamp, open(stamp_path, 'w'))
+    return info_path, test_path

@@ -1059,6 +1059,38 @@ int gga_kitti_format_dets(const float* boxes, const float* scores, const int64_t
                           const int32_t* image_hw, const float* limit_range_host, float* out_cols, int64_t* out_labels,
                           float* out_yaw, int32_t* valid_counts, void* stream);
 
+/* The camera-box variant for the image branch (mmdet3d/datasets/kitti_mono_dataset.py:302-334,497-561): boxes [n_dets,7] f32 are
+ * CameraInstance3DBoxes rows (x, y_bottom, z, x_size, y_size, z_size, rotation_y). No yaw limit, no change of frame, no range
+ * test: the eight corners projected by p2, valid = the unclipped 2D box meets the image (x1 < w, y1 < h, x2 > 0, y2 > 0), the
+ * clip, alpha = -atan2(x, z) + rotation_y. out_cols [n_dets, GGA_KITTI_FORMAT_CAM_COLS] f32 = bbox (4), dimensions (3),
+ * location (3), rotation_y, alpha, score; rows, out_labels, valid_counts and the frame_offsets rule as above. */
+#define GGA_KITTI_FORMAT_CAM_COLS 13
+int gga_kitti_format_dets_cam(const float* boxes, const float* scores, const int64_t* labels, int64_t n_dets,
+                              const int64_t* frame_offsets, int n_frames, const float* p2, const int32_t* image_hw,
+                              float* out_cols, int64_t* out_labels, int32_t* valid_counts, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Image batch of the mono3d branch (gga_amd/image_pipelines.py).              */
+/* ------------------------------------------------------------------------- */
+/* One launch builds the detector's input from the uint8 sources of a whole batch. src: DEVICE buffer of src_bytes bytes that
+ * holds every image as H x W x 3 uint8 at its src_offset. images_host: HOST array of n_images <= GGA_IMAGE_BATCH_MAX records
+ * (checked here, then passed to the kernel by value). table: DEVICE [3,256] f32, table[c][v] = the normalised value of byte v
+ * in output channel c. out: DEVICE f32, [n_images,3,out_h,out_w] (GGA_LAYOUT_NCHW) or [n_images,out_h,out_w,3]
+ * (GGA_LAYOUT_NHWC), 16-byte aligned, out_w a multiple of 4; EVERY element is written (torch.empty is enough).
+ * Output pixel (b, c, y, x): 0 outside dst_h x dst_w; otherwise table[c][p], p = the fixed-point bilinear sample (weights
+ * of 1/2048, half-pixel centres, integers only; DESIGN.md "Image batch") of source channel c (2 - c with reverse_channels)
+ * of the src_h x src_w source resized to dst_h x dst_w, at (y, x') with x' = dst_w - 1 - x when flip. dst == src reads the
+ * source pixel itself. Bit-identical to image_pipelines.materialize on the host.
+ * Refused before any launch: null pointers, n_images < 0 or above the maximum, an unknown layout, sizes < 1, dst larger than
+ * out, an offset or extent that leaves the source buffer. n_images == 0 is a no-op. */
+#define GGA_IMAGE_BATCH_MAX 64
+typedef struct {
+    int64_t src_offset;
+    int32_t src_h, src_w, dst_h, dst_w, flip, reserved;
+} gga_image_desc;
+int gga_image_batch(const uint8_t* src, int64_t src_bytes, const gga_image_desc* images_host, int n_images, const float* table,
+                    int reverse_channels, int out_h, int out_w, int layout, float* out, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Indoor mAP / mAR evaluation (mmdet3d/core/evaluation/indoor_eval.py).       */
 /* ------------------------------------------------------------------------- */

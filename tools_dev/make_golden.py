@@ -1982,6 +1982,129 @@ def golden_indoor_datasets(ref):
         f.write('\n')
 
 
+KITTI_MONO_CLASSES = ('Pedestrian', 'Cyclist', 'Car')
+
+
+def make_kitti_mono_case(seed=31):
+    """Seeded inputs of the KittiMonoDataset golden: four images with coco annotations - among them an ignored one, one
+    outside the image, a zero-area one, one narrower than a pixel, one of an unknown category and a crowd box; image 1 has no
+    annotation, image 2 only annotations that are skipped - and four frames of camera-box detections (12, 0, 5 that all miss
+    the image, 9). -> (image records, annotation lists, anno infos, detections as plain arrays)."""
+    rng = np.random.default_rng(seed)
+    p2 = synthetic.KITTI_CALIB['P2']
+    images, anns, infos, dets = [], [], [], []
+    ann_id = 0
+    for f in range(4):
+        h, w = int(rng.integers(370, 377)), int(rng.integers(1224, 1243))
+        images.append(dict(file_name=f'training/image_2/{f:06d}.jpg', id=f, width=w, height=h, cam_intrinsic=p2.tolist()))
+        records = []
+
+        def add(bbox, cat, **extra):
+            nonlocal ann_id
+            depth = float(rng.uniform(5, 50))
+            rec = dict(file_name=images[-1]['file_name'], image_id=f, area=float(bbox[2] * bbox[3]), category_name='x', category_id=cat,
+                       bbox=[float(v) for v in bbox], iscrowd=0,
+                       bbox_cam3d=[float(v) for v in np.concatenate([rng.uniform(-10, 10, 2), [depth], rng.uniform(0.5, 4, 3), rng.uniform(-3, 3, 1)])],
+                       velo_cam3d=-1, center2d=[float(rng.uniform(0, w)), float(rng.uniform(0, h)), depth], attribute_name=-1,
+                       attribute_id=-1, segmentation=[], id=ann_id)
+            rec.update(extra)
+            ann_id += 1
+            records.append(rec)
+        if f in (0, 3):
+            for _ in range(int(rng.integers(3, 6))):
+                add([rng.uniform(0, w - 120), rng.uniform(0, h - 90), rng.uniform(5, 110), rng.uniform(5, 80)], int(rng.integers(0, 3)))
+            add([-30.0, 20.0, 80.0, 50.0], 2)                      # crosses the left border: kept as it is
+        if f in (0, 2):
+            add([10.0, 10.0, 40.0, 40.0], 1, ignore=True)
+            add([w + 5.0, 10.0, 40.0, 40.0], 0)                    # outside the image
+            add([50.0, 50.0, 30.0, 0.0], 2)                        # zero area
+            add([60.0, 60.0, 0.5, 30.0], 2)                        # narrower than a pixel
+            add([70.0, 70.0, 30.0, 30.0], 7)                       # unknown category
+        if f == 0:
+            add([200.0, 100.0, 60.0, 40.0], 1, iscrowd=1)
+        anns.append(records)
+        infos.append(dict(image=dict(image_idx=10 + f, image_shape=np.array([h, w], np.int32)),
+                          calib={k: v.copy() for k, v in synthetic.KITTI_CALIB.items()}))
+        n = (12, 0, 5, 9)[f]
+        z = rng.uniform(6, 50, n)
+        u = rng.uniform(-200, w + 200, n) if f != 2 else -rng.uniform(400, 900, n)
+        v = rng.uniform(100, h - 20, n)
+        labels = rng.integers(0, 3, n)
+        size = np.array([(0.8, 1.73, 0.6), (1.76, 1.73, 0.6), (3.9, 1.56, 1.6)])[labels].reshape(n, 3)
+        boxes = np.concatenate([((u - p2[0, 2]) * z / p2[0, 0])[:, None], ((v - p2[1, 2]) * z / p2[1, 1] + size[:, 1] / 2)[:, None], z[:, None],
+                                size, rng.uniform(-4, 4, (n, 1))], 1).astype(np.float32)
+        dets.append(dict(boxes=boxes, scores=rng.uniform(0.01, 1, n).astype(np.float32), labels=labels.astype(np.int64)))
+    return images, anns, infos, dets
+
+
+def golden_kitti_mono(ref):
+    """The reference's ``KittiMonoDataset._parse_ann_info``, ``convert_valid_bboxes`` and ``bbox2result_kitti``
+    (mmdet3d/datasets/kitti_mono_dataset.py:57-145,271-384,497-569; real ``CameraInstance3DBoxes`` / ``Box3DMode`` /
+    ``points_cam2img``) on the seeded case above -> tests/golden/kitti_mono.npz: the inputs (the coco records as one JSON
+    string, calibration, detections) and what the methods returned, submission lines included. Stand-ins: the dataset object
+    carries only what the three methods read (``cat_ids``, ``cat2label``, ``bbox_code_size``, ``anno_infos``); mmcv's
+    ``track_iter_progress`` / ``mkdir_or_exist`` are the obvious one-liners."""
+    import json
+    import tempfile
+    import_reference_pipeline(ref)
+    su = ref['su']
+    cb = sys.modules['mmdet3d.core.bbox']
+    cam = load('mmdet3d.core.bbox.structures.cam_box3d', 'mmdet3d/core/bbox/structures/cam_box3d.py')
+    dep = load('mmdet3d.core.bbox.structures.depth_box3d', 'mmdet3d/core/bbox/structures/depth_box3d.py')
+    st = sys.modules['mmdet3d.core.bbox.structures']
+    st.base_box3d = sys.modules['mmdet3d.core.bbox.structures.base_box3d']
+    bm = load('mmdet3d.core.bbox.structures.box_3d_mode', 'mmdet3d/core/bbox/structures/box_3d_mode.py')
+    cb.CameraInstance3DBoxes, cb.DepthInstance3DBoxes, cb.Box3DMode, cb.points_cam2img = (cam.CameraInstance3DBoxes, dep.DepthInstance3DBoxes,
+                                                                                        bm.Box3DMode, su.points_cam2img)
+    mm = sys.modules['mmcv']
+    mm.track_iter_progress = lambda x: x
+    mm.mkdir_or_exist = lambda d: os.makedirs(d, exist_ok=True)
+    sys.modules['mmcv.utils'].print_log = lambda *a, **k: None
+    sys.modules['mmdet3d.datasets.builder'].DATASETS = _Reg()
+    _mod('mmdet3d.datasets.nuscenes_mono_dataset', NuScenesMonoDataset=object)
+    km = load('mmdet3d.datasets.kitti_mono_dataset', 'mmdet3d/datasets/kitti_mono_dataset.py')
+    images, anns, infos, dets = make_kitti_mono_case()
+
+    class FakeDataset(km.KittiMonoDataset):
+        def __init__(self):            # NuScenesMonoDataset.__init__ (third-party-heavy) is not run: only its fields
+            self.CLASSES = KITTI_MONO_CLASSES
+            self.cat_ids, self.cat2label = [0, 1, 2], {0: 0, 1: 1, 2: 2}
+            self.bbox_code_size, self.anno_infos = 7, infos
+
+    ds = FakeDataset()
+    out = {'inputs.coco': np.array(json.dumps(dict(images=images, annotations=[a for recs in anns for a in recs],
+                                                   categories=[dict(id=i, name=n) for i, n in enumerate(KITTI_MONO_CLASSES)])))}
+    for f, (img, recs) in enumerate(zip(images, anns)):
+        a = ds._parse_ann_info(dict(img, filename=img['file_name']), recs)
+        for k in ('bboxes', 'labels', 'gt_labels_3d', 'centers2d', 'depths', 'bboxes_ignore'):
+            out[f'parse.{f}.{k}'] = np.asarray(a[k])
+        out[f'parse.{f}.gt_bboxes_3d'] = a['gt_bboxes_3d'].tensor.numpy()
+        out[f'parse.{f}.seg_map'] = np.array(a['seg_map'])
+        out[f'parse.{f}.n_masks'] = np.int64(len(a['masks']))
+    for k in ('P2', 'R0_rect', 'Tr_velo_to_cam'):
+        out[f'inputs.calib.{k}'] = synthetic.KITTI_CALIB[k]
+    results = []
+    for f, d in enumerate(dets):
+        out[f'inputs.{f}.image_idx'], out[f'inputs.{f}.image_shape'] = np.int64(infos[f]['image']['image_idx']), infos[f]['image']['image_shape']
+        for k, v in d.items():
+            out[f'inputs.{f}.{k}'] = v
+        results.append(dict(boxes_3d=cam.CameraInstance3DBoxes(torch.from_numpy(d['boxes'].copy())), scores_3d=torch.from_numpy(d['scores'].copy()),
+                            labels_3d=torch.from_numpy(d['labels'].copy())))
+        conv = ds.convert_valid_bboxes(results[-1], infos[f])
+        out[f'convert.{f}.keys'] = np.array(sorted(conv))
+        for k, v in conv.items():
+            out[f'convert.{f}.{k}'] = np.asarray(v)
+    with tempfile.TemporaryDirectory() as tmp:
+        annos = ds.bbox2result_kitti(results, KITTI_MONO_CLASSES, pklfile_prefix=None, submission_prefix=os.path.join(tmp, 'sub'))
+        for f, anno in enumerate(annos):
+            for k, v in anno.items():
+                out[f'anno.{f}.{k}'] = np.asarray(v)
+            out[f'submission.{f}'] = np.array(open(os.path.join(tmp, 'sub', f'{10 + f:06d}.txt')).read())
+    np.savez_compressed(os.path.join(OUT, 'kitti_mono.npz'), **out)
+    print('  kitti mono:', len(out), 'arrays; valid detections per frame', [len(a['score']) for a in annos],
+          '; parsed boxes per image', [len(out[f'parse.{f}.bboxes']) for f in range(4)])
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -2008,6 +2131,7 @@ def main():
     golden_dynamic_voxel(ref)
     golden_tta(ref)
     golden_indoor_datasets(ref)
+    golden_kitti_mono(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
