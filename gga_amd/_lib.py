@@ -188,6 +188,8 @@ SIGNATURES = {
     'gga_region_grow': (i32, [vp, i64, i32, vp, vp, vp, i32, C.c_double, i32, vp, vp, sz, vp]),
     'gga_points_in_convex_polyhedra': (i32, [vp, i64, i32, vp, vp, i32, i32, vp, vp]),
     'gga_plane_inliers': (i32, [vp, i64, i32, vp, i32, C.c_double, vp, vp, vp]),
+    'gga_frame_point_tests_workspace_bytes': (sz, [i64]),
+    'gga_frame_point_tests': (i32, [vp, i64, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_image_box_match': (i32, [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]),
     'gga_kitti_eval_overlaps': (i32, [vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp]),
     'gga_kitti_eval_stats_workspace_bytes': (sz, [i32, i32, i32]),

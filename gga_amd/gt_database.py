@@ -10,8 +10,9 @@ Per frame: every annotated object that passed the offline label generator
 The two point tests run on the device primitives of ``gga_amd.label_gen``
 (``gga_points_in_convex_polyhedra``: float64, the reference's operation order):
 frustum membership for the saved points, box membership for ``num_points_in_gt``
-(``box_np_ops.points_in_rbbox``, core/bbox/box_np_ops.py:343-370). All boxes of a frame go through
-ONE launch each. File handling and the info dicts are host code, as in the reference.
+(``box_np_ops.points_in_rbbox``, core/bbox/box_np_ops.py:343-370). A frame's boxes and frusta go through ONE
+``label_gen.frame_point_tests`` call on the float32 cloud as loaded (``GGA_PREP_ONE_PASS=0``: one float64 launch for the
+boxes and one for the frusta). File handling and the info dicts are host code, as in the reference.
 """
 import os
 import pickle
@@ -24,12 +25,17 @@ DB_KEYS = ('GGA_gt_box', 'GGA_box_img', 'GGA_mask_depth', 'GGA_mask2d', 'GGA_mas
            'GGA_bdry_mask', 'GGA_in_box_points', 'GGA_init_pseudo_label', 'GGA_num_points_in_box2d', 'GGA_lidar2img')
 
 
+def rbbox_surfaces(rbbox, z_axis=2, origin=(0.5, 0.5, 0)):
+    """The six faces [M, 6, 4, 3] of rotated boxes, as ``points_in_rbbox`` tests them."""
+    corners = LG.center_to_corner_box3d(rbbox[:, :3], rbbox[:, 3:6], rbbox[:, 6], origin=origin, axis=z_axis)
+    return LG.corner_to_surfaces_3d(corners)
+
+
 def points_in_rbbox(points, rbbox, z_axis=2, origin=(0.5, 0.5, 0)):
     """box_np_ops.points_in_rbbox: [N, M] bool, point n inside rotated box m."""
     if len(rbbox) == 0:
         return np.zeros((points.shape[0], 0), dtype=bool)
-    corners = LG.center_to_corner_box3d(rbbox[:, :3], rbbox[:, 3:6], rbbox[:, 6], origin=origin, axis=z_axis)
-    return LG.points_in_convex_polygon_3d(points[:, :3], LG.corner_to_surfaces_3d(corners))
+    return LG.points_in_convex_polygon_3d(points[:, :3], rbbox_surfaces(rbbox, z_axis, origin))
 
 
 def frame_entries(example, image_idx, info_prefix, group_counter, used_classes=None):
@@ -50,13 +56,17 @@ def frame_entries(example, image_idx, info_prefix, group_counter, used_classes=N
     in_box = [item for item, keep in zip(annos['GGA_in_box_points'], m) if keep]
     num_obj = gt_boxes_3d.shape[0]
     assert f['GGA_boxes_img'].shape[0] == num_obj and f['bboxes'].shape[0] == num_obj, 'The boxes are mismatched'
-    gt_point_indices = points_in_rbbox(points, gt_boxes_3d)
     point_indices = np.zeros((points.shape[0], num_obj), dtype=bool)
     live = [i for i, sign in enumerate(f['GGA_mask2d']) if sign]
-    if live:       # the frusta of all live boxes in one launch
-        surf = np.concatenate([LG.frustum_surfaces(example['rect'], example['Trv2c'], example['P2'], f['GGA_boxes_img'][i])
-                               for i in live], 0)
-        point_indices[:, live] = LG.points_in_convex_polygon_3d(points[:, :3], surf)
+    surf = [LG.frustum_surfaces(example['rect'], example['Trv2c'], example['P2'], f['GGA_boxes_img'][i]) for i in live]
+    if LG.one_pass() and num_obj and points.dtype == np.float32:      # boxes and live frusta in one pass over the cloud
+        member = LG.frame_point_tests(points, [rbbox_surfaces(gt_boxes_3d)] + ([np.concatenate(surf, 0)] if live else []))[0]
+        gt_point_indices = member[:, :num_obj]
+        point_indices[:, live] = member[:, num_obj:]
+    else:
+        gt_point_indices = points_in_rbbox(points, gt_boxes_3d)
+        if live:       # the frusta of all live boxes in one launch
+            point_indices[:, live] = LG.points_in_convex_polygon_3d(points[:, :3], np.concatenate(surf, 0))
     out, group_dict = [], {}
     for i in range(num_obj):
         filename = f'{image_idx}_{names[i]}_{i}.bin'
@@ -83,12 +93,31 @@ def frame_entries(example, image_idx, info_prefix, group_counter, used_classes=N
     return out, group_counter
 
 
+def build_database_dataset(data_path, info_path):
+    """The dataset ``create_groundtruth_database('KittiDataset_GGA', data_path, info_prefix, info_path)`` builds for itself
+    (its ``dataset_cfg``, create_gt_database_gga.py:146-171): the train infos, ``training/velodyne`` - the full clouds, not
+    the reduced ones -, four point features, boxes and labels loaded, DontCare entries dropped
+    (``remove_dontcare_GGA``)."""
+    from .datasets import KittiDataset_GGA_train, LoadAnnotations3D
+    from .pipelines import LoadPointsFromFile
+    return KittiDataset_GGA_train(data_path, info_path, 'training', test_mode=False,
+                                  modality=dict(use_lidar=True, use_depth=False, use_lidar_intensity=True, use_camera=False),
+                                  pipeline=[LoadPointsFromFile(coord_type='LIDAR', load_dim=4, use_dim=4),
+                                            LoadAnnotations3D(with_bbox_3d=True, with_label_3d=True)])
+
+
 def create_groundtruth_database(dataset, data_path, info_prefix, used_classes=None, database_save_path=None,
-                                db_info_save_path=None, logger=print):
-    """``create_groundtruth_database('KittiDataset_GGA', ...)`` for an already built dataset whose pipeline
-    is ``[LoadPointsFromFile(load_dim=4, use_dim=4), LoadAnnotations3D(with_bbox_3d, with_label_3d)]``
+                                db_info_save_path=None, logger=print, info_path=None):
+    """``create_groundtruth_database('KittiDataset_GGA', data_path, info_prefix, info_path=...)``: ``dataset`` is that name
+    (the dataset is then built from ``info_path``, default ``<data_path>/<prefix>_infos_train_GGA.pkl``:
+    ``build_database_dataset``) or an already built dataset whose pipeline is
+    ``[LoadPointsFromFile(load_dim=4, use_dim=4), LoadAnnotations3D(with_bbox_3d, with_label_3d)]``
     (create_gt_database_gga.py:148-171). Writes ``<prefix>_gt_database_GGA/*.bin`` and
     ``<prefix>_dbinfos_train_GGA.pkl``; returns the info dict."""
+    if isinstance(dataset, str):
+        if dataset != 'KittiDataset_GGA':
+            raise NotImplementedError(f'create_groundtruth_database: dataset {dataset!r} (only KittiDataset_GGA)')
+        dataset = build_database_dataset(data_path, info_path or os.path.join(data_path, f'{info_prefix}_infos_train_GGA.pkl'))
     database_save_path = database_save_path or os.path.join(data_path, f'{info_prefix}_gt_database_GGA')
     db_info_save_path = db_info_save_path or os.path.join(data_path, f'{info_prefix}_dbinfos_train_GGA.pkl')
     os.makedirs(database_save_path, exist_ok=True)

@@ -12,6 +12,9 @@ float64 in the reference's operation order, so the masks are bit-identical to nu
   8-corner frustum and its surface equations are a handful of 4x4 / 3x3 numpy operations taken in
   the reference's order (box_np_ops.py:13-33, 256-276, 526-552, 584-638); the point test runs on
   the device.
+* ``frame_point_tests(points_f32, surfaces, reduce_poly)`` - every point-in-polyhedron question of a frame (image frustum,
+  boxes, object frusta, the reduced cloud) in one pass over the float32 cloud as read (``gga_frame_point_tests``), bit for bit
+  what ``points_in_convex_polygon_3d`` answers one call at a time; ``one_pass()`` is the ``GGA_PREP_ONE_PASS`` switch.
 * ``calculate_ground(point_cloud, thresh_ransac, back_cut, back_cut_z)`` — utils_gga.py:103-133:
   the candidate triples are drawn on the host with ``np.random.choice`` in the reference's order
   (so equal seeds give equal planes), all candidates of a round are scored in one launch.
@@ -24,6 +27,7 @@ float64 in the reference's operation order, so the masks are bit-identical to nu
   ``array_converter``); ``_rotate_bev`` / ``_rotate3d`` reproduce that.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -123,6 +127,61 @@ def points_in_convex_polygon_3d(points, polygon_surfaces):
                                                         normal.shape[1], F._p(out), F._stream()),
               'gga_points_in_convex_polyhedra')
     return out.cpu().numpy().astype(bool)
+
+
+def one_pass():
+    """The data preparation's switch: ``GGA_PREP_ONE_PASS=0`` keeps one launch (with its own upload and download of the
+    cloud) per question; anything else asks all of a frame's point questions through ``frame_point_tests``."""
+    return os.environ.get('GGA_PREP_ONE_PASS', '1') != '0'
+
+
+def frame_point_tests(points_f32, surfaces, reduce_poly=-1):
+    """Every point-in-polyhedron question of a frame in one pass (``gga_frame_point_tests``): ``points_f32`` [N, >=3]
+    float32 as read from the velodyne file, ``surfaces`` [P, S, >=3, 3] (``corner_to_surfaces_3d``; boxes and frusta alike)
+    or a list of such arrays, whose face equations are then taken group by group in each group's own dtype (as the per-call
+    form takes them) and the polyhedra numbered through the list.
+    -> (member bool [N, P], counts int32 [P], counts_reduced int32 [P] = points inside p and ``reduce_poly``,
+    reduced float32 [n_reduced, stride] = the rows inside ``reduce_poly`` in input order, n_reduced).
+    ``reduce_poly=-1``: no reduced cloud (an empty array), ``counts_reduced == counts``. The cloud and the face table go
+    up in one copy, the membership words and counts come back in one copy, then the ``n_reduced`` reduced rows alone."""
+    pts = np.ascontiguousarray(points_f32, np.float32)
+    n, stride = pts.shape
+    groups = surfaces if isinstance(surfaces, (list, tuple)) else [surfaces]
+    equ = [surface_equ_3d(np.asarray(g)[:, :, :3, :]) for g in groups]
+    normal = np.ascontiguousarray(np.concatenate([e[0].astype(np.float64) for e in equ], 0))
+    d = np.ascontiguousarray(np.concatenate([e[1].astype(np.float64) for e in equ], 0))
+    P = normal.shape[0]
+    words = (P + 31) // 32
+    if n == 0:
+        zero = np.zeros(P, np.int32)
+        return np.zeros((0, P), bool), zero, zero.copy(), np.zeros((0, stride), np.float32), 0
+    # upload: [points | pad to 8 B | normal | d] as one buffer
+    off_n = (pts.nbytes + 7) // 8 * 8
+    host = np.empty(off_n + normal.nbytes + d.nbytes, np.uint8)
+    host[:pts.nbytes] = pts.reshape(-1).view(np.uint8)
+    host[off_n:off_n + normal.nbytes] = normal.reshape(-1).view(np.uint8)
+    host[off_n + normal.nbytes:] = d.reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(host).to(DEVICE)
+    F._need_cuda(dev)
+    base = dev.data_ptr()
+    # results: [counts P | counts_reduced P | n_reduced 1 | member words * N] int32
+    head = 2 * P + 1
+    out = torch.empty(head + words * n, dtype=torch.int32, device=DEVICE)
+    reduced = torch.empty((n, stride), dtype=torch.float32, device=DEVICE) if reduce_poly >= 0 else None
+    L = _lib.lib()
+    ws = F._workspace('frame_point_tests', L.gga_frame_point_tests_workspace_bytes(n), torch.device(DEVICE))
+    o = out.data_ptr()
+    with torch.cuda.device(DEVICE):
+        check(L.gga_frame_point_tests(C.c_void_p(base), n, stride, C.c_void_p(base + off_n), C.c_void_p(base + off_n + normal.nbytes),
+                                      P, normal.shape[1], int(reduce_poly), C.c_void_p(o + 4 * head), C.c_void_p(o),
+                                      C.c_void_p(o + 4 * P), F._p(reduced), C.c_void_p(o + 8 * P), F._p(ws), ws.numel(),
+                                      F._stream()), 'gga_frame_point_tests')
+    res = out.cpu().numpy()
+    counts, counts_reduced, n_reduced = res[:P].copy(), res[P:2 * P].copy(), int(res[2 * P])
+    w = res[head:].view(np.uint32).reshape(words, n)
+    member = ((w[np.arange(P) // 32] >> (np.arange(P, dtype=np.uint32) % 32)[:, None]) & 1).astype(bool).T
+    rows = reduced[:n_reduced].cpu().numpy() if reduce_poly >= 0 else np.zeros((0, stride), np.float32)
+    return member, counts, counts_reduced, rows, n_reduced
 
 
 def frustum_surfaces(rect, Trv2c, P2, bbox_shape):
@@ -366,7 +425,7 @@ def box2d_labels(annos, P2, image_shape):
     return (np.concatenate(box2d), np.array(depth_mask), np.array(mask2d), np.array(mask_boundary), np.stack(bdry_masks))
 
 
-def calculate_rga(points_v, calib, annos, image_shape):
+def calculate_rga(points_v, calib, annos, image_shape, frusta=None):
     """The per-frame GGA label generation of ``_calculate_rga`` (kitti_converter_gga.py:214-517) as a
     function of the loaded frame: ``points_v`` [N, >=3] f32 velodyne points, ``calib`` with 4x4
     ``R0_rect`` / ``Tr_velo_to_cam`` / ``P2``, KITTI ``annos`` (modified in place and returned),
@@ -393,7 +452,8 @@ def calculate_rga(points_v, calib, annos, image_shape):
 
     # objects front to back (median depth of the points inside their frustum)
     boxes_img = gt_boxes_img.copy()
-    frusta = [points_in_frustm_indices(points_lidar, rect, Trv2c, P2, b).squeeze() for b in boxes_img]
+    if frusta is None:
+        frusta = [points_in_frustm_indices(points_lidar, rect, Trv2c, P2, b).squeeze() for b in boxes_img]
     isvalid, medis = [], []
     for index, bpi in enumerate(frusta):
         if (bpi.sum() == 0) or (num_points_in_gt[index] == 0):

@@ -1049,3 +1049,87 @@ def write_kitti_mono_tree(root, n_frames, img_hw=(96, 320), seed=4300, n_obj_ran
         pickle.dump(tests, fh)
     json.dump(stamp, open(stamp_path, 'w'))
     return info_path, test_path
+
+
+# ---- raw KITTI tree (step 1 of the recipe, tools/create_data_gga.py kitti): what an unpacked KITTI download looks like
+def _project_box_2d(loc, dims, rot, P2, hw):
+    """Image box (x1, y1, x2, y2) of a camera-frame box (bottom centre ``loc``, ``dims`` (l, h, w)), clipped to the image."""
+    c, s = np.cos(rot), np.sin(rot)
+    k = np.array([[a, b, d] for a in (-0.5, 0.5) for b in (-1.0, 0.0) for d in (-0.5, 0.5)]) * np.asarray(dims)
+    pts = np.stack([k[:, 0] * c + k[:, 2] * s, k[:, 1], -k[:, 0] * s + k[:, 2] * c], 1) + np.asarray(loc)
+    q = np.concatenate([pts, np.ones((8, 1))], 1) @ P2.T
+    q = q[q[:, 2] > 0.1]
+    if len(q) == 0:
+        return [0.0, 0.0, 1.0, 1.0]
+    u, v = q[:, 0] / q[:, 2], q[:, 1] / q[:, 2]
+    return [float(np.clip(u.min(), 0, hw[1] - 1)), float(np.clip(v.min(), 0, hw[0] - 1)),
+            float(np.clip(u.max(), 0, hw[1] - 1)), float(np.clip(v.max(), 0, hw[0] - 1))]
+
+
+def write_kitti_raw_tree(root, n_train, n_val, n_test, seed=7100, n_points=3000, with_plane=False):
+    """Writes a raw KITTI tree of ``n_train + n_val + n_test`` synthetic frames under ``root``:
+
+        ImageSets/{train,val,test}.txt                        frame ids, train and val interleaved over training/ as KITTI's are
+        training/{calib,image_2,label_2,velodyne}/%06d.*      testing/{calib,image_2,velodyne}/%06d.*
+
+    A frame is ``make_rga_scene(seed + id)`` scaled to about ``n_points`` points: a ground plane, clutter, objects whose
+    clusters grow. Labels are KITTI text to 2 decimals with one DontCare line per frame; training frame 1 has no object lines
+    but its DontCare. Calib files carry all seven rows; images are PNGs of the frame's ``image_shape`` in one grey level
+    (about a kilobyte each). ``with_plane``: also ``training/planes/%06d.txt``, the ground plane in KITTI's four-line form.
+    Test frames are numbered from 0 again, like KITTI's.
+    -> {'train': ids, 'val': ids, 'test': ids}. Deterministic in its arguments."""
+    import os
+    from PIL import Image
+    n_trainval = n_train + n_val
+    order = [i for i in range(n_trainval) if i % 3 == 1] + [i for i in range(n_trainval) if i % 3 != 1]
+    val_ids = sorted(order[:n_val])
+    train_ids = [i for i in range(n_trainval) if i not in val_ids]
+    ids = dict(train=train_ids, val=val_ids, test=list(range(n_test)))
+    os.makedirs(os.path.join(root, 'ImageSets'), exist_ok=True)
+    for split, lst in ids.items():
+        with open(os.path.join(root, 'ImageSets', f'{split}.txt'), 'w') as f:
+            f.write('\n'.join(f'{i:06d}' for i in lst))
+    row = lambda name, m: name + ': ' + ' '.join('%.12e' % v for v in np.asarray(m).reshape(-1))
+
+    def frame(split, i, scene_seed, with_labels):
+        for sub in ('calib', 'image_2', 'velodyne') + (('label_2', ) if with_labels else ()):
+            os.makedirs(os.path.join(root, split, sub), exist_ok=True)
+        points_v, calib, annos, hw = make_rga_scene(scene_seed, n_ground=int(n_points * 0.55), n_clutter=int(n_points * 0.25))
+        hw = (hw[0] - scene_seed % 3, hw[1] - scene_seed % 5)          # KITTI's images differ by a few pixels
+        points_v.tofile(os.path.join(root, split, 'velodyne', f'{i:06d}.bin'))
+        Image.new('L', (hw[1], hw[0]), 96).save(os.path.join(root, split, 'image_2', f'{i:06d}.png'))
+        P2 = calib['P2'][:3]
+        P0, P1, P3 = P2.copy(), P2.copy(), P2.copy()
+        P0[:, 3] = 0.0
+        P1[0, 3], P3[0, 3] = -386.1448, -339.5242
+        imu = np.array([[9.999976e-01, 7.553071e-04, -2.035826e-03, -8.086759e-01], [-7.854027e-04, 9.998898e-01, -1.482298e-02, 3.195559e-01],
+                        [2.024406e-03, 1.482454e-02, 9.998881e-01, -7.997231e-01]])
+        with open(os.path.join(root, split, 'calib', f'{i:06d}.txt'), 'w') as f:
+            f.write('\n'.join([row('P0', P0), row('P1', P1), row('P2', P2), row('P3', P3), row('R0_rect', calib['R0_rect'][:3, :3]),
+                               row('Tr_velo_to_cam', calib['Tr_velo_to_cam'][:3]), row('Tr_imu_to_velo', imu)]) + '\n')
+        if not with_labels:
+            return
+        if with_plane:
+            os.makedirs(os.path.join(root, split, 'planes'), exist_ok=True)
+            with open(os.path.join(root, split, 'planes', f'{i:06d}.txt'), 'w') as f:
+                f.write('# Plane\nWidth 4\nHeight 1\n%.6e %.6e %.6e %.6e\n' % (-0.002 - 1e-4 * i, -0.999998, 0.0011, 1.72 + 0.01 * i))
+        lines = []
+        n_obj = len([n for n in annos['name'] if n != 'DontCare'])
+        if not (split == 'training' and i == 1):
+            for j in range(n_obj):
+                l, h, w = annos['dimensions'][j]
+                loc, rot = annos['location'][j], float(annos['rotation_y'][j])
+                rot = (rot + np.pi) % (2 * np.pi) - np.pi
+                box = _project_box_2d(loc, (l, h, w), rot, calib['P2'], hw)
+                alpha = rot - np.arctan2(loc[0], loc[2])
+                lines.append('%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f' % (
+                    annos['name'][j], 0.0, j % 3, alpha, box[0], box[1], box[2], box[3], h, w, l, loc[0], loc[1], loc[2], rot))
+        lines.append('DontCare -1 -1 -10 %.2f %.2f %.2f %.2f -1 -1 -1 -1000 -1000 -1000 -10' % (503.89, 169.71, 590.61, 190.13))
+        with open(os.path.join(root, split, 'label_2', f'{i:06d}.txt'), 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+    for i in train_ids + val_ids:
+        frame('training', i, seed + i, True)
+    for i in ids['test']:
+        frame('testing', i, seed + 100000 + i, False)
+    return ids

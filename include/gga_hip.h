@@ -1142,6 +1142,32 @@ int gga_region_grow(const double* pc, int64_t n_points, int dim, const uint8_t* 
 int gga_points_in_convex_polyhedra(const double* points, int64_t n_points, int point_stride, const double* normal_vec,
                                    const double* d, int n_polyhedra, int n_surfaces, uint8_t* out, void* stream);
 
+/* Every point-in-polyhedron question of one frame in one pass over its raw cloud (the data preparation's per-frame point
+ * stage: image frustum, ground-truth boxes, object frusta, reduced cloud).
+ * points [n_points, point_stride] f32 as the velodyne file holds them (columns 0..2 = x, y, z; widened to f64 on the device,
+ * which is exact), normal_vec [n_polyhedra, n_surfaces, 3] f64 and d [n_polyhedra, n_surfaces] f64 (surface_equ_3d).
+ * Inside is gga_points_in_convex_polyhedra's test in its arithmetic, so every bit equals what that entry returns for the
+ * same points given as f64.
+ *   member         [ceil(n_polyhedra / 32), n_points] u32: bit p % 32 of word [p / 32, i] = point i inside polyhedron p;
+ *                  the bits above the last polyhedron are zero
+ *   counts         [n_polyhedra] i32: points inside p
+ *   counts_reduced [n_polyhedra] i32: points inside p and inside reduce_poly (= counts when reduce_poly is -1)
+ *   reduced        [n_points, point_stride] f32: the rows inside reduce_poly, whole and in input order (a stable compaction;
+ *                  rows behind the last one are not written); not touched and may be null when reduce_poly is -1
+ *   n_reduced      i32: the number of those rows (0 when reduce_poly is -1)
+ * n_points == 0 returns GGA_OK and writes nothing. GGA_ERR_INVALID_ARG before any HIP call for n_points outside 0..2^21,
+ * point_stride outside 3..64, n_polyhedra outside 1..256, n_surfaces < 1 or n_polyhedra * n_surfaces > 1920 (the table is
+ * kept in LDS), reduce_poly outside -1..n_polyhedra-1, a null pointer while n_points > 0; GGA_ERR_WORKSPACE for a workspace
+ * below gga_frame_point_tests_workspace_bytes(n_points) (0 for a refused n_points). Rows are moved with 16-byte accesses
+ * when point_stride is 4 and points / reduced lie on 16-byte addresses. Launches: one memset when counts, counts_reduced
+ * and n_reduced lie one behind the other (else three), the test kernel, and with a reduce_poly one single-workgroup scan
+ * and the scatter. */
+size_t gga_frame_point_tests_workspace_bytes(int64_t n_points);
+int gga_frame_point_tests(const float* points, int64_t n_points, int point_stride, const double* normal_vec, const double* d,
+                          int n_polyhedra, int n_surfaces, int reduce_poly, uint32_t* member, int32_t* counts,
+                          int32_t* counts_reduced, float* reduced, int32_t* n_reduced, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* RANSAC scoring of calculate_ground (utils_gga.py:121-125): for every candidate plane a.p = 1,
  * counts[c] = #{ i : |p_i . plane_c - 1| / ||plane_c|| < threshold }; masks (optional)
  * [n_planes, n_points] u8 the inlier masks. */

@@ -1,0 +1,143 @@
+"""``gga_frame_point_tests`` (gga_amd/csrc/frame_points.hip) and its wrapper ``label_gen.frame_point_tests`` on the device,
+bit for bit against the numpy statement of the face test (tests/_frame_points_ref.py) and against
+``gga_points_in_convex_polyhedra`` given the same points as float64."""
+import numpy as np
+import pytest
+import torch
+
+from _frame_points_ref import face_test
+from gga_amd import _lib
+from gga_amd import functional as F
+from gga_amd import label_gen as LG
+from gga_amd.gt_database import rbbox_surfaces
+
+pytestmark = pytest.mark.gpu
+
+P_MAX = 70
+
+
+def _points(n, stride, seed=5):
+    rng = np.random.default_rng(seed)
+    cols = [rng.uniform(0, 40, n), rng.uniform(-20, 20, n), rng.uniform(-2, 2, n)] + [rng.uniform(0, 1, n)] * (stride - 3)
+    return np.stack(cols, 1).astype(np.float32)
+
+
+@pytest.fixture(scope='module')
+def boxes():
+    """P_MAX rotated boxes over the points' range; the first and the last are large, so that either as ``reduce_poly`` keeps
+    a good share of the points."""
+    rng = np.random.default_rng(11)
+    b = np.stack([rng.uniform(0, 40, P_MAX), rng.uniform(-20, 20, P_MAX), rng.uniform(-3, 0, P_MAX), rng.uniform(2, 14, P_MAX),
+                  rng.uniform(2, 14, P_MAX), rng.uniform(1, 5, P_MAX), rng.uniform(-np.pi, np.pi, P_MAX)], 1)
+    b[0] = [20, 0, -3, 30, 24, 6, 0.3]
+    b[-1] = [12, -4, -3, 22, 18, 6, -1.1]
+    return b
+
+
+def _check(pts, surf, reduce_poly, got, want_member):
+    member, counts, counts_reduced, reduced, n_reduced = got
+    n, P = len(pts), surf.shape[0]
+    assert member.dtype == bool and member.shape == (n, P) and np.array_equal(member, want_member)
+    assert counts.dtype == np.int32 and counts.tolist() == want_member.sum(0).tolist()
+    keep = want_member[:, reduce_poly] if reduce_poly >= 0 else np.ones(n, bool)
+    assert counts_reduced.dtype == np.int32 and counts_reduced.tolist() == (want_member & keep[:, None]).sum(0).tolist()
+    want_rows = pts[keep] if reduce_poly >= 0 else pts[:0]
+    assert n_reduced == len(want_rows) and reduced.dtype == np.float32 and reduced.shape == want_rows.shape
+    assert reduced.tobytes() == want_rows.tobytes()
+
+
+@pytest.mark.parametrize('n', [0, 1, 63, 64, 65, 255, 256, 257, 4099])
+def test_frame_point_tests_matches_numpy_and_the_per_call_kernel(n, boxes):
+    kept = 0
+    for stride in (3, 4, 5):
+        pts = _points(n, stride)
+        for P in (1, 31, 32, 33, 70):
+            surf = rbbox_surfaces(np.concatenate([boxes[:P - 1], boxes[-1:]]))
+            normal, d = LG.surface_equ_3d(surf[:, :, :3, :])
+            want = face_test(pts, normal, d)
+            assert np.array_equal(LG.points_in_convex_polygon_3d(pts[:, :3], surf), want)        # the per-call kernel, float64 points
+            for reduce_poly in (-1, 0, P - 1):
+                got = LG.frame_point_tests(pts, surf, reduce_poly)
+                _check(pts, surf, reduce_poly, got, want)
+                kept += got[4]
+    assert n < 63 or kept > n              # the reduced clouds were not all empty
+
+
+def test_product_shape_all_none_and_groups(boxes):
+    """A KITTI-sized cloud with 33 polyhedra; one polyhedron that holds every point and one that holds none as
+    ``reduce_poly``; groups of surfaces of different dtypes keep their own face equations."""
+    pts = _points(120000, 4, seed=6)
+    every = np.array([[20, 0, -50, 100, 100, 100, 0.0]])
+    none = np.array([[500, 500, 0, 1, 1, 1, 0.0]])
+    groups = [rbbox_surfaces(every), rbbox_surfaces(boxes[:30].astype(np.float32)), rbbox_surfaces(none), rbbox_surfaces(boxes[30:31])]
+    assert groups[1].dtype == np.float32 and groups[0].dtype == np.float64
+    equ = [LG.surface_equ_3d(g[:, :, :3, :]) for g in groups]
+    normal = np.concatenate([e[0].astype(np.float64) for e in equ])
+    d = np.concatenate([e[1].astype(np.float64) for e in equ])
+    want = face_test(pts, normal, d)
+    per_call = np.concatenate([LG.points_in_convex_polygon_3d(pts[:, :3], g) for g in groups], 1)
+    assert np.array_equal(per_call, want) and want[:, 0].all() and not want[:, 31].any() and 0 < want[:, 1:31].sum()
+    for reduce_poly, n_want in ((0, len(pts)), (31, 0), (32, int(want[:, 32].sum()))):
+        got = LG.frame_point_tests(pts, groups, reduce_poly)
+        assert got[4] == n_want
+        _check(pts, normal, reduce_poly, got, want)
+
+
+def test_points_on_a_face_are_outside():
+    """An axis-aligned box with integer corners, x in [2, 6], y in [1, 3], z in [0, 2]: its face equations and these points
+    are small integers, so the float64 sum is exactly 0 on a face - and ``s == 0`` is outside."""
+    surf = rbbox_surfaces(np.array([[4.0, 2.0, 0.0, 4.0, 2.0, 2.0, 0.0]]))
+    normal, d = LG.surface_equ_3d(surf[:, :, :3, :])
+    assert np.array_equal(normal, np.round(normal)) and np.array_equal(d, np.round(d))
+    pts = np.array([[3, 2, 1, 7], [2, 2, 1, 7], [6, 2, 1, 7], [4, 1, 1, 7], [4, 3, 1, 7], [4, 2, 0, 7], [4, 2, 2, 7], [6, 3, 2, 7],
+                    [5, 2, 1, 7], [1, 2, 1, 7]], np.float32)
+    want = np.array([True] + [False] * 7 + [True, False])[:, None]
+    assert np.array_equal(face_test(pts, normal, d), want)
+    for stride in (3, 4):
+        got = LG.frame_point_tests(pts[:, :stride], surf, 0)
+        _check(pts[:, :stride], surf, 0, got, want)
+        assert got[1].tolist() == [2] and got[4] == 2
+
+
+def test_runs_on_the_callers_stream(boxes):
+    pts = _points(4099, 4, seed=8)
+    surf = rbbox_surfaces(boxes[:33])
+    want = LG.frame_point_tests(pts, surf, 0)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert F._stream().value == side.cuda_stream
+        got = LG.frame_point_tests(pts, surf, 0)
+    for a, b in zip(got[:4], want[:4]):
+        assert np.array_equal(a, b)
+    assert got[4] == want[4] > 0
+
+
+def test_raw_entry_unused_bits_and_rows_behind_the_last(boxes):
+    """The entry point itself: the membership words' bits above the last polyhedron are zero whatever the buffer held, the
+    rows of ``reduced`` behind ``n_reduced`` are not written, and the wrapper hands back exactly ``n_reduced`` rows."""
+    n, P, stride = 1000, 33, 5
+    pts = _points(n, stride, seed=9)
+    surf = rbbox_surfaces(boxes[:P])
+    normal, d = LG.surface_equ_3d(surf[:, :, :3, :])
+    want = face_test(pts, normal, d)
+    dev = torch.device('cuda:0')
+    t_pts, t_n, t_d = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (pts, normal, d))
+    member = torch.full((2, n), -1, dtype=torch.int32, device=dev)
+    counts = torch.full((P, ), 77, dtype=torch.int32, device=dev)
+    counts_reduced = torch.full((P, ), 77, dtype=torch.int32, device=dev)
+    reduced = torch.full((n, stride), -5.0, dtype=torch.float32, device=dev)
+    n_reduced = torch.full((1, ), 77, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = torch.empty(L.gga_frame_point_tests_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    _lib.check(L.gga_frame_point_tests(F._p(t_pts), n, stride, F._p(t_n), F._p(t_d), P, 6, 0, F._p(member), F._p(counts),
+                                       F._p(counts_reduced), F._p(reduced), F._p(n_reduced), F._p(ws), ws.numel(), F._stream()),
+               'gga_frame_point_tests')
+    words = member.cpu().numpy().view(np.uint32)
+    assert (words[1] >> 1 == 0).all()                                   # polyhedron 32 is bit 0 of word 1; the rest is unused
+    bits = np.stack([(words[p // 32] >> (p % 32)) & 1 for p in range(P)], 1).astype(bool)
+    assert np.array_equal(bits, want)
+    k = int(n_reduced.item())
+    assert 0 < k == int(want[:, 0].sum()) < n and counts.cpu().tolist() == want.sum(0).tolist()
+    rows = reduced.cpu().numpy()
+    assert rows[:k].tobytes() == pts[want[:, 0]].tobytes() and (rows[k:] == -5.0).all()
+    assert LG.frame_point_tests(pts, surf, 0)[3].shape == (k, stride)

@@ -2105,6 +2105,56 @@ def golden_kitti_mono(ref):
           '; parsed boxes per image', [len(out[f'parse.{f}.bboxes']) for f in range(4)])
 
 
+KITTI_RAW_TREE = dict(n_train=3, n_val=2, n_test=2, seed=7100, n_points=400, with_plane=True)
+
+
+def golden_kitti_raw(ref):
+    """Raw-file parsing (tools/data_converter/kitti_data_utils.py: get_kitti_image_info, get_label_anno,
+    add_difficulty_to_annos) run by the reference's own functions on ``synthetic.write_kitti_raw_tree(**KITTI_RAW_TREE)``:
+    every field of every info dict of the three splits -> tests/golden/kitti_raw.npz. mmcv's ``list_from_file`` and
+    skimage's ``io.imread`` (absent wheels) are stand-ins: a list of stripped lines, the decoded image via PIL."""
+    import tempfile
+    from PIL import Image
+    sys.modules['mmcv'].list_from_file = lambda path: [line.rstrip('\n\r') for line in open(path)]
+    _mod('skimage', io=_mod('skimage.io', imread=lambda path: np.asarray(Image.open(path))))
+    if not hasattr(np, 'bool'):
+        np.bool = bool
+    du = load('tools.data_converter.kitti_data_utils', 'tools/data_converter/kitti_data_utils.py')
+    out = {}
+
+    def put(prefix, value):
+        if isinstance(value, dict):
+            out[prefix + '.keys'] = np.array(list(value))          # in insertion order
+            for k, v in value.items():
+                put(f'{prefix}.{k}', v)
+        else:
+            out[prefix] = np.asarray(value)
+
+    with tempfile.TemporaryDirectory() as tmp:
+        ids = synthetic.write_kitti_raw_tree(tmp, **KITTI_RAW_TREE)
+        for split in ('train', 'val', 'test'):
+            training = split != 'test'
+            infos = du.get_kitti_image_info(tmp, training=training, label_info=training, velodyne=True, calib=True,
+                                            with_plane=training, image_ids=ids[split], relative_path=True)
+            out[f'{split}.ids'] = np.array(ids[split])
+            for i, info in zip(ids[split], infos):
+                put(f'{split}.{i}', info)
+        plain = du.get_kitti_image_info(tmp, training=True, calib=True, image_ids=ids['train'][:1], extend_matrix=False,
+                                        relative_path=False, with_imageshape=False)[0]
+        plain['image']['image_path'] = os.path.relpath(plain['image']['image_path'], tmp)
+        put('plain', plain)
+        label = os.path.join(tmp, 'training', 'label_2', f"{ids['train'][0]:06d}.txt")
+        anno = du.get_label_anno(label)
+        put('label_anno', anno)
+        out['difficulty_return'] = np.array(du.add_difficulty_to_annos(dict(annos=anno)))
+        scored = os.path.join(tmp, 'scored.txt')          # a detection file: a 16th column
+        with open(scored, 'w') as f:
+            f.write(''.join(line.rstrip('\n') + ' %.2f\n' % (0.25 * (n + 1)) for n, line in enumerate(open(label))))
+        put('label_anno_scored', du.get_label_anno(scored))
+    np.savez_compressed(os.path.join(OUT, 'kitti_raw.npz'), **out)
+    print('  kitti raw:', len(out), 'arrays;', {s: out[f'{s}.ids'].tolist() for s in ('train', 'val', 'test')})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = import_reference()
@@ -2132,6 +2182,7 @@ def main():
     golden_tta(ref)
     golden_indoor_datasets(ref)
     golden_kitti_mono(ref)
+    golden_kitti_raw(ref)
     for f in sorted(os.listdir(OUT)):
         print(f'{f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB')
 
