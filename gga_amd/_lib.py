@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 _lib = None
 
@@ -127,7 +127,6 @@ SIGNATURES = {
     'gga_sparse_conv_wgrad_workspace_bytes': (sz, [i64, i32, i32, i32]),
     'gga_dense_wgrad3x3_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
     'gga_sparse_pack_weight_planes': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
-    'gga_sparse_conv_apply_stats': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp]),
     'gga_sparse_conv_apply_tiles': (i64, [i64]),
     'gga_sparse_conv_apply_bn_bwd': (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
     'gga_sparse_bev_nhwc_fwd': (i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp]),

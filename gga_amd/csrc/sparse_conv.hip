@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64 * X9_NW, 2) void sp_conv_x9_kernel(const float* 
     // tile of this workgroup. tile_order 0: tiles in reverse (the mask-sorted order puts the rows with most neighbours
     // last: those start first). 1: XCD-major - workgroups are dealt to the 8 XCDs round robin, so workgroup b takes tile
     // (b % 8) * ceil(tiles / 8) + b / 8: every XCD walks a contiguous range of tiles in order and the rows its tiles gather
-    // (neighbours of a spatially ordered row range, see sparse.py) stay in that XCD's L2. The grid is rounded up to 8 * ceil.
+    // (neighbours of a spatially ordered row range, see gather_gemm.py::_Halo) stay in that XCD's L2. The grid is rounded up to 8 * ceil.
     int64_t tile = (int64_t)gridDim.x - 1 - blockIdx.x;
     if (tile_order == 1) {
         const int64_t per = (n_tiles + 7) / 8;
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(64 * X9_NW, 2) void sp_conv_x9_kernel(const float* 
 //   issue   every gathered fp32 element is split into its two fp16 planes by the lane that feeds it to the MFMA - ~12 vector
 //           instructions per pair of elements, 27 times per element: ~900 issue cycles per wave and stage next to 768 cycles
 //           of matrix work.
-// This form removes both. The rows are tiled in SPATIAL order (256 consecutive rows of a Z-ordered level, sparse.py::_Halo),
+// This form removes both. The rows are tiled in SPATIAL order (256 consecutive rows of a Z-ordered level, gather_gemm.py::_Halo),
 // so the 27 x 256 neighbours of a tile are only ~1.4 x 256 DISTINCT rows (its halo). Per 32-channel chunk the halo is
 // fetched ONCE into an LDS image (512 rows x 128 B, LDS-DMA, whole 128-byte lines), split ONCE, in place, into the two fp16
 // planes (the same 128 bytes per row), and all 27 offsets read their A fragments from the image - ready to use - through a
@@ -830,14 +830,6 @@ extern "C" int gga_sparse_conv_apply_halo(const float* x, const void* split_weig
 }
 
 extern "C" int64_t gga_sparse_conv_apply_tiles(int64_t n_rows) { return (n_rows + X9_TM - 1) / X9_TM; }
-
-extern "C" int gga_sparse_conv_apply_stats(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                           const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,
-                                           float* y, int64_t y_row_stride, int planes, const uint32_t* amax_x,
-                                           const uint32_t* amax_weight, double* stats, void* stream_) {
-    return gga_sparse_conv_apply_bn_bwd(x, map, split_weight, perm, rowmask, n_rows, kvol, cin, cout, flip, y, y_row_stride, planes,
-                                        amax_x, amax_weight, stats, nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream_);
-}
 
 extern "C" int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
                                             const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip,

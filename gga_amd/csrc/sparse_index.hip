@@ -403,7 +403,7 @@ extern "C" int gga_sparse_mask_order(const uint32_t* mask, int64_t n_rows, int k
     return GGA_OK;
 }
 
-// Rows of a level along a Z-order curve per sample (the halo form's tiles, sparse.py: morton_order): key = sample, then the
+// Rows of a level along a Z-order curve per sample (the halo form's tiles, gather_gemm.py: morton_order): key = sample, then the
 // bit-interleaved (z, y, x) - 17 elementwise launches and a merge sort of int64 keys in the framework; here one key kernel and an
 // Onesweep radix sort over the bits the level's extent can set. Coordinates are distinct, so the order is THE ascending order of
 // the keys whatever sorts them.

@@ -8,7 +8,8 @@ checkpoints load; the arithmetic is the published DCNv2 definition (oracle/dcn_r
 plain torch).
 
 Sampling (``gga_dcn_im2col``) and its backward (``gga_dcn_col2im``) are hand-written HIP kernels on
-channels-last activations; the two GEMMs are library GEMMs (``torch.matmul`` -> hipBLASLt).
+channels-last activations; the three matrix products run on the gather-GEMM kernels (``gather_gemm.apply`` / ``wgrad``
+over the rows of the column matrix), library GEMMs (``torch.matmul`` -> hipBLASLt) for the widths those do not take.
 """
 import math
 
@@ -17,6 +18,7 @@ from torch import nn
 
 from . import _lib
 from . import functional as F
+from . import gather_gemm as G
 from ._lib import check
 from .registry import CONV_LAYERS
 
@@ -31,18 +33,17 @@ _MAPS = {}
 
 def _maps(n_pix, K, device):
     """Rule books that make the three matrix products of a DCN call gather-GEMMs over the rows of the column matrix
-    viewed as [n_pix * K, C] (``strided_conv._apply`` / ``_wgrad``): ``fwd`` [K, n_pix]: row of (tap, pixel);
-    ``bwd`` [K, n_pix * K]: the pixel whose gradient reaches column row r through tap r % K (-1 for the other taps),
-    with its row masks / mask-sorted order. Built once per (pixels, taps)."""
+    viewed as [n_pix * K, C] (``gather_gemm.apply`` / ``wgrad``): ``fwd.nbr`` [K, n_pix]: row of (tap, pixel);
+    ``bwd.nbr`` [K, n_pix * K]: the pixel whose gradient reaches column row r through tap r % K (-1 for the other taps).
+    Built once per (pixels, taps)."""
     key = (n_pix, K, str(device))
     if key not in _MAPS:
-        from .strided_conv import _Book
         with torch.no_grad():
             p = torch.arange(n_pix, device=device, dtype=torch.int32)
             fwd = torch.stack([p * K + k for k in range(K)]).contiguous()
             r = torch.arange(n_pix * K, device=device, dtype=torch.int32)
             bwd = torch.stack([torch.where(r % K == k, r // K, -1) for k in range(K)]).int().contiguous()
-            _MAPS[key] = (fwd, *_Book._order(fwd), bwd, *_Book._order(bwd))
+            _MAPS[key] = (G.Rulebook(fwd, uniform_check=True), G.Rulebook(bwd, uniform_check=True))
     return _MAPS[key]
 
 
@@ -68,13 +69,13 @@ class _ModulatedDeformConv(torch.autograd.Function):
         if ctx.matrix:
             # y[p] = sum_k col[p * K + k] W_k: the gather-GEMM of the strided convolutions over the rows of col (two fp16
             # planes on the matrix cores; the library's fp32 GEMM ran these shapes at 57 TFLOP/s). im2col leaves max |col|.
-            from . import dense_conv, strided_conv
+            from . import dense_conv
             col_amax = dense_conv.new_amax(x.device)
             check(L.gga_dcn_im2col_amax(F._p(xl), F._p(offset), F._p(mask), *geom, F._p(col), F._p(col_amax), F._stream()),
                   'gga_dcn_im2col')
-            fwd, fmask, fperm = _maps(n_pix, K, x.device)[:3]
+            fwd, _ = _maps(n_pix, K, x.device)
             w_kio = weight.detach().permute(2, 3, 1, 0).reshape(K, C, cout).contiguous()
-            y = strided_conv._apply(col.view(n_pix * K, C), fwd, fmask, fperm, w_kio, n_pix, col_amax)
+            y = G.apply(col.view(n_pix * K, C), fwd, w_kio, n_pix, planes=G.planes(), x_amax=col_amax)
         else:
             check(L.gga_dcn_im2col(F._p(xl), F._p(offset), F._p(mask), *geom, F._p(col), F._stream()), 'gga_dcn_im2col')
             wmat = weight.permute(0, 2, 3, 1).reshape(cout, kh * kw * C)       # [Cout, tap, C]: the column order
@@ -109,16 +110,15 @@ class _ModulatedDeformConv(torch.autograd.Function):
                   'gga_dcn_im2col')
         gw = gb = gx = None
         if ctx.matrix:
-            from . import strided_conv
-            fwd, _, _, bwd, bmask, bperm = _maps(n_pix, K, g.device)
-            g_amax = strided_conv._amax(g)
+            fwd, bwd = _maps(n_pix, K, g.device)
+            g_amax = G.amax(g)
             if ctx.needs_input_grad[3]:       # gw[k] = sum_p col[p * K + k]^T g[p]
-                gw_kio = strided_conv._wgrad(col.view(n_pix * K, C), g, fwd, n_pix, col_amax, g_amax)
+                gw_kio = G.wgrad(col.view(n_pix * K, C), g, fwd.nbr, n_pix, planes=G.planes(), x_amax=col_amax, g_amax=g_amax)
                 gw = gw_kio.view(kh, kw, C, cout).permute(3, 2, 0, 1)
             del col
             # grad_col[p * K + k] = g[p] W_k^T: every row of grad_col runs the one tap of its position
             w_koi = weight.detach().permute(2, 3, 0, 1).reshape(K, cout, C).contiguous()
-            gcol = strided_conv._apply(g, bwd, bmask, bperm, w_koi, n_pix * K, g_amax).view(n_pix, K * C)
+            gcol = G.apply(g, bwd, w_koi, n_pix * K, planes=G.planes(), x_amax=g_amax).view(n_pix, K * C)
         else:
             if ctx.needs_input_grad[3]:
                 gw = (g.t() @ col).view(cout, kh, kw, C).permute(0, 3, 1, 2)

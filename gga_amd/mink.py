@@ -31,7 +31,7 @@ spatial axis FASTEST). Training from scratch is indifferent to the numbering (th
 from a real MinkowskiEngine convolution with an asymmetric kernel pins the order, **checkpoints are not interchangeable with
 the reference's FCAF3D**; ``reorder_kernel_offsets`` converts a kernel between the two numberings for whoever has such a file.
 
-Convolutions run on the gather-GEMM kernels of the sparse 3D trunk (``strided_conv._apply`` / ``_wgrad``: forward,
+Convolutions run on the gather-GEMM kernels of the sparse 3D trunk (``gather_gemm.apply`` / ``wgrad``: forward,
 backward-data and the deterministic weight gradient) through rule books built by ``gga_sparse_rulebook`` on the hash index
 of ``sparse._Level``; coordinates are kept per level in units of the tensor stride and shifted to be non-negative."""
 import math
@@ -41,8 +41,10 @@ from torch import nn
 
 from . import _lib
 from . import functional as F
+from . import gather_gemm as G
 from ._lib import check
-from .sparse import _Level, _Rulebook, _i3
+from .gather_gemm import Rulebook
+from .sparse import _Level, _i3
 
 def reorder_kernel_offsets(kernel, kernel_size):
     """``kernel`` [kernel_size^3, Cin, Cout] numbered with the first spatial axis FASTEST (k = k1 + K k2 + K^2 k3) -> the
@@ -131,7 +133,7 @@ class CoordMap:
                 hit = (None, None)
             elif kernel == 3 and stride == 1:
                 rb = self.level.subm_rulebook((3, 3, 3))
-                hit = (rb, _Rulebook(rb.nbr.flip(0).contiguous()))       # SubM: the transposed map is the reversed offsets
+                hit = (rb, Rulebook(rb.nbr.flip(0).contiguous()))       # SubM: the transposed map is the reversed offsets
             else:
                 L = _lib.lib()
                 kvol = kernel ** 3
@@ -143,7 +145,7 @@ class CoordMap:
                                             _i3(self.extent), _i3(out_map.extent), _i3((kernel,) * 3), _i3((stride,) * 3), _i3((pad,) * 3),
                                             F._p(self.level.index), self.level.index_n, F._p(out_map.level.index), out_map.level.index_n,
                                             F._p(nbr), F._p(nbr_t), F._stream()), 'gga_sparse_rulebook')
-                hit = (_Rulebook(nbr), _Rulebook(nbr_t))
+                hit = (Rulebook(nbr), Rulebook(nbr_t))
             self.cache[key] = hit
         return hit
 
@@ -159,7 +161,7 @@ class CoordMap:
             for o in range(8):
                 nbr[o, :, o] = rows
                 nbr_t[o] = rows * 8 + o
-            hit = self.cache[key] = (_Rulebook(nbr.reshape(8, self.n * 8).contiguous()), _Rulebook(nbr_t))
+            hit = self.cache[key] = (Rulebook(nbr.reshape(8, self.n * 8).contiguous()), Rulebook(nbr_t))
         return hit
 
 
@@ -260,20 +262,18 @@ class _MapConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, fwd, bwd, n_out, flip_bwd):
-        from . import strided_conv as S
         x = x.contiguous()
         w = weight.detach().contiguous()
         # the layer's own parameter (not the zero-padded temporary of odd widths, map_conv): its packed operands live in the
         # weight bank and are refreshed with all others once per optimizer step
         banked = weight.grad_fn is None and w.data_ptr() == weight.data_ptr()
-        y = S._apply(x, fwd.nbr, fwd.mask, fwd.perm, w, n_out, bank=banked)
+        y = G.apply(x, fwd, w, n_out, planes=G.planes(), bank=banked)     # (not banked: the weight's absmax is one pass per call)
         ctx.save_for_backward(x, weight)
         ctx.maps, ctx.flip, ctx.banked = (fwd, bwd, n_out), flip_bwd, banked
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        from . import strided_conv as S
         x, weight = ctx.saved_tensors
         fwd, bwd, n_out = ctx.maps
         gy = gy.contiguous()
@@ -282,9 +282,9 @@ class _MapConv(torch.autograd.Function):
             # gx[i] = sum_k gy[bwd[k][i]] W[k]^T: bwd[k][i] is the output row that reads row i through offset k (for SubM maps
             # that is row K-1-k of the forward rule book, which is how CoordMap.kernel_map builds it)
             wt = weight.detach().transpose(1, 2)                # [kvol, cout, cin]: a view for the bank, a copy otherwise
-            gx = S._apply(gy, bwd.nbr, bwd.mask, bwd.perm, wt if ctx.banked else wt.contiguous(), x.shape[0], bank=ctx.banked)
+            gx = G.apply(gy, bwd, wt if ctx.banked else wt.contiguous(), x.shape[0], planes=G.planes(), bank=ctx.banked)
         if ctx.needs_input_grad[1]:
-            gw = S._wgrad(x, gy, fwd.nbr, n_out)
+            gw = G.wgrad(x, gy, fwd.nbr, n_out, planes=G.planes())
         return gx, gw, None, None, None, None
 
 

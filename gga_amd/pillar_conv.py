@@ -3,13 +3,13 @@
 The canvas of ``PointPillarsScatter`` (pillar_scatter.py:58-102) is zero except at the occupied
 cells (~7 % at KITTI sizes), and its gradient is read back only there (the scatter's backward is a
 gather). The forward of the convolution that consumes it (second.py:49-57, block 0, conv 0) is the
-plain dense convolution (run as strided_conv.py's gather-GEMM over the canvas rows); its backward needs
+plain dense convolution (run as a gather-GEMM over the canvas rows with strided_conv.py's rule book); its backward needs
 
 * the input gradient only at the occupied cells,
 * the weight gradient ``sum_cells x^T gy``, where ``x`` is non-zero only at the occupied cells,
 
 i.e. a gather-GEMM over the pillars with the gather map ``gga_pillar_conv_map`` — the same
-kernels as the sparse 3D convolution (``gga_sparse_conv_apply_bn_bwd`` / ``gga_sparse_conv_wgrad_planes``),
+kernels as the sparse 3D convolution (``gather_gemm.apply`` / ``gather_gemm.wgrad``),
 with the output gradient (NHWC rows = output cells) as the gathered operand. At batch 16 that
 replaces a 3.1 ms backward-data convolution into an 877 MB canvas gradient (+ its zero fill and
 the scatter's gather) and a 3.3 ms weight-gradient convolution by < 0.5 ms of work; the values
@@ -21,6 +21,7 @@ from torch import nn
 
 from . import _lib
 from . import functional as F
+from . import gather_gemm as G
 from ._lib import check
 
 
@@ -51,13 +52,12 @@ class _PillarConv2d(torch.autograd.Function):
         kh, kw = weight.shape[2:]
         if (strided_conv.ENABLED and kh == kw and stride[0] == stride[1] and padding[0] == padding[1] and stride[0] > 1
                 and kh <= 5 and weight.shape[0] % 4 == 0):
-            # the dense forward as a gather-GEMM over the canvas rows (strided_conv.py): no framework convolution
+            # the dense forward as a gather-GEMM over the canvas rows (strided_conv.py's rule book): no framework convolution
             B, Ci, ny, nx = canvas.shape
             bk = strided_conv.book(B, ny, nx, kh, stride[0], padding[0], canvas.device)
             # the canvas holds the pillar features and zeros: its largest magnitude is theirs (16 MB instead of 877 MB)
-            y, stats = strided_conv._apply(strided_conv._rows(canvas), bk.fwd, bk.fwd_mask, bk.fwd_perm,
-                                           weight.detach().permute(2, 3, 1, 0).reshape(kh * kw, Ci, -1), bk.n_out,
-                                           strided_conv._amax(feats.detach().contiguous()), want_stats=True)
+            y, stats = G.apply(canvas.permute(0, 2, 3, 1).reshape(-1, Ci), bk.fwd, weight.detach().permute(2, 3, 1, 0).reshape(kh * kw, Ci, -1),
+                               bk.n_out, planes=G.planes(), x_amax=G.amax(feats.detach().contiguous()), want_stats=True)
             y = y.view(B, bk.Ho, bk.Wo, -1).permute(0, 3, 1, 2)
         else:
             y = torch.conv2d(canvas, weight, None, stride, padding)
@@ -70,7 +70,6 @@ class _PillarConv2d(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gstats=None):
-        from .sparse import _Rulebook, _conv_apply, _pack_weight, conv_wgrad
         feats, w, coors, num_valid = ctx.saved_tensors
         (B, Ci, ny, nx), (sh, sw), (ph, pw) = ctx.geom
         Co, _, kh, kw = w.shape
@@ -83,15 +82,13 @@ class _PillarConv2d(torch.autograd.Function):
         check(L.gga_pillar_conv_map(F._p(coors), m, F._p(num_valid), B, ny, nx, kh, kw, sh, sw, ph, pw, F._p(nbr),
                                     F._stream()), 'gga_pillar_conv_map')
         gx = gw = None
+        # both backward products on three bf16 planes whatever dense_conv.PLANES says: they never took the operands' absmax
         if ctx.needs_input_grad[0]:
-            rb = _Rulebook(nbr)             # rows sorted by tap pattern (the parity class of the cell)
+            rb = G.Rulebook(nbr)            # rows sorted by tap pattern (the parity class of the cell)
             wk = w.permute(2, 3, 0, 1).reshape(kvol, Co, Ci).contiguous()       # tap-major [k][co][ci]
-            gx = torch.empty_like(feats)
-            _conv_apply(rows, rb, _pack_weight(wk, kvol, Co, Ci, 0), m, kvol, Co, Ci, 0, gx)
+            gx = G.apply(rows, rb, wk, m, planes=3)
         if ctx.needs_input_grad[1]:
-            g = torch.empty((kvol, Co, Ci), dtype=torch.float32, device=gy.device)
-            conv_wgrad(rows, feats, nbr, m, kvol, Co, Ci, g)
-            gw = g.view(kh, kw, Co, Ci).permute(2, 3, 0, 1)
+            gw = G.wgrad(rows, feats, nbr, m, planes=3).view(kh, kw, Co, Ci).permute(2, 3, 0, 1)
         return gx, gw, None, None, None, None, None
 
 

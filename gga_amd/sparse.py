@@ -9,15 +9,18 @@ spatial_shape, batch_size)`` with ``.features`` / ``.indices`` / ``.dense()`` /
 bias=False)`` works unchanged. Weights use the mmcv layout ``[kz, ky, kx, Cin, Cout]``.
 """
 import ctypes as C
-import os
 import math
+import os
 
 import torch
 from torch import nn
 
 from . import _lib
 from . import functional as F
+from . import gather_gemm as G
 from ._lib import check
+# (the tilings and orders are reached as sparse._Halo / mask_order / morton_order by bench.py's sparse roofline and the tests)
+from .gather_gemm import Rulebook, _Halo, mask_order, morton_order         # noqa: F401
 from .registry import CONV_LAYERS
 
 
@@ -27,93 +30,6 @@ def _triple(v):
 
 def _i3(v):
     return (C.c_int32 * 3)(*v)
-
-
-def mask_order(mask, kvol):
-    """Rows in ascending order of their offset mask, ties in row order: what ``torch.sort(mask, stable=True)[1].int()`` returns,
-    from an LSD radix sort over the ``kvol`` mask bits (gga_sparse_mask_order, include/gga_hip.h) - the framework's stable
-    sort of int32 keys is a 22-launch merge sort per rule book on this stack."""
-    L = _lib.lib()
-    n = int(mask.shape[0])
-    order = torch.empty(n, dtype=torch.int32, device=mask.device)
-    nbytes = int(L.gga_sparse_mask_order_workspace_bytes(n))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
-    check(L.gga_sparse_mask_order(F._p(mask), n, int(kvol), F._p(order), F._p(ws), nbytes, F._stream()), 'gga_sparse_mask_order')
-    return order
-
-
-class _Rulebook:
-    """Gather map [kvol, n_rows] + per-row offset bit mask + mask-sorted processing order."""
-
-    def __init__(self, nbr, coors=None, occupancy=0.0, extent=None):
-        self.nbr = nbr
-        kvol, n = nbr.shape
-        self.mask = self.perm = None
-        # submanifold rule books: the level's coordinates and the share of its grid cells that are active (halo form)
-        self.coors, self.occupancy, self._halo = coors, occupancy, None
-        self.extent = extent                    # (batch size, largest grid extent) of the level, for the Z-order tiling
-        if kvol <= 32:
-            self.mask = torch.empty(n, dtype=torch.int32, device=nbr.device)
-            check(_lib.lib().gga_sparse_rowmask(F._p(nbr), n, kvol, F._p(self.mask), F._stream()), 'gga_sparse_rowmask')
-            # index preprocessing (once per level, shared by every conv on it): rows with the same
-            # neighbour pattern become adjacent, so a 128-row tile skips the offsets none of them uses
-            self.perm = mask_order(self.mask, kvol)
-
-    def halo(self):
-        if self._halo is None:
-            self._halo = _Halo(self.coors, self)
-        return self._halo
-
-
-def _spread3(v):
-    """Bits of v (< 2^16, int64) moved to every third position."""
-    v = v & 0xFFFF
-    v = (v | (v << 32)) & 0x1F00000000FFFF
-    v = (v | (v << 16)) & 0x1F0000FF0000FF
-    v = (v | (v << 8)) & 0x100F00F00F00F00F
-    v = (v | (v << 4)) & 0x10C30C30C30C30C3
-    v = (v | (v << 2)) & 0x1249249249249249
-    return v
-
-
-def morton_order(coors, batch_size=None, max_extent=None):
-    """Rows of ``coors`` [n,4] (batch, z, y, x) along a Z-order curve per sample: consecutive rows are close in space.
-    With the level's ``batch_size`` and largest grid extent on a device tensor: gga_sparse_morton_order (one key kernel + a radix
-    sort over the bits the extent can set; int32 order) - the expression below is 17 elementwise launches and a merge sort."""
-    if batch_size is not None and max_extent is not None and coors.is_cuda and coors.dtype == torch.int32 and coors.shape[0]:
-        L = _lib.lib()
-        c = coors.contiguous()
-        n = int(c.shape[0])
-        order = torch.empty(n, dtype=torch.int32, device=c.device)
-        nbytes = int(L.gga_sparse_morton_order_workspace_bytes(n))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=c.device)
-        check(L.gga_sparse_morton_order(F._p(c), n, int(batch_size), int(max_extent), F._p(order), F._p(ws), nbytes, F._stream()),
-              'gga_sparse_morton_order')
-        return order
-    c = coors.long()
-    key = (c[:, 0] << 48) | (_spread3(c[:, 1]) << 2) | (_spread3(c[:, 2]) << 1) | _spread3(c[:, 3])
-    return torch.argsort(key)
-
-
-class _Halo:
-    """Tiling of a submanifold rule book for gga_sparse_conv_apply_halo (include/gga_hip.h): tiles of 256 rows in Z-order,
-    each with the list of distinct input rows its entries name and the entries rewritten as positions in that list
-    (gga_sparse_halo_build)."""
-
-    def __init__(self, coors, rb):
-        L = _lib.lib()
-        TM = int(L.gga_sparse_halo_tile_rows())
-        kvol, n = rb.nbr.shape
-        dev = rb.nbr.device
-        self.n_tiles = T = (n + TM - 1) // TM
-        self.tile_rows = torch.full((T * TM,), -1, dtype=torch.int32, device=dev)
-        self.tile_rows[:n] = morton_order(coors, *(rb.extent or (None, None))).int()
-        self.capacity = kvol * TM
-        self.halo_rows = torch.empty((T, self.capacity), dtype=torch.int32, device=dev)
-        self.counts = torch.empty(T, dtype=torch.int32, device=dev)
-        self.local_map = torch.empty((T, kvol, TM), dtype=torch.int16, device=dev)
-        check(L.gga_sparse_halo_build(F._p(rb.nbr), F._p(self.tile_rows), n, T, kvol, self.capacity, F._p(self.halo_rows),
-                                      F._p(self.counts), F._p(self.local_map), F._stream()), 'gga_sparse_halo_build')
 
 
 class _Level:
@@ -149,7 +65,7 @@ class _Level:
                                                  F._p(self.index), self.index_n, None, 0, F._p(nbr), None,
                                                  F._stream()), 'gga_sparse_rulebook')
             cells = self.batch_size * self.shape[0] * self.shape[1] * self.shape[2]
-            nbr = _Rulebook(nbr, self.coors, self.n / max(cells, 1), (self.batch_size, max(self.shape)))
+            nbr = Rulebook(nbr, self.coors, self.n / max(cells, 1), (self.batch_size, max(self.shape)))
             self._subm[kernel] = nbr
         return nbr
 
@@ -183,7 +99,7 @@ class _Level:
                                     _i3(out.shape), _i3(kernel), _i3(stride), _i3(padding), F._p(self.index),
                                     self.index_n, F._p(out_index), out.index_n, F._p(nbr), F._p(nbr_t), F._stream()),
               'gga_sparse_rulebook')
-        return out, _Rulebook(nbr), _Rulebook(nbr_t)
+        return out, Rulebook(nbr), Rulebook(nbr_t)
 
 
 def _empty_level(shape, batch_size, device):
@@ -338,68 +254,11 @@ class SparseSequential(SparseModule):
 # channels), its 128 accumulators per wave leave no registers for a second set, and ending a chain through the accumulator file
 # costs ~5 vector instructions per element (measured: the compiler spills 1 000 registers; by hand 640 instructions per chain end):
 # 0.8 ms of the 52 ms step bought the last rows of the precision table (profiles/r06_sparse_chain_ab.txt).
+# gather_gemm.apply reads these; any rule book that carries its level's coordinates can take the form (subm_rulebook below).
 HALO = int(os.environ.get('GGA_SP_HALO', '0'))
 HALO_COLUMNS = (128,)
 HALO_MIN_ROWS = int(os.environ.get('GGA_SP_HALO_MIN_ROWS', '65536'))
 HALO_MIN_OCCUPANCY = float(os.environ.get('GGA_SP_HALO_MIN_OCCUPANCY', '0.25'))
-
-
-
-def planes():
-    """Arithmetic of the split-plane gather kernels: 2 = two fp16 planes of the scaled operands / three partial
-    products, 3 = three bf16 planes / six (dense_conv.PLANES, one switch for all matrix kernels)."""
-    from . import dense_conv
-    return dense_conv.PLANES
-
-
-def amax_bits(t):
-    """Absmax bits of ``t``: left by its producer (the fused BatchNorm kernels) when possible, else one pass."""
-    from . import dense_conv
-    return dense_conv.tensor_amax(t)
-
-
-def _pack_weight(w, kvol, cin, cout, transpose, w_amax=None):
-    """[kvol,cin,cout] (or [kvol,cout,cin] with ``transpose``) -> the conv kernel's operand order
-    (gga_sparse_pack_weight_planes). ``w_amax``: absmax bits of the weight -> two fp16
-    planes; None -> three bf16 planes (fp32 as the sum of three bf16 numbers: nine exact partial products on the
-    matrix cores, fp32 accumulation - csrc/sparse_conv.hip, tools_dev/micro/bf16x9_probe.hip)."""
-    L = _lib.lib()
-    wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, cout) // 2, dtype=torch.int16, device=w.device)
-    check(L.gga_sparse_pack_weight_planes(F._p(w), kvol, cin, cout, transpose, 2 if w_amax is not None else 3, F._p(w_amax),
-                                          F._p(wp), F._stream()), 'gga_sparse_pack_weight_planes')
-    return wp
-
-
-def _conv_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, x_amax=None, w_amax=None, stats=None, bn=None):
-    """``x_amax`` / ``w_amax`` given: ``wp`` holds two fp16 planes (packed with the same ``w_amax``). ``stats``: f64
-    [gga_sparse_conv_apply_tiles(n_rows), 2, cout] for the per-channel sums of y. ``bn``
-    (backward-data launches, with ``stats``): ``BnSource.part`` pointers of the BatchNorm + ReLU whose output gradient y
-    is - y is stored masked by the ReLU and ``stats`` receives that BatchNorm's backward sums."""
-    L = _lib.lib()
-    if (HALO and w_amax is not None and rb.coors is not None and cin % 32 == 0 and 9 <= kvol <= 27
-            and cout in HALO_COLUMNS and n_rows >= HALO_MIN_ROWS and rb.occupancy >= HALO_MIN_OCCUPANCY):
-        hl = rb.halo()
-        check(L.gga_sparse_conv_apply_halo(F._p(x), F._p(wp), F._p(hl.tile_rows), F._p(hl.counts), hl.capacity, F._p(hl.halo_rows),
-                                           F._p(hl.local_map), n_rows, hl.n_tiles, kvol, cin, cout, flip, F._p(y), cout, 2, F._p(x_amax),
-                                           F._p(w_amax), F._p(stats), *(bn if bn else (None, 0, None, None, None, None)), F._stream()),
-              'gga_sparse_conv_apply_halo')
-        return
-    check(L.gga_sparse_conv_apply_bn_bwd(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n_rows,
-                                         kvol, cin, cout, flip, F._p(y), cout, 2 if w_amax is not None else 3, F._p(x_amax),
-                                         F._p(w_amax), F._p(stats), *(bn if bn else (None, 0, None, None, None, None)),
-                                         F._stream()), 'gga_sparse_conv_apply_bn_bwd')
-
-
-def conv_wgrad(x, gy, nbr, n_rows, kvol, cin, cout, gw, x_amax=None, g_amax=None):
-    """gw [kvol,cin,cout] = sum over the pairs of ``nbr`` of x[in]^T gy[out]: the deterministic
-    split-plane kernel (two fp16 planes when the operands' absmax bits are given, three bf16 planes otherwise)."""
-    L = _lib.lib()
-    ws = F._workspace('sp_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, cin, cout), x.device)
-    two = x_amax is not None and g_amax is not None
-    check(L.gga_sparse_conv_wgrad_planes(F._p(x), cin, F._p(gy), cout, F._p(nbr), n_rows, kvol, cin, cout, F._p(gw),
-                                         2 if two else 3, F._p(x_amax) if two else None, F._p(g_amax) if two else None,
-                                         F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_planes')
-    return gw
 
 
 class _SparseConvFn(torch.autograd.Function):
@@ -411,30 +270,20 @@ class _SparseConvFn(torch.autograd.Function):
         feats, w = feats.contiguous(), weight.contiguous()
         kvol = rb.nbr.shape[0]
         cin, cout = w.shape[-2], w.shape[-1]
-        y = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-        two = planes() == 2
-        x_amax = amax_bits(feats) if two else None
+        planes = G.planes()
+        x_amax = G.amax(feats)
         banked = cout <= 128 and w.data_ptr() == weight.data_ptr()      # the parameter itself: its operands live in the weight bank
-        w_amax = amax_bits(w.detach()) if two and not banked else None
+        w_amax = None if banked else G.amax(w.detach())
         # the per-channel sums of y for the BatchNorm that follows (widths the fused BatchNorm takes)
-        stats = None
-        if cout % 4 == 0 and cout <= 128 and n_out >= 1:
-            stats = torch.empty((int(_lib.lib().gga_sparse_conv_apply_tiles(n_out)), 2, cout), dtype=torch.float64, device=feats.device)
-        if banked:
-            from . import dense_conv, weight_bank
-            wp, w_amax = weight_bank.gather_operand(w.detach().reshape(kvol, cin, cout), planes())
-            if two and dense_conv.RANGE_GUARD.armed:
-                dense_conv.RANGE_GUARD.record(w.detach())
-        else:
-            wp = _pack_weight(w, kvol, cin, cout, 0, w_amax=w_amax)
-        _conv_apply(feats, rb, wp, n_out, kvol, cin, cout, 0, y, x_amax, w_amax, stats)
+        want_stats = cout % 4 == 0 and cout <= 128 and n_out >= 1
+        res = G.apply(feats, rb, w.detach().reshape(kvol, cin, cout), n_out, planes=planes, x_amax=x_amax, w_amax=w_amax,
+                      want_stats=want_stats, bank=banked)
+        y, stats = res if want_stats else (res, torch.empty(0, dtype=torch.float64, device=feats.device))
         ctx.save_for_backward(feats, w)
-        ctx.rb, ctx.rb_t, ctx.amax, ctx.banked = rb, rb_t, (x_amax, w_amax), banked
+        ctx.rb, ctx.rb_t, ctx.planes, ctx.amax, ctx.banked = rb, rb_t, planes, (x_amax, w_amax), banked
         # feats = relu(bn(.)) with this convolution as its consumer: the backward-data pass then does that BatchNorm's reduce
         from . import dense_conv
         ctx.bn_src = dense_conv.bn_source(feats, cin) if cin % 4 == 0 else None
-        if stats is None:
-            stats = torch.empty(0, dtype=torch.float64, device=feats.device)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)     # no zero tensors (one fill launch each) for the gradients of the non-differentiable outputs
         return y, stats
@@ -442,34 +291,28 @@ class _SparseConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, _gstats=None):
         feats, w = ctx.saved_tensors
-        rb, rb_t = ctx.rb, ctx.rb_t
+        rb, rb_t, planes = ctx.rb, ctx.rb_t, ctx.planes
         gy = gy.contiguous()
         kvol, n_out = rb.nbr.shape
         n_in = feats.shape[0]
         cin, cout = w.shape[-2], w.shape[-1]
-        L = _lib.lib()
         gx = gw = None
         x_amax, w_amax = ctx.amax
-        g_amax = amax_bits(gy) if x_amax is not None else None        # one pass for both consumers of gy
+        g_amax = G.amax(gy) if planes == 2 else None        # one pass for both consumers of gy
         if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(feats)
-            if ctx.banked:                    # W[k]^T: the transposed view of the parameter, from the weight bank
-                from . import weight_bank
-                wt, w_amax = weight_bank.gather_operand(w.detach().reshape(kvol, cin, cout).transpose(1, 2), planes())
-            else:
-                wt = _pack_weight(w, kvol, cout, cin, 1, w_amax=w_amax)   # W[k]^T in fragment order
+            # W[k]^T: the transposed view of the parameter (from the weight bank) or of its contiguous copy (packed in place)
+            wt = w.detach().reshape(kvol, cin, cout).transpose(1, 2)
             tb, flip = (rb_t, 0) if rb_t is not None else (rb, 1)     # SubM: transposed map = reversed offsets
             src = ctx.bn_src
-            if src is not None:
+            bn = src.part(0, cin) if src is not None else None
+            gx = G.apply(gy, tb, wt, n_in, planes=planes, x_amax=g_amax, w_amax=w_amax, flip=flip, want_stats=bn is not None,
+                         bank=ctx.banked, bn=bn, guard=False)
+            if bn is not None:
                 from . import dense_conv
-                st = torch.empty((int(L.gga_sparse_conv_apply_tiles(n_in)), 2, cin), dtype=torch.float64, device=gy.device)
-                _conv_apply(gy, tb, wt, n_in, kvol, cout, cin, flip, gx, g_amax, w_amax, st, src.part(0, cin))
+                gx, st = gx
                 gx._gga_bn_bwd = dense_conv.BnPartials(gx, [(0, cin, st)], tuple(p[5].data_ptr() for p in src.parts))
-            else:
-                _conv_apply(gy, tb, wt, n_in, kvol, cout, cin, flip, gx, g_amax, w_amax)
         if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w)
-            conv_wgrad(feats, gy, rb.nbr, n_out, kvol, cin, cout, gw, x_amax, g_amax)
+            gw = G.wgrad(feats, gy, rb.nbr, n_out, planes=planes, x_amax=x_amax, g_amax=g_amax, out=torch.empty_like(w))
         return gx, gw, None, None, None
 
 

@@ -4,11 +4,11 @@ the repo's own matrix kernels: forward, backward-data and weight gradient.
 
 Over the pixel rows of a channels-last image all of them are gather-GEMMs ``y[row] = sum_k x[map[k][row]] W[k]``
 with an ARITHMETIC rule book - exactly what the sparse-convolution kernels compute from a hashed one
-(``gga_sparse_conv_apply_stats`` / ``gga_sparse_conv_wgrad_planes``: fp32 carried by operand planes,
+(``gather_gemm.apply`` / ``gather_gemm.wgrad``: fp32 carried by operand planes,
 deterministic weight gradient). The rule books depend on the shape only and are built once per
 (batch, map size, kernel, stride, padding); rows are visited grouped by their set of valid taps, so a transposed
 convolution's output rows run the one tap of their phase and border rows skip the padding taps.
-Channel widths above 128 run as 128-wide column blocks (the row strides of those entry points).
+Channel widths above 128 run as 128-wide column blocks (``gather_gemm``).
 """
 import ctypes as C
 import os
@@ -18,6 +18,7 @@ from torch import nn
 
 from . import _lib
 from . import functional as F
+from . import gather_gemm as G
 from ._lib import check
 
 ENABLED = True
@@ -31,9 +32,9 @@ _BOOKS = {}
 
 class _Book:
     """Rule books of a k x k / stride s / padding p convolution [B, H, W] -> [B, Ho, Wo]:
-    ``fwd`` [k*k, n_out]: input pixel of (tap, output pixel) or -1; ``bwd`` [k*k, n_in]: output pixel that
-    reaches the input pixel through that tap or -1; row masks and mask-sorted row orders of both. Each side is built when
-    it is first asked for (a transposed convolution on the streaming kernels needs ``fwd`` alone, for its weight gradient)."""
+    ``fwd.nbr`` [k*k, n_out]: input pixel of (tap, output pixel) or -1; ``bwd.nbr`` [k*k, n_in]: output pixel that
+    reaches the input pixel through that tap or -1. Each side is built when it is first asked for (a transposed convolution
+    on the streaming kernels needs ``fwd`` alone, for its weight gradient)."""
 
     def __init__(self, B, H, W, k, s, p, device):
         Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
@@ -41,15 +42,13 @@ class _Book:
         self.n_in, self.n_out = B * H * W, B * Ho * Wo
         self._geom = (B, H, W, k, s, p, device)
 
-    def __getattr__(self, name):                 # fwd, fwd_mask, fwd_perm, bwd, bwd_mask, bwd_perm
-        side = name.split('_')[0]
-        if side not in ('fwd', 'bwd') or name not in (side, side + '_mask', side + '_perm'):
-            raise AttributeError(name)
+    def __getattr__(self, side):
+        if side not in ('fwd', 'bwd'):
+            raise AttributeError(side)
         with torch.no_grad():
-            m = self._map(side)
-            mask, perm = self._order(m)
-        self.__dict__.update({side: m, side + '_mask': mask, side + '_perm': perm})
-        return self.__dict__[name]
+            # cached per shape: where every row has the same taps (kernel = stride) the natural row order is kept
+            self.__dict__[side] = G.Rulebook(self._map(side), uniform_check=True)
+        return self.__dict__[side]
 
     def _map(self, side):
         B, H, W, k, s, p, device = self._geom
@@ -70,18 +69,6 @@ class _Book:
                     rows.append(torch.where(ok, b * (Ho * Wo) + (ny // s) * Wo + nx // s, -1).reshape(-1))
         return torch.stack(rows).int().contiguous()
 
-    @staticmethod
-    def _order(m):
-        kvol, n = m.shape
-        if kvol > 32:
-            return None, None
-        mask = torch.empty(n, dtype=torch.int32, device=m.device)
-        check(_lib.lib().gga_sparse_rowmask(F._p(m), n, kvol, F._p(mask), F._stream()), 'gga_sparse_rowmask')
-        if bool((mask == mask[0]).all()):          # every row has the same taps: the natural order is the best one
-            return mask, None
-        from .sparse import mask_order
-        return mask, mask_order(mask, kvol)
-
 
 def book(B, H, W, k, s, p, device):
     key = (B, H, W, k, s, p, str(device))
@@ -97,86 +84,6 @@ def _rows(t):
     return t.permute(0, 2, 3, 1).reshape(B * H * W, C)
 
 
-def _planes():
-    from . import dense_conv
-    return dense_conv.PLANES
-
-
-def _amax(t):
-    """Absmax bits of ``t`` (left by its producer when possible), None on the three-bf16-plane path."""
-    from . import dense_conv
-    return dense_conv.tensor_amax(t) if dense_conv.PLANES == 2 else None
-
-
-def _apply(x_rows, m, mask, perm, w_kio, n_rows, x_amax=None, w_amax=None, want_stats=False, bank=False):
-    """y [n_rows, cout] = sum_k x_rows[m[k]] @ w_kio[k]  (w_kio [kvol, cin, cout]). ``x_amax`` / ``w_amax``: absmax
-    bits of the operands (two-plane arithmetic), computed here when missing. ``want_stats``: also return the f64
-    [workgroups, 2, cout] per-channel sums of y for the BatchNorm that follows (``gga_sparse_conv_apply_stats``).
-    ``bank``: ``w_kio`` is a VIEW ([kvol, cin, cout] or [k, k, cin, cout], any strides) of a parameter that lives across
-    steps - its operand and absmax then come from the weight bank (refreshed with all others once per optimizer step)
-    instead of a pack + absmax launch per call."""
-    L = _lib.lib()
-    kvol, cin, cout = (w_kio.shape[0] * w_kio.shape[1], w_kio.shape[2], w_kio.shape[3]) if w_kio.dim() == 4 else w_kio.shape
-    planes = _planes()
-    if planes == 2:
-        x_amax = _amax(x_rows) if x_amax is None else x_amax
-        if not bank:
-            w_amax = _amax(w_kio) if w_amax is None else w_amax
-        else:
-            from . import dense_conv
-            if dense_conv.RANGE_GUARD.armed:
-                dense_conv.RANGE_GUARD.record(w_kio.detach())
-    else:
-        x_amax = w_amax = None
-    y = torch.empty((n_rows, cout), dtype=torch.float32, device=x_rows.device)
-    tiles = int(L.gga_sparse_conv_apply_tiles(n_rows)) if want_stats else 0
-    parts = []
-    for c0 in range(0, cout, 128):
-        c1 = min(c0 + 128, cout)
-        if bank:
-            from . import weight_bank
-            wp, w_amax = weight_bank.gather_operand(w_kio, planes, c0, c1)
-        else:
-            wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, c1 - c0) // 2, dtype=torch.int16, device=y.device)
-            check(L.gga_sparse_pack_weight_planes(F._p(w_kio[:, :, c0:c1].contiguous()), kvol, cin, c1 - c0, 0, planes, F._p(w_amax),
-                                                  F._p(wp), F._stream()), 'gga_sparse_pack_weight_planes')
-        st = torch.empty((tiles, 2, c1 - c0), dtype=torch.float64, device=y.device) if want_stats else None
-        check(L.gga_sparse_conv_apply_stats(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin,
-                                            c1 - c0, 0, y.data_ptr() + 4 * c0, cout, planes, F._p(x_amax), F._p(w_amax),
-                                            F._p(st), F._stream()), 'gga_sparse_conv_apply_stats')
-        if want_stats:
-            parts.append(st)
-    if want_stats:
-        return y, (parts[0] if len(parts) == 1 else torch.cat(parts, dim=2))
-    return y
-
-
-def _wgrad(x_rows, g_rows, m, n_rows, x_amax=None, g_amax=None):
-    """gw [kvol, cin, cout] = sum over rows of x_rows[m[k][row]]^T g_rows[row] (deterministic)."""
-    planes = _planes()
-    if planes == 2:
-        x_amax = _amax(x_rows) if x_amax is None else x_amax
-        g_amax = _amax(g_rows) if g_amax is None else g_amax
-    else:
-        x_amax = g_amax = None
-    L = _lib.lib()
-    kvol, cin, cout = m.shape[0], x_rows.shape[1], g_rows.shape[1]
-    gw = torch.empty((kvol, cin, cout), dtype=torch.float32, device=x_rows.device)
-    for i0 in range(0, cin, 128):
-        i1 = min(i0 + 128, cin)
-        for o0 in range(0, cout, 128):
-            o1 = min(o0 + 128, cout)
-            whole = i1 - i0 == cin and o1 - o0 == cout
-            part = gw if whole else torch.empty((kvol, i1 - i0, o1 - o0), dtype=torch.float32, device=gw.device)
-            ws = F._workspace('sp_wgrad', L.gga_sparse_conv_wgrad_workspace_bytes(n_rows, kvol, i1 - i0, o1 - o0), gw.device)
-            check(L.gga_sparse_conv_wgrad_planes(x_rows.data_ptr() + 4 * i0, cin, g_rows.data_ptr() + 4 * o0, cout, F._p(m),
-                                                 n_rows, kvol, i1 - i0, o1 - o0, F._p(part), planes, F._p(x_amax), F._p(g_amax),
-                                                 F._p(ws), ws.numel(), F._stream()), 'gga_sparse_conv_wgrad_planes')
-            if not whole:
-                gw[:, i0:i1, o0:o1] = part
-    return gw
-
-
 class _StridedConv(torch.autograd.Function):
     """Conv2d(k, stride s, padding p), weight [cout, cin, k, k]."""
 
@@ -185,8 +92,8 @@ class _StridedConv(torch.autograd.Function):
         B, cin, H, W = x.shape
         bk = book(B, H, W, k, s, p, x.device)
         w = weight.detach()
-        x_amax = _amax(x)
-        y, stats = _apply(_rows(x), bk.fwd, bk.fwd_mask, bk.fwd_perm, w.permute(2, 3, 1, 0), bk.n_out, x_amax, want_stats=True, bank=True)
+        x_amax = G.amax(x)
+        y, stats = G.apply(_rows(x), bk.fwd, w.permute(2, 3, 1, 0), bk.n_out, planes=G.planes(), x_amax=x_amax, want_stats=True, bank=True)
         ctx.save_for_backward(x, weight)
         ctx.geom, ctx.amax = (k, s, p), (x_amax, None)
         ctx.mark_non_differentiable(stats)
@@ -203,21 +110,21 @@ class _StridedConv(torch.autograd.Function):
         gy = gy.contiguous(memory_format=torch.channels_last)
         g_rows = _rows(gy)
         gx = gw = None
-        x_amax, w_amax = ctx.amax if _planes() == 2 else (None, None)
-        g_amax = _amax(gy)
+        x_amax, w_amax = ctx.amax if G.planes() == 2 else (None, None)
+        g_amax = G.amax(gy)
         if ctx.needs_input_grad[0]:
             w = weight.detach()
-            gx = _apply(g_rows, bk.bwd, bk.bwd_mask, bk.bwd_perm, w.permute(2, 3, 0, 1), bk.n_in, g_amax, bank=True)
+            gx = G.apply(g_rows, bk.bwd, w.permute(2, 3, 0, 1), bk.n_in, planes=G.planes(), x_amax=g_amax, bank=True)
             gx = gx.view(B, H, W, cin).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
-            gw = _wgrad(_rows(x), g_rows, bk.fwd, bk.n_out, x_amax, g_amax).view(k, k, cin, cout).permute(3, 2, 0, 1)
+            gw = G.wgrad(_rows(x), g_rows, bk.fwd.nbr, bk.n_out, planes=G.planes(), x_amax=x_amax, g_amax=g_amax).view(k, k, cin, cout).permute(3, 2, 0, 1)
         return gx, gw, None, None, None
 
 
 def _stream_form(cin, cout, s, backward):
     """The streaming kernels (csrc/deconv_stream.hip) take this transposed convolution: two-plane arithmetic, cout in
     128-column blocks, cin 64 / 128 / 256 (backward-data keeps a [64, cout] gradient tile in LDS: cout a power of two)."""
-    if not STREAM or _planes() != 2 or cin not in (64, 128, 256) or cout % 128 or not 1 <= s <= 4:
+    if not STREAM or G.planes() != 2 or cin not in (64, 128, 256) or cout % 128 or not 1 <= s <= 4:
         return False
     form = (s, 'bwd' if backward else 'fwd')
     return form not in STREAM_OFF and (not backward or cout in (128, 256, 512))
@@ -238,7 +145,7 @@ def _stream_fwd(x, weight, s, x_amax, want_stats=True):
     if dense_conv.RANGE_GUARD.armed:
         dense_conv.RANGE_GUARD.record(w_kio)
     ops = [weight_bank.gather_operand(w_kio, 2, c0, c0 + 128) for c0 in range(0, cout, 128)]
-    x_amax = _amax(x) if x_amax is None else x_amax
+    x_amax = G.amax(x) if x_amax is None else x_amax
     y = torch.empty((B, H * s, W * s, cout), dtype=torch.float32, device=x.device)
     tiles = int(L.gga_deconv_stream_tiles(B * H * W, cin, s))
     stats = torch.empty((tiles, 2, cout), dtype=torch.float64, device=x.device) if want_stats else None
@@ -258,7 +165,7 @@ def _stream_bwd(gy, weight, s, g_amax):
     if dense_conv.RANGE_GUARD.armed:
         dense_conv.RANGE_GUARD.record(w_koi)
     ops = [weight_bank.gather_operand(w_koi, 2, c0, min(c0 + 128, cin)) for c0 in range(0, cin, 128)]
-    g_amax = _amax(gy) if g_amax is None else g_amax
+    g_amax = G.amax(gy) if g_amax is None else g_amax
     gx = torch.empty((B, H, W, cin), dtype=torch.float32, device=gy.device)
     check(L.gga_deconv_stream_bwd(F._p(_rows(gy)), _block_pointers([op for op, _ in ops]), F._p(g_amax), F._p(ops[0][1]), B, H, W,
                                   cin, cout, s, F._p(gx), F._stream()), 'gga_deconv_stream_bwd')
@@ -274,7 +181,7 @@ class _Deconv(torch.autograd.Function):
     def forward(ctx, x, weight, s):
         B, cin, H, W = x.shape
         w = weight.detach()
-        x_amax = _amax(x)
+        x_amax = G.amax(x)
         if _stream_form(cin, weight.shape[1], s, False):
             y, stats = _stream_fwd(x, weight, s, x_amax)
             ctx.save_for_backward(x, weight)
@@ -283,7 +190,7 @@ class _Deconv(torch.autograd.Function):
             ctx.set_materialize_grads(False)
             return y.permute(0, 3, 1, 2), stats
         bk = book(B, H * s, W * s, s, s, 0, x.device)          # fwd [s*s, n_coarse] fine pixel; bwd [s*s, n_fine] coarse pixel
-        y, stats = _apply(_rows(x), bk.bwd, bk.bwd_mask, bk.bwd_perm, w.permute(2, 3, 0, 1), bk.n_in, x_amax, want_stats=True, bank=True)
+        y, stats = G.apply(_rows(x), bk.bwd, w.permute(2, 3, 0, 1), bk.n_in, planes=G.planes(), x_amax=x_amax, want_stats=True, bank=True)
         ctx.save_for_backward(x, weight)
         ctx.s, ctx.amax = s, (x_amax, None)
         ctx.mark_non_differentiable(stats)
@@ -299,8 +206,8 @@ class _Deconv(torch.autograd.Function):
         gy = gy.contiguous(memory_format=torch.channels_last)
         g_rows = _rows(gy)
         gx = gw = None
-        x_amax, w_amax = ctx.amax if _planes() == 2 else (None, None)
-        g_amax = _amax(gy)
+        x_amax, w_amax = ctx.amax if G.planes() == 2 else (None, None)
+        g_amax = G.amax(gy)
         stream = _stream_form(cin, cout, s, True)
         if not stream or ctx.needs_input_grad[1]:
             bk = book(B, H * s, W * s, s, s, 0, x.device)
@@ -309,10 +216,10 @@ class _Deconv(torch.autograd.Function):
                 gx = _stream_bwd(gy, weight, s, g_amax).permute(0, 3, 1, 2)
             else:
                 w = weight.detach()
-                gx = _apply(g_rows, bk.fwd, bk.fwd_mask, bk.fwd_perm, w.permute(2, 3, 1, 0), bk.n_out, g_amax, bank=True)
+                gx = G.apply(g_rows, bk.fwd, w.permute(2, 3, 1, 0), bk.n_out, planes=G.planes(), x_amax=g_amax, bank=True)
                 gx = gx.view(B, H, W, cin).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:      # [k][cout][cin] = sum over coarse rows of gy[fine(k, row)]^T x[row]
-            gw = _wgrad(g_rows, _rows(x), bk.fwd, bk.n_out, g_amax, x_amax).view(s, s, cout, cin).permute(3, 2, 0, 1)
+            gw = G.wgrad(g_rows, _rows(x), bk.fwd.nbr, bk.n_out, planes=G.planes(), x_amax=g_amax, g_amax=x_amax).view(s, s, cout, cin).permute(3, 2, 0, 1)
         return gx, gw, None
 
 

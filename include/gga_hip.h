@@ -51,7 +51,7 @@ int gga_abi_version(void);
 enum {
     GGA_TIME_SCATTER_FWD = 0,   /* gga_pillar_scatter_fwd: NHWC fill [+ map] + rows, NCHW canvas kernel */
     GGA_TIME_DENSE_CONV = 1,    /* gga_dense_conv3x3_bn_bwd: key = GGA_TIMING_CONV_KEY(cin, cout, H*W) */
-    GGA_TIME_SPARSE_CONV = 2,   /* gga_sparse_conv_apply_stats / _bn_bwd: key = GGA_TIMING_CONV_KEY(cin, cout, 0); gga_sparse_conv_apply_halo: (cin, cout, kvol) */
+    GGA_TIME_SPARSE_CONV = 2,   /* gga_sparse_conv_apply_bn_bwd: key = GGA_TIMING_CONV_KEY(cin, cout, 0); gga_sparse_conv_apply_halo: (cin, cout, kvol) */
     GGA_TIME_SPARSE_WGRAD = 3,  /* gga_sparse_conv_wgrad_planes: key = GGA_TIMING_CONV_KEY(cin, cout, 0) */
     GGA_TIME_DENSE_WGRAD = 4,   /* gga_dense_wgrad3x3_block_amax: key as GGA_TIME_DENSE_CONV */
     GGA_TIME_SITES = 5
@@ -299,7 +299,7 @@ int gga_sparse_bev_nhwc_bwd(const float* grad_out, const int32_t* coors, int64_t
  * backward of the first SECOND convolution (second.py:49-57 applied to the canvas of
  * pillar_scatter.py:58-102) runs on the pillars only: its input gradient is needed just at the
  * occupied cells (all the scatter's backward reads) and its weight gradient only sees non-zero
- * input there - gga_sparse_conv_apply_stats / gga_sparse_conv_wgrad_planes with this map, the
+ * input there - gga_sparse_conv_apply_bn_bwd / gga_sparse_conv_wgrad_planes with this map, the
  * output gradient as `x` (rows = output cells) and the pillar features as the other operand. */
 int gga_pillar_conv_map(const int32_t* coors, int64_t m, const int32_t* num_valid, int batch, int ny, int nx,
                         int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int32_t* map,
@@ -347,7 +347,7 @@ int gga_sparse_rulebook(const int32_t* out_coors, int64_t n_out, const int32_t* 
  * tiles whose rows use the same kernel offsets; the conv kernel skips the others. */
 int gga_sparse_rowmask(const int32_t* map, int64_t n_rows, int kvol, uint32_t* mask, void* stream);
 /* order[i] = the row with the i-th smallest mask, rows with equal masks in row order (a stable sort of the int32 masks: the
- * processing order gga_sparse_conv_apply_stats takes as `perm`; replaces the framework's stable sort, sparse.py). kvol <= 32
+ * processing order gga_sparse_conv_apply_bn_bwd takes as `perm`; replaces the framework's stable sort, gather_gemm.py). kvol <= 32
  * mask bits take part; masks are compared as signed 32-bit values when kvol == 32. workspace: device memory of
  * gga_sparse_mask_order_workspace_bytes(n_rows) bytes. */
 /* order[i] = the row with the i-th smallest Z-order key (sample, then the bit-interleaved (z, y, x)) of coors [n_rows][4] =
@@ -367,7 +367,7 @@ int gga_sparse_mask_order(const uint32_t* mask, int64_t n_rows, int kvol, int32_
  * gfx950; error vs float64 not larger than the fp32 MFMA's). The kernels issue six of the nine: the
  * three products of the low planes are together below 2^-23 of the product (one fp32 ulp) and the
  * measured error of a convolution does not change; build with -DX9_NINE for all nine. Two fp16 planes (planes = 2):
- * see gga_absmax_bits below. The entry points (gga_sparse_pack_weight_planes, gga_sparse_conv_apply_stats / _bn_bwd,
+ * see gga_absmax_bits below. The entry points (gga_sparse_pack_weight_planes, gga_sparse_conv_apply_bn_bwd,
  * gga_sparse_conv_wgrad_planes) are declared there, next to the dense kernels that share the arithmetic.
  * gga_sparse_split_weight_bytes: size of a packed weight operand, packed[k][chunk][plane][col][32 ch] 16-bit elements,
  * zero beyond cin / cout (sized for three planes whatever `planes` the packing call is given; cout <= 128, else 0).
@@ -449,14 +449,11 @@ int gga_sparse_pack_weight_planes(const float* weight, int kvol, int cin, int co
  * [gga_sparse_conv_apply_tiles(n_rows)][2][cout] f64 = per workgroup of 128 rows the sum and the sum of squares - the
  * partials gga_bn_relu_fwd takes. */
 int64_t gga_sparse_conv_apply_tiles(int64_t n_rows);
-int gga_sparse_conv_apply_stats(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
-                                const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip, float* y,
-                                int64_t y_row_stride, int planes, const uint32_t* amax_x, const uint32_t* amax_weight,
-                                double* stats, void* stream);
-/* gga_sparse_conv_apply_stats run as the backward-data pass that produces the gradient of z = relu(bn(bn_x)) (the
- * conv -> BatchNorm1d -> ReLU -> conv chains of middle_encoders/sparse_encoder.py:107-214): rows are masked by the ReLU
- * (recomputed from bn_x [n_rows, row stride bn_x_row_stride] and gamma, beta, mean, invstd exactly as the forward decided)
- * before they are stored, and stats (required) holds the sums of g and g * xhat for gga_bn_relu_bwd_partials. */
+/* With bn_x (NULL: none of this, the other bn_* arguments are ignored) the launch is the backward-data pass that produces the
+ * gradient of z = relu(bn(bn_x)) (the conv -> BatchNorm1d -> ReLU -> conv chains of middle_encoders/sparse_encoder.py:107-214):
+ * rows are masked by the ReLU (recomputed from bn_x [n_rows, row stride bn_x_row_stride] and gamma, beta, mean, invstd exactly
+ * as the forward decided) before they are stored, and stats (required) holds the sums of g and g * xhat for
+ * gga_bn_relu_bwd_partials. */
 int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, const void* split_weight, const int32_t* perm,
                                  const uint32_t* rowmask, int64_t n_rows, int kvol, int cin, int cout, int flip, float* y,
                                  int64_t y_row_stride, int planes, const uint32_t* amax_x, const uint32_t* amax_weight,
@@ -466,7 +463,7 @@ int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, const void*
  * middle_encoders/sparse_encoder.py:107-214 / ops/sparse_block.py:117-199; same arithmetic and epilogues). The rows are
  * processed in tiles of gga_sparse_halo_tile_rows() (256) rows that lie close together in space; the distinct input rows a
  * tile's kvol x 256 rule-book entries name (its halo) are staged once per 32-channel chunk in LDS and every offset reads
- * them there. gga_sparse_halo_build makes the tiling from the rule book and a spatial order of its rows (gga_amd/sparse.py::
+ * them there. gga_sparse_halo_build makes the tiling from the rule book and a spatial order of its rows (gga_amd/gather_gemm.py::
  * _Halo: Z-order of the level's coordinates):
  *   tile_rows    int32 [n_tiles * 256]         output row (= row of the rule book) of each tile slot, -1 = empty slot
  *   halo_rows    int32 [n_tiles][capacity]     tile t's halo: its first halo_counts[t] entries, distinct input rows
@@ -474,7 +471,7 @@ int gga_sparse_conv_apply_bn_bwd(const float* x, const int32_t* map, const void*
  *   local_map    uint16 [n_tiles][kvol][256]   position of the neighbour in the tile's halo, 0xFFFF = none; offset k of a
  *                                              flipped (backward-data) launch reads entry kvol-1-k
  * n_tiles = ceil(n_rows / 256); capacity >= kvol * 256 (no tile can overflow); apply: 8 <= kvol <= 27; cin % 32 == 0; cout 64
- * or 128; two fp16 planes only (planes == 2). stats (may be NULL) is sized as for gga_sparse_conv_apply_stats
+ * or 128; two fp16 planes only (planes == 2). stats (may be NULL) is sized as for gga_sparse_conv_apply_bn_bwd
  * ([gga_sparse_conv_apply_tiles(n_rows)][2][cout]); the rows no tile writes are zeroed. */
 int64_t gga_sparse_halo_tile_rows(void);
 int gga_sparse_halo_build(const int32_t* nbr, const int32_t* tile_rows, int64_t n_rows, int64_t n_tiles, int kvol,
@@ -505,7 +502,7 @@ int gga_sparse_conv_wgrad_planes(const float* x, int64_t x_row_stride, const flo
 /* The kernel = stride transposed convolution of SECONDFPN (necks/second_fpn.py:52-69; s = 1: the 1x1 product) as a streaming
  * GEMM over the coarse pixels - no rule book, mask or permutation: every address is arithmetic on the pixel index
  * (csrc/deconv_stream.hip). Two fp16 planes only, fp32 in and out; y and gx are bit for bit what the gather-GEMM over the
- * arithmetic rule book gives (gga_sparse_conv_apply_stats, gga_amd/strided_conv.py).
+ * arithmetic rule book gives (gga_sparse_conv_apply_bn_bwd, gga_amd/strided_conv.py).
  *   forward        x [B*h*w, cin] -> y [B, s*h, s*w, cout] channels-last (every element written exactly once);
  *                  stats (NULL: none) [gga_deconv_stream_tiles(B*h*w, cin, s)][2][cout] f64: sum and sum of squares per
  *                  (tap, pixel tile) - the partials gga_bn_relu_fwd takes; fp32 inside a 32-pixel block, as the gather kernel.
@@ -623,7 +620,7 @@ int gga_bn_stats(const float* x, const float* gamma, const float* beta, float* r
  * (necks/second_fpn.py:85-91: torch.cat of the deblock outputs) - no concat copy, no split copy.
  * partials != NULL: training-mode statistics from per-channel sums already reduced by the producer of x: partials
  * [n_partials][2][channels] f64 (sum, sum of squares over disjoint row sets that together cover all `rows`), e.g. the `stats`
- * of gga_dense_conv3x3_bn_bwd or gga_sparse_conv_apply_stats; the reduce pass over x is skipped.
+ * of gga_dense_conv3x3_bn_bwd or gga_sparse_conv_apply_bn_bwd; the reduce pass over x is skipped.
  * Backward (batch statistics): grad_x, optional grad_residual (= masked grad_y), grad_gamma/beta; grad_y strided like y.
  * relu: 0 none, 1 mask_bits = the bits written by the forward, 2 mask_bits = scale_shift of
  * gga_bn_stats (mask recomputed from x). training = 0 is the backward of an evaluation-mode forward (running statistics,

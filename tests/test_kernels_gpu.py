@@ -986,7 +986,7 @@ def test_dense_conv_leaves_batchnorm_partials(cin, cout, B, H, W):
 @pytest.mark.parametrize('kind,cin,cout,k,s,B,H,W', [('conv', 64, 128, 3, 2, 2, 37, 45), ('conv', 128, 256, 3, 2, 2, 24, 30),
                                                       ('deconv', 128, 128, 2, 2, 2, 19, 23), ('deconv', 64, 128, 1, 1, 2, 37, 45)])
 def test_gather_convs_leave_batchnorm_partials(kind, cin, cout, k, s, B, H, W):
-    """The strided / transposed convolutions (gather-GEMM kernel, gga_sparse_conv_apply_stats) hand the BatchNorm that
+    """The strided / transposed convolutions (gather-GEMM kernel, gga_sparse_conv_apply_bn_bwd) hand the BatchNorm that
     follows the per-channel sums of their output: equal to the reductions of y, and the BatchNorm fed with them equals the
     BatchNorm that reduces y itself."""
     import copy

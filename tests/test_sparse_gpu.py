@@ -291,7 +291,7 @@ def test_sparse_encoder_full_grid_vs_pair_list_reference(planes, monkeypatch):
 
 def test_sparse_conv_leaves_batchnorm_partials():
     """A sparse convolution hands the BatchNorm1d that follows the per-channel sums of its output features
-    (gga_sparse_conv_apply_stats): they equal the column sums, and bn_act with them equals bn_act without."""
+    (gga_sparse_conv_apply_bn_bwd): they equal the column sums, and bn_act with them equals bn_act without."""
     import copy
     from gga_amd import functional as F, sparse
     torch.manual_seed(5)
@@ -452,11 +452,11 @@ def test_halo_form_of_the_submanifold_convolution(mid, monkeypatch):
 ])
 @pytest.mark.parametrize('flip', [0, 1])
 def test_halo_entry_point_against_the_default_kernel(case, flip):
-    """gga_sparse_halo_build + gga_sparse_conv_apply_halo called directly (C ABI) against gga_sparse_conv_apply_stats on the same
+    """gga_sparse_halo_build + gga_sparse_conv_apply_halo called directly (C ABI) against gga_sparse_conv_apply_bn_bwd on the same
     rule book, weights and absmax slots: output rows and the BatchNorm sums, forward (flip 0) and backward-data (flip 1) order of
     the offsets - channel chunk counts 1 / 2 / 3 / 4, 9 and 27 offsets, dense and nearly empty levels, a level smaller than a tile."""
     from gga_amd import _lib, dense_conv, functional as F
-    from gga_amd.sparse import _Level, _pack_weight, _Halo
+    from gga_amd.sparse import _Level, _Halo
     torch.manual_seed(3)
     dev, L = DEV, _lib.lib()
     B, shape = case['B'], case['shape']
@@ -471,13 +471,15 @@ def test_halo_entry_point_against_the_default_kernel(case, flip):
     x = torch.randn(n, cin, device=dev)
     w = torch.randn(kvol, cin, cout, device=dev) * 0.1
     x_amax, w_amax = dense_conv._amax_bits(x), dense_conv._amax_bits(w)
-    wp = _pack_weight(w, kvol, cin, cout, 0, w_amax=w_amax)
+    wp = torch.empty(L.gga_sparse_split_weight_bytes(kvol, cin, cout) // 2, dtype=torch.int16, device=dev)
+    _lib.check(L.gga_sparse_pack_weight_planes(F._p(w), kvol, cin, cout, 0, 2, F._p(w_amax), F._p(wp), F._stream()), 'pack')
     tiles = int(L.gga_sparse_conv_apply_tiles(n))
     y0, y1 = torch.empty(n, cout, device=dev), torch.full((n, cout), float('nan'), device=dev)
     s0 = torch.empty((tiles, 2, cout), dtype=torch.float64, device=dev)
     s1 = torch.full_like(s0, float('nan'))
-    _lib.check(L.gga_sparse_conv_apply_stats(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n, kvol, cin, cout, flip,
-                                             F._p(y0), cout, 2, F._p(x_amax), F._p(w_amax), F._p(s0), F._stream()), 'default kernel')
+    _lib.check(L.gga_sparse_conv_apply_bn_bwd(F._p(x), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), n, kvol, cin, cout, flip,
+                                              F._p(y0), cout, 2, F._p(x_amax), F._p(w_amax), F._p(s0), None, 0, None, None, None, None,
+                                              F._stream()), 'default kernel')
     _lib.check(L.gga_sparse_conv_apply_halo(F._p(x), F._p(wp), F._p(halo.tile_rows), F._p(halo.counts), halo.capacity, F._p(halo.halo_rows),
                                             F._p(halo.local_map), n, halo.n_tiles, kvol, cin, cout, flip, F._p(y1), cout, 2, F._p(x_amax),
                                             F._p(w_amax), F._p(s1), None, 0, None, None, None, None, F._stream()), 'halo form')

@@ -4,7 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import torch
 from gga_amd import _lib, functional as F
-from gga_amd.sparse import _pack_weight
+from gga_amd.gather_gemm import _pack
 
 dev = 'cuda:0'
 torch.backends.cudnn.benchmark = False

@@ -43,15 +43,15 @@ with torch.no_grad():
         u128, u32 = unions(ms, 128), unions(ms, 32)
         w = torch.randn(27, C_, C_, device=DEV) * 0.05
         y = torch.empty(lv.n, C_, device=DEV)
-        from gga_amd.sparse import _pack_weight
+        from gga_amd.gather_gemm import _pack
         feats = x.features.contiguous()
         fl = lambda k: 2.0 * lv.n * k * C_ * C_
-        wps = _pack_weight(w, 27, C_, C_, 0)
-        t_x9 = timeit(lambda: L.gga_sparse_conv_apply_stats(F._p(feats), F._p(rb.nbr), F._p(wps), F._p(rb.perm), F._p(rb.mask), lv.n, 27, C_, C_, 0, F._p(y), C_, 3, None, None, None, F._stream()))
+        wps = _pack(w, 0, C_, 3, None)
+        t_x9 = timeit(lambda: L.gga_sparse_conv_apply_bn_bwd(F._p(feats), F._p(rb.nbr), F._p(wps), F._p(rb.perm), F._p(rb.mask), lv.n, 27, C_, C_, 0, F._p(y), C_, 3, None, None, None, None, 0, None, None, None, None, F._stream()))
         for nsub in (16384, 65536):
             sel = rb.perm.long()[-nsub:]
             nbr_s = rb.nbr[:, sel].contiguous(); mask_s = rb.mask[sel].contiguous(); ys = torch.empty(nsub, C_, device=DEV)
-            t_s = timeit(lambda: L.gga_sparse_conv_apply_stats(F._p(feats), F._p(nbr_s), F._p(wps), None, F._p(mask_s), nsub, 27, C_, C_, 0, F._p(ys), C_, 3, None, None, None, F._stream()))
+            t_s = timeit(lambda: L.gga_sparse_conv_apply_bn_bwd(F._p(feats), F._p(nbr_s), F._p(wps), None, F._p(mask_s), nsub, 27, C_, C_, 0, F._p(ys), C_, 3, None, None, None, None, 0, None, None, None, None, F._stream()))
             pcs = float(sum(((mask_s.long() >> kb) & 1) for kb in range(27)).float().mean())
             print(f'   bf16x9 on the last {nsub} rows of the mask order ({nsub // 256} tiles, {pcs:.1f} offsets/row): {t_s:.0f} us')
         gw2 = torch.empty_like(w)

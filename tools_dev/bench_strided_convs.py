@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gga_amd import _lib
 from gga_amd import functional as F
-from gga_amd.sparse import _pack_weight
+from gga_amd.gather_gemm import _pack
 
 DEV = 'cuda:0'
 L = _lib.lib()
@@ -50,8 +50,8 @@ def mask_perm(m):
 
 def apply(x_rows, m, mask, perm, wp, n_rows, kvol, cin, cout):
     y = torch.empty((n_rows, cout), device=DEV)
-    rc = L.gga_sparse_conv_apply_stats(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin, cout, 0, F._p(y),
-                                       cout, 3, None, None, None, F._stream())
+    rc = L.gga_sparse_conv_apply_bn_bwd(F._p(x_rows), F._p(m), F._p(wp), F._p(perm), F._p(mask), n_rows, kvol, cin, cout, 0, F._p(y),
+                                       cout, 3, None, None, None, None, 0, None, None, None, None, F._stream())
     _lib.check(rc, 'proto')
     return y
 
@@ -79,8 +79,8 @@ def conv_case(B, cin, cout, H, W, k=3, s=2, p=1):
     bmask, bperm = mask_perm(bm)
     xr = x.permute(0, 2, 3, 1).reshape(n_in, cin)
     w = conv.weight.detach()
-    wf = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), k * k, cin, cout, 0)
-    wb = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), k * k, cout, cin, 0)
+    wf = _pack(w.permute(2, 3, 1, 0).reshape(k * k, cin, cout), 0, cout, 3, None)
+    wb = _pack(w.permute(2, 3, 0, 1).reshape(k * k, cout, cin), 0, cin, 3, None)
     y = apply(xr, fm, fmask, fperm, wf, n_out, k * k, cin, cout)
     gy = torch.randn(B, cout, Ho, Wo, device=DEV).contiguous(memory_format=torch.channels_last)
     gr = gy.permute(0, 2, 3, 1).reshape(n_out, cout)
@@ -116,8 +116,8 @@ def deconv_case(B, cin, cout, H, W, s):
     bmask, bperm = mask_perm(bm)
     fmask, fperm = mask_perm(fm)
     w = dec.weight.detach()                                # [cin, cout, s, s]
-    wf = _pack_weight(w.permute(2, 3, 0, 1).contiguous(), s * s, cin, cout, 0)
-    wb = _pack_weight(w.permute(2, 3, 1, 0).contiguous(), s * s, cout, cin, 0)
+    wf = _pack(w.permute(2, 3, 0, 1).reshape(s * s, cin, cout), 0, cout, 3, None)
+    wb = _pack(w.permute(2, 3, 1, 0).reshape(s * s, cout, cin), 0, cin, 3, None)
     xr = x.permute(0, 2, 3, 1).reshape(n_lo, cin)
     y = apply(xr, bm, bmask, bperm, wf, n_hi, s * s, cin, cout)
     gy = torch.randn(B, cout, Ho, Wo, device=DEV).contiguous(memory_format=torch.channels_last)

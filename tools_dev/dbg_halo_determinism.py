@@ -5,7 +5,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 import torch
 from gga_amd import Config, build_model, synthetic, _lib, dense_conv
 from gga_amd import functional as F
-from gga_amd.sparse import SparseConvTensor, _Halo, _pack_weight
+from gga_amd.gather_gemm import _Halo, _pack
+from gga_amd.sparse import SparseConvTensor
 DEV = 'cuda:0'
 BS = 8
 dense_conv.PLANES = 2
@@ -59,7 +60,7 @@ for rep in range(12):
         print('  tiling differs under concurrency, repeat', rep)
 print('tiling repeated under concurrency')
 for flip in (0, 1):
-    wp = _pack_weight(w, 27, C_, C_, flip, w_amax=w_amax)
+    wp = _pack(w.transpose(1, 2) if flip else w, 0, C_, 2, w_amax)
     ref = None
     bad = 0
     for it in range(40):

@@ -4,7 +4,7 @@ import copy, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
 import torch
-from gga_amd import dense_conv, sparse
+from gga_amd import dense_conv, gather_gemm, sparse
 from gga_amd.sparse_encoder import SparseEncoder
 from test_sparse_gpu import _coords
 DEV = 'cuda:0'
@@ -45,27 +45,28 @@ for n in f2:
 # ---- finer: every backward-data result, cloned right after the launch and again after the weight gradient of the same call
 print('per-call backward-data results (3 planes vs 2 planes)')
 calls = {}
-orig_apply, orig_wgrad = sparse._conv_apply, sparse.conv_wgrad
+orig_apply, orig_wgrad = gather_gemm.apply, gather_gemm.wgrad
 for planes in (2, 3):
     dense_conv.PLANES = planes
     log = calls[planes] = []
     state = {}
-    def conv_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, *a, **k):
-        r = orig_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, *a, **k)
-        state['last'] = (y, y.detach().clone(), (n_rows, kvol, cin, cout, flip))
+    def apply_spy(x, rb, w, n_rows, **k):
+        r = orig_apply(x, rb, w, n_rows, **k)
+        y = r[0] if isinstance(r, tuple) else r
+        state['last'] = (y, y.detach().clone(), (n_rows, *w.shape, k.get('flip', 0)))
         return r
-    def conv_wgrad(x, gy, nbr, n_rows, kvol, cin, cout, gw, *a, **k):
-        r = orig_wgrad(x, gy, nbr, n_rows, kvol, cin, cout, gw, *a, **k)
+    def wgrad_spy(x, gy, nbr, n_rows, **k):
+        r = gw = orig_wgrad(x, gy, nbr, n_rows, **k)
         torch.cuda.synchronize()
         y, before, sig = state['last']
         log.append((sig, before, y.detach().clone(), gw.detach().clone()))
         return r
-    sparse._conv_apply, sparse.conv_wgrad = conv_apply, conv_wgrad
+    gather_gemm.apply, gather_gemm.wgrad = apply_spy, wgrad_spy
     e = copy.deepcopy(enc).to(DEV)
     y = e(feats.to(DEV), coors.to(DEV), B)
     log.clear()
     y.backward(g)
-sparse._conv_apply, sparse.conv_wgrad = orig_apply, orig_wgrad
+gather_gemm.apply, gather_gemm.wgrad = orig_apply, orig_wgrad
 for (s2, b2, a2, w2), (s3, b3, a3, w3) in zip(calls[2], calls[3]):
     d = lambda u, v: float((u - v).norm() / (v.norm() + 1e-30))
     print(f'{str(s2):32s} gx right after launch: 3 vs 2 planes {d(b3, b2):.2e}; after wgrad vs before (2 planes) {d(a2, b2):.2e} (3 planes) {d(a3, b3):.2e}; gw 3 vs 2 {d(w3, w2):.2e}')

@@ -2,7 +2,7 @@ import copy, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
 import torch
-from gga_amd import dense_conv, sparse
+from gga_amd import dense_conv, gather_gemm, sparse
 from gga_amd.sparse_encoder import SparseEncoder
 from test_sparse_gpu import _coords
 DEV = 'cuda:0'
@@ -14,20 +14,21 @@ enc = SparseEncoder(in_channels=4, sparse_shape=list(shape), output_channels=128
 enc.train()
 coors = _coords(B, shape, 900, seed=5)
 feats = torch.randn(len(coors), 4)
-orig_apply = sparse._conv_apply
+orig_apply = gather_gemm.apply
 captured = []
-def conv_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, x_amax=None, w_amax=None, stats=None, bn=None):
+def apply_spy(x, rb, w, n_rows, *, flip=0, want_stats=False, bn=None, **k):
     if flip == 1 or (x.requires_grad is False and len(captured) < 100):
-        captured.append(dict(x=x.detach().clone(), rb=rb, n_rows=n_rows, kvol=kvol, cin=cin, cout=cout, flip=flip, bn=bn, had_stats=stats is not None))
-    return orig_apply(x, rb, wp, n_rows, kvol, cin, cout, flip, y, x_amax, w_amax, stats, bn)
+        kvol, cin, cout = w.shape
+        captured.append(dict(x=x.detach().clone(), rb=rb, n_rows=n_rows, kvol=kvol, cin=cin, cout=cout, flip=flip, bn=bn, had_stats=want_stats))
+    return orig_apply(x, rb, w, n_rows, flip=flip, want_stats=want_stats, bn=bn, **k)
 dense_conv.PLANES = 3
 e = copy.deepcopy(enc).to(DEV)
 y = e(feats.to(DEV), coors.to(DEV), B)
 captured.clear()
-sparse._conv_apply = conv_apply
+gather_gemm.apply = apply_spy
 torch.manual_seed(1)
 y.backward(torch.randn_like(y))
-sparse._conv_apply = orig_apply
+gather_gemm.apply = orig_apply
 ws = [m.weight for m in e.modules() if isinstance(m, sparse.SparseConvolution)][::-1]
 print(len(captured), 'backward-data calls')
 for i, c in enumerate(captured):
@@ -49,13 +50,13 @@ for i, c in enumerate(captured):
         two = planes == 2
         g_amax = dense_conv._amax_bits(gy) if two else None
         w_amax = dense_conv._amax_bits(w.contiguous()) if two else None
-        wt = sparse._pack_weight(w.contiguous(), K, c['cin'], c['cout'], 1, w_amax=w_amax)
+        wt = w.contiguous().transpose(1, 2)           # W[k]^T
         for use_bn in (False, True):
             if use_bn and c['bn'] is None:
                 continue
             gx = torch.full((c['n_rows'], c['cout']), float('nan'), device=DEV)
-            st = torch.empty((int(sparse._lib.lib().gga_sparse_conv_apply_tiles(c['n_rows'])), 2, c['cout']), dtype=torch.float64, device=DEV)
-            orig_apply(gy, rb, wt, c['n_rows'], K, c['cin'], c['cout'], 1, gx, g_amax, w_amax, st, c['bn'] if use_bn else None)
+            orig_apply(gy, rb, wt, c['n_rows'], planes=planes, x_amax=g_amax, w_amax=w_amax, flip=1, want_stats=True,
+                       bn=c['bn'] if use_bn else None, out=gx)
             outs[(planes, use_bn)] = gx
     d = lambda u, v: float((u.double() - v.double()).norm() / v.double().norm())
     line = f'call {i}: bn given {c["bn"] is not None} |'

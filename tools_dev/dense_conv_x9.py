@@ -10,7 +10,7 @@ TFLOP/s at C=64, 113 vs 111 at C=128, results equal to 2e-6), so the product kee
 import torch
 
 from gga_amd import functional as F
-from gga_amd import sparse as S
+from gga_amd import gather_gemm as G
 
 _MAPS = {}
 
@@ -22,7 +22,7 @@ class _DenseRulebook:
         rows = torch.arange(B * H * W, dtype=torch.int32, device=device).view(B, H, W)
         pad = torch.nn.functional.pad(rows, (1, 1, 1, 1), value=-1)
         self.nbr = torch.stack([pad[:, ky:ky + H, kx:kx + W].reshape(-1) for ky in range(3) for kx in range(3)]).contiguous()
-        self.perm = self.mask = None            # every row uses every offset: nothing to sort or skip
+        self.perm = self.mask = self.coors = None       # every row uses every offset: nothing to sort or skip
 
 
 def _rulebook(B, H, W, device):
@@ -44,8 +44,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         xr = xr.reshape(-1, cin)
         w = weight.detach().permute(2, 3, 1, 0).reshape(9, cin, cout).contiguous()     # [k][ci][co]
         rb = _rulebook(B, H, W, x.device)
-        y = torch.empty((B * H * W, cout), dtype=torch.float32, device=x.device)
-        S._conv_apply(xr, rb, S._pack_weight(w, 9, cin, cout, 0), B * H * W, 9, cin, cout, 0, y)
+        y = G.apply(xr, rb, w, B * H * W, planes=3)
         ctx.save_for_backward(x, weight)
         return y.view(B, H, W, cout).permute(0, 3, 1, 2)
 
@@ -59,10 +58,8 @@ class _Conv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             rb = _rulebook(B, H, W, x.device)
             w = weight.detach().permute(2, 3, 1, 0).reshape(9, cin, cout).contiguous()
-            g = torch.empty((B * H * W, cin), dtype=torch.float32, device=x.device)
             # transposed map of a stride-1 'same' convolution = reversed offsets (as for SubM)
-            S._conv_apply(gy.permute(0, 2, 3, 1).reshape(-1, cout), rb, S._pack_weight(w, 9, cout, cin, 1),
-                          B * H * W, 9, cout, cin, 1, g)
+            g = G.apply(gy.permute(0, 2, 3, 1).reshape(-1, cout), rb, w.transpose(1, 2), B * H * W, planes=3, flip=1)
             gx = g.view(B, H, W, cin).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             gw = torch.ops.aten.convolution_backward(gy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,

@@ -5,7 +5,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 import torch
 from gga_amd import Config, build_model, synthetic, _lib, dense_conv
 from gga_amd import functional as F
-from gga_amd.sparse import SparseConvTensor, _Halo, _pack_weight
+from gga_amd.gather_gemm import _Halo, _pack
+from gga_amd.sparse import SparseConvTensor
 DEV = 'cuda:0'
 BS = 8
 
@@ -63,13 +64,13 @@ for planes in (2,):
         x_amax = dense_conv._amax_bits(feats) if two else None
         w_amax = dense_conv._amax_bits(w) if two else None
         for flip in (0, 1):
-            wp = _pack_weight(w, 27, C_, C_, flip, w_amax=w_amax)
+            wp = _pack(w.transpose(1, 2) if flip else w, 0, C_, planes, w_amax)
             y0 = torch.empty(nrow, C_, device=DEV)
             y1 = torch.zeros(nrow, C_, device=DEV)
             st0 = torch.empty((int(L.gga_sparse_conv_apply_tiles(nrow)), 2, C_), dtype=torch.float64, device=DEV)
             st1 = torch.empty_like(st0)
-            f0 = lambda: L.gga_sparse_conv_apply_stats(F._p(feats), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), nrow, 27, C_, C_, flip,
-                                                       F._p(y0), C_, planes, F._p(x_amax), F._p(w_amax), F._p(st0), F._stream())
+            f0 = lambda: L.gga_sparse_conv_apply_bn_bwd(F._p(feats), F._p(rb.nbr), F._p(wp), F._p(rb.perm), F._p(rb.mask), nrow, 27, C_, C_, flip,
+                                                       F._p(y0), C_, planes, F._p(x_amax), F._p(w_amax), F._p(st0), None, 0, None, None, None, None, F._stream())
             f1 = lambda: L.gga_sparse_conv_apply_halo(F._p(feats), F._p(wp), F._p(halo.tile_rows), F._p(halo.counts), halo.capacity, F._p(halo.halo_rows),
                                                       F._p(halo.local_map), nrow, halo.n_tiles, 27, C_, C_, flip, F._p(y1), C_, planes,
                                                       F._p(x_amax), F._p(w_amax), F._p(st1), None, 0, None, None, None, None, F._stream())

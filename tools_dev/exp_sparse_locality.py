@@ -9,7 +9,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 import torch
 from gga_amd import Config, build_model, synthetic, _lib, dense_conv
 from gga_amd import functional as F
-from gga_amd.sparse import SparseConvTensor, _Level, _pack_weight
+from gga_amd.gather_gemm import _pack
+from gga_amd.sparse import SparseConvTensor, _Level
 DEV = 'cuda:0'
 BS = 8
 dense_conv.PLANES = 2
@@ -79,7 +80,7 @@ for li, (lvl, C_) in enumerate(levels):
         rb = lv.subm_rulebook((3, 3, 3))
         xs = feats[order].contiguous()
         x_amax, w_amax = dense_conv._amax_bits(xs), dense_conv._amax_bits(w)
-        wp = _pack_weight(w, 27, C_, C_, 0, w_amax=w_amax)
+        wp = _pack(w, 0, C_, 2, w_amax)
         y = torch.empty(nrow, C_, device=DEV)
         pairs = float((rb.nbr >= 0).sum()) / nrow
         for R in ((0,) if T is None else (-1,)) if os.environ.get('GGA_EXP_FEW') else (0, -1):
@@ -93,8 +94,8 @@ for li, (lvl, C_) in enumerate(levels):
                 k2 = (torch.arange(nrow, device=DEV) // R) * (1 << 32) + (rb.mask.long() & 0xFFFFFFFF)
                 perm = torch.argsort(k2, stable=True).int()
             ms = rb.mask[perm.long()] & 0x7FFFFFF
-            t_f = timeit(lambda: L.gga_sparse_conv_apply_stats(F._p(xs), F._p(rb.nbr), F._p(wp), F._p(perm), F._p(rb.mask), nrow, 27, C_, C_, 0,
-                                                              F._p(y), C_, 2, F._p(x_amax), F._p(w_amax), None, F._stream()))
+            t_f = timeit(lambda: L.gga_sparse_conv_apply_bn_bwd(F._p(xs), F._p(rb.nbr), F._p(wp), F._p(perm), F._p(rb.mask), nrow, 27, C_, C_, 0,
+                                                              F._p(y), C_, 2, F._p(x_amax), F._p(w_amax), None, None, 0, None, None, None, None, F._stream()))
             print(f'  {name} region {R:6d}: pairs/row {pairs:.2f} offsets per 128-row tile {unions(ms, 128):5.2f} per 256 {unions(ms, 256):5.2f} | forward {t_f:7.1f} us')
         gw = torch.empty_like(w)
         g = torch.randn(nrow, C_, device=DEV)

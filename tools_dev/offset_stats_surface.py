@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from gga_amd import Config, build_model, synthetic
-from gga_amd.sparse import morton_order
+from gga_amd.gather_gemm import morton_order
 
 DEV = 'cuda:0'
 BS = 8

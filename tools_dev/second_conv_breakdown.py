@@ -8,7 +8,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import torch
 import bench
-from gga_amd import _lib, sparse, strided_conv
+from gga_amd import _lib, gather_gemm
 
 which = sys.argv[1] if len(sys.argv) > 1 else 'second'
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else (8 if which == 'second' else 16)
@@ -21,17 +21,11 @@ def remember(t):
         maps[t.data_ptr()] = t
 
 
-o1 = sparse._Rulebook.__init__
-def init1(self, nbr):
-    o1(self, nbr)
+o1 = gather_gemm.Rulebook.__init__
+def init1(self, nbr, *a, **k):
+    o1(self, nbr, *a, **k)
     remember(self.nbr)
-sparse._Rulebook.__init__ = init1
-o2 = strided_conv._Book.__init__
-def init2(self, *a, **k):
-    o2(self, *a, **k)
-    for n in ('fwd', 'bwd'):
-        remember(getattr(self, n, None))
-strided_conv._Book.__init__ = init2
+gather_gemm.Rulebook.__init__ = init1        # (the arithmetic books of strided_conv are Rulebooks too)
 
 L = _lib.lib()
 records, active = [], [False]
@@ -65,7 +59,6 @@ def wrap(name, unpack):
 
 
 wrap('gga_sparse_conv_apply_bn_bwd', lambda a: dict(map=a[1], rows=a[5], kvol=a[6], cin=a[7], cout=a[8], flip=a[9], bn=bool(a[17])))
-wrap('gga_sparse_conv_apply_stats', lambda a: dict(map=a[1], rows=a[5], kvol=a[6], cin=a[7], cout=a[8], flip=a[9], bn=False))
 wrap('gga_sparse_conv_wgrad_planes', lambda a: dict(map=a[4], rows=a[5], kvol=a[6], cin=a[7], cout=a[8], flip=-1, bn=False))
 
 args = bench.parse_args(['--config', cfg_path, '--batch', str(batch), '--steps', '1', '--warmup', '3', '--no-cpu-baseline', '--no-roofline'])

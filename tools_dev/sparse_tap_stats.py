@@ -5,14 +5,14 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import torch
 import bench
-from gga_amd import sparse
+from gga_amd import gather_gemm
 
 seen = []
-orig = sparse._Rulebook.__init__
-def init(self, nbr):
-    orig(self, nbr)
+orig = gather_gemm.Rulebook.__init__
+def init(self, nbr, *a, **k):
+    orig(self, nbr, *a, **k)
     seen.append(self)
-sparse._Rulebook.__init__ = init
+gather_gemm.Rulebook.__init__ = init
 args = bench.parse_args(['--config', bench.SECOND_CONFIG, '--batch', '8', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-roofline'])
 r = bench.run_workload(bench.SECOND_CONFIG, 8, 1, 1, args, 0, 1, torch.device('cuda:0')) if hasattr(bench, 'run_workload') else None
 done = set()
