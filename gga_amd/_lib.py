@@ -62,6 +62,20 @@ class TtaTable(C.Structure):
                 ('hflip', C.c_int32 * TTA_MAX_VIEWS), ('vflip', C.c_int32 * TTA_MAX_VIEWS), ('map', TtaMap * TTA_MAX_MAPS)]
 
 
+MONO3D_TTA_MAX_MAPS = 48            # GGA_MONO3D_TTA_MAX_MAPS
+MONO3D_TTA_MEAN, MONO3D_TTA_REG = range(2)
+MONO3D_COLLECT_MAX_IMAGES = 4096    # GGA_MONO3D_COLLECT_MAX_IMAGES
+
+
+class Mono3dTtaMap(C.Structure):
+    _fields_ = [('src', vp), ('dst', vp), ('channels', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('kind', C.c_int32)]
+
+
+class Mono3dTtaTable(C.Structure):
+    """gga_mono3d_tta_table: one entry per (output group, FPN level) of the two-view head output."""
+    _fields_ = [('n_maps', C.c_int32), ('n_frames', C.c_int32), ('map', Mono3dTtaMap * MONO3D_TTA_MAX_MAPS)]
+
+
 IMAGE_BATCH_MAX = 64                # GGA_IMAGE_BATCH_MAX
 
 
@@ -205,6 +219,9 @@ SIGNATURES = {
     'gga_multiclass_nms3d_workspace_bytes': (sz, [i64, i32, i32]),
     'gga_multiclass_nms3d': (i32, [vp, vp, vp, i64, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
     'gga_tta_merge_maps': (i32, [C.POINTER(TtaTable), i32, i32, i32, vp]),
+    'gga_mono3d_tta_merge': (i32, [C.POINTER(Mono3dTtaTable), vp]),
+    'gga_mono3d_collect_workspace_bytes': (sz, [i64, i32, i32]),
+    'gga_mono3d_collect': (i32, [vp, vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'gga_points_in_boxes': (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     'gga_fcos3d_targets': (i32, [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), f32, vp, i32,
                                   vp, vp, vp, vp, i32, vp, vp, vp, i64, i64, f32, vp, vp, vp, vp, vp, vp, vp]),

@@ -1422,3 +1422,82 @@ def tta_merge_maps(outs, group, hflip, vflip, n_frames):
     tb.n_maps = n
     check(_lib.lib().gga_tta_merge_maps(C.byref(tb), F_, shape[0], shape[1], _stream()), 'gga_tta_merge_maps')
     return merged
+
+
+def mono3d_tta_merge(outs, n_frames):
+    """``gga_mono3d_tta_merge``: the mono3d head's output for a view-major two-view batch - the tuple ``(cls_scores, bbox_preds,
+    dir_cls_preds, depth_cls_preds, weights, attr_preds, centernesses)`` of per-level ``[2 F, C, H, W]`` maps, view 0 the
+    unflipped images, view 1 their horizontal mirrors - merged into ``[F, C, H, W]`` maps in one launch, with the bits of the
+    reference's flip / ``1 - x`` / mean sequence (single_stage_mono3d.py:141-181). The direction classifier keeps view 0 (a
+    slice); a group of ``None`` entries stays as it is."""
+    F_ = int(n_frames)
+    tb = _lib.Mono3dTtaTable()
+    tb.n_frames = F_
+    merged, keep, n = [], [], 0
+    for g, group in enumerate(outs):
+        if group[0] is None:
+            merged.append(list(group))
+            continue
+        new = []
+        for src in group:
+            _need_cuda(src)
+            if src.dtype != torch.float32 or src.dim() != 4 or src.shape[0] != 2 * F_:
+                raise ValueError(f'mono3d_tta_merge: group {g} must hold float32 [{2 * F_}, C, H, W] maps, got {src.dtype} {tuple(src.shape)}')
+            if g == 2:                            # dir_cls keeps the original
+                new.append(src[:F_])
+                continue
+            if g == 1 and src.shape[1] < 7:
+                raise ValueError(f'mono3d_tta_merge: a regression map of {src.shape[1]} channels (at least 7 expected)')
+            if n == _lib.MONO3D_TTA_MAX_MAPS:
+                raise ValueError(f'mono3d_tta_merge: more than {_lib.MONO3D_TTA_MAX_MAPS} maps')
+            src = src.contiguous()
+            dst = torch.empty((F_,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+            e = tb.map[n]
+            e.src, e.dst, e.channels, e.H, e.W = _p(src), _p(dst), src.shape[1], src.shape[2], src.shape[3]
+            e.kind = _lib.MONO3D_TTA_REG if g == 1 else _lib.MONO3D_TTA_MEAN
+            keep.append(src)
+            new.append(dst)
+            n += 1
+        merged.append(new)
+    if n:
+        tb.n_maps = n
+        check(_lib.lib().gga_mono3d_tta_merge(C.byref(tb), _stream()), 'gga_mono3d_tta_merge')
+    return tuple(merged)
+
+
+def mono3d_collect(rows, classes, count, scores, boxes, dir_scores, attr_scores, boxes2d, max_per_img):
+    """``gga_mono3d_collect``: the packed output of ``multiclass_nms3d`` (scene = image) -> one byte buffer on the device that
+    holds, for ``B = len(count)`` images, ``max_per_img`` slots of boxes [code], score, label, direction, attribute and 2D box
+    (when ``boxes2d`` is given) and the per-image counts; an image with more kept detections than ``max_per_img`` keeps its
+    highest scores in descending order. -> ``(buffer, views)``: ``views(host_buffer)`` cuts a (downloaded) copy of the buffer
+    into ``dict(boxes, scores, labels, dir, attr, boxes2d, count)``. Nothing is read back here."""
+    _need_cuda(rows, classes, count, scores, boxes)
+    B, (n, nc), code, M = int(count.shape[0]), scores.shape, int(boxes.shape[1]), int(max_per_img)
+    if boxes.shape[0] != n or rows.numel() < n * nc or classes.numel() < n * nc:
+        raise ValueError(f'mono3d_collect: scores {tuple(scores.shape)}, boxes {tuple(boxes.shape)}, lists of {rows.numel()} / {classes.numel()}')
+    dev = boxes.device
+    scores, boxes = scores.float().contiguous(), boxes.float().contiguous()
+    opt = lambda t, dt: None if t is None else t.to(dt).contiguous()
+    dir_scores, attr_scores, boxes2d = opt(dir_scores, torch.int64), opt(attr_scores, torch.int64), opt(boxes2d, torch.float32)
+    fields = [('boxes', torch.float32, (B, M, code)), ('scores', torch.float32, (B, M)), ('labels', torch.int32, (B, M)),
+              ('dir', torch.int32, (B, M)), ('attr', torch.int32, (B, M)), ('boxes2d', torch.float32, (B, M, 4)),
+              ('count', torch.int32, (B,))]
+    if boxes2d is None:
+        fields = [f for f in fields if f[0] != 'boxes2d']
+    where, at = {}, 0
+    for name, dt, shape in fields:
+        where[name] = (at, dt, shape)
+        at += -(-int(np.prod(shape)) * 4 // 16) * 16
+
+    def views(buf):
+        return {name: buf[o:o + int(np.prod(shape)) * 4].view(dt).reshape(shape) for name, (o, dt, shape) in where.items()}
+
+    out = torch.empty(at, dtype=torch.uint8, device=dev)
+    v = views(out)
+    L = _lib.lib()
+    ws = _workspace('mono3d_collect', L.gga_mono3d_collect_workspace_bytes(n, nc, B), dev)
+    check(L.gga_mono3d_collect(_p(rows), _p(classes), _p(count), B, n, nc, _p(scores), nc, _p(boxes), code,
+                               _p(dir_scores), _p(attr_scores), _p(boxes2d), M, _p(v['boxes']), _p(v['scores']), _p(v['labels']),
+                               _p(v['dir']), _p(v['attr']), _p(v.get('boxes2d')), _p(v['count']), _p(ws), ws.numel(), _stream()),
+          'gga_mono3d_collect')
+    return out, views

@@ -3,7 +3,7 @@ batch to the device.
 
 Transforms (mmdet 2.x semantics; mmdet's source is not part of the reference tree, the behaviour is restated here):
 ``LoadImageFromFileMono3D`` (mmdet3d/datasets/pipelines/loading.py:76-96), ``Resize`` (``keep_ratio=True`` with one
-``img_scale``), ``Normalize``, ``Pad`` (``size_divisor``), ``MultiScaleFlipAug`` (one scale factor, no flip). ``RandomFlip3D``
+``img_scale``), ``Normalize``, ``Pad`` (``size_divisor``), ``MultiScaleFlipAug`` (one scale factor; ``flip=True`` adds the mirrored view). ``RandomFlip3D``
 (gga_amd/pipelines.py) calls ``flip_image`` / ``flip_bboxes`` below when a sample carries an image.
 
 Two ways to the pixels, the same bits:
@@ -89,6 +89,14 @@ class DeferredImage:
         self.flip, self.table, self.reverse = False, None, False
         self.pad_h = self.pad_w = None
 
+    def copy(self):
+        """A second record of decisions about the SAME pixels (``src`` is shared, not copied): the other view of a sample under
+        ``MultiScaleFlipAug(flip=True)``, which ``flip_image`` may toggle without touching this one."""
+        other = DeferredImage(self.src)
+        other.dst_h, other.dst_w, other.flip, other.table, other.reverse = self.dst_h, self.dst_w, self.flip, self.table, self.reverse
+        other.pad_h, other.pad_w = self.pad_h, self.pad_w
+        return other
+
     @property
     def shape(self):
         """The shape the eager image would have now."""
@@ -111,26 +119,34 @@ class DeferredImage:
 
 class PackedImages:
     """The deferred images of one chunk as ONE uint8 tensor - the table first, every source at a 16-byte aligned offset -
-    plus the small per-image records. Picklable: what crosses the process boundary for a batch of images."""
+    plus the small per-image records. Picklable: what crosses the process boundary for a batch of images. Images that share
+    their ``src`` array (the views of a frame under ``MultiScaleFlipAug(flip=True)``) share its bytes in the buffer: every
+    source is held once. ``n_views``: the images are ``n_views`` views of ``len / n_views`` frames, view-major (all frames
+    of view 0 first) - the order of the output rows of ``image_batch``."""
 
     TABLE_BYTES = 3 * 256 * 4
 
-    def __init__(self, images):
+    def __init__(self, images, n_views=1):
         assert images and all(isinstance(i, DeferredImage) for i in images)
+        assert n_views >= 1 and len(images) % n_views == 0, (len(images), n_views)
         first = images[0]
         assert first.table is not None, 'Normalize must be part of a deferred image pipeline'
         for i in images:
             assert i.reverse == first.reverse and np.array_equal(i.table, first.table), 'one img_norm_cfg per batch'
-        self.reverse = bool(first.reverse)
-        self.records, at = [], self.TABLE_BYTES
+        self.reverse, self.n_views = bool(first.reverse), int(n_views)
+        self.records, at, placed, sources = [], self.TABLE_BYTES, {}, []
         for i in images:
-            self.records.append((at, i.src.shape[0], i.src.shape[1], i.dst_h, i.dst_w, int(i.flip), i.pad_h or i.dst_h, i.pad_w or i.dst_w))
-            at += -(-i.src.size // 16) * 16
+            if id(i.src) not in placed:
+                placed[id(i.src)] = at
+                sources.append((at, i.src))
+                at += -(-i.src.size // 16) * 16
+            self.records.append((placed[id(i.src)], i.src.shape[0], i.src.shape[1], i.dst_h, i.dst_w, int(i.flip), i.pad_h or i.dst_h,
+                                 i.pad_w or i.dst_w))
         self.buffer = torch.zeros(at, dtype=torch.uint8)
         buf = self.buffer.numpy()
         buf[:self.TABLE_BYTES] = np.ascontiguousarray(first.table, np.float32).reshape(-1).view(np.uint8)
-        for r, i in zip(self.records, images):
-            buf[r[0]:r[0] + i.src.size] = i.src.reshape(-1)
+        for o, src in sources:
+            buf[o:o + src.size] = src.reshape(-1)
 
     def __len__(self):
         return len(self.records)
@@ -147,11 +163,19 @@ class PackedImages:
         return out
 
 
+class PackedView:
+    """Stands where view ``index`` > 0 of a chunk was in a collated test-time batch: its images travel in view 0's
+    ``PackedImages`` (``n_views`` > 1)."""
+
+    def __init__(self, index):
+        self.index = int(index)
+
+
 def image_batch(images, device=None, channels_last=False):
     """``PackedImages`` or a list of ``DeferredImage`` -> float32 [B, 3, Hp, Wp], Hp / Wp the largest padded sizes of the
     batch; ``channels_last``: in channels-last memory. ``device=None``: the host arithmetic; a device: one upload of the
     byte buffer and one launch of ``gga_image_batch``."""
-    packed = images if isinstance(images, PackedImages) else PackedImages(list(images))
+    packed = images if isinstance(images, PackedImages) else PackedImages(list(images))      # (``n_views`` views: [V * B, ...], view-major)
     hp, wp = max(r[6] for r in packed.records), max(r[7] for r in packed.records)
     fmt = torch.channels_last if channels_last else torch.contiguous_format
     if device is None:
@@ -325,19 +349,31 @@ class Pad:
 
 @PIPELINES.register_module()
 class MultiScaleFlipAug:
-    """mmdet ``MultiScaleFlipAug`` for ``scale_factor=1.0, flip=False``: one pass with both written into the sample, every
-    output key wrapped in a one-element list."""
+    """mmdet ``MultiScaleFlipAug`` for one ``scale_factor``: a pass with ``flip=False`` and, with ``flip=True``, a second
+    one with the horizontal flip written into the sample (``RandomFlip3D`` among the transforms then mirrors the image and
+    sets ``pcd_horizontal_flip``); every output key is a list with one entry per view. The second view works on a
+    ``DeferredImage`` record and on lists of its own; the source pixels are shared. Several scales cannot be merged by the
+    detector (maps of different sizes) and are refused, as are ``img_scale`` and the vertical flip."""
 
     def __init__(self, transforms, img_scale=None, scale_factor=None, flip=False, flip_direction='horizontal'):
-        if img_scale is not None or isinstance(scale_factor, (list, tuple)) or scale_factor is None or flip:
-            raise NotImplementedError('MultiScaleFlipAug: one scale_factor, no flip')
-        self.transforms, self.scale_factor = Compose(transforms), float(scale_factor)
+        if img_scale is not None or isinstance(scale_factor, (list, tuple)) or scale_factor is None:
+            raise NotImplementedError('MultiScaleFlipAug: one scale_factor')
+        if flip and flip_direction not in ('horizontal', ['horizontal'], ('horizontal', )):
+            raise NotImplementedError(f'MultiScaleFlipAug: flip_direction {flip_direction!r} (the horizontal flip is built)')
+        if flip and not any((t.get('type') if isinstance(t, dict) else type(t).__name__) == 'RandomFlip3D' for t in transforms):
+            # this transform only writes the flag; without the one that reads it the second view would be the first again
+            raise NotImplementedError('MultiScaleFlipAug: flip=True needs a RandomFlip3D among the transforms to mirror the second view')
+        self.transforms, self.scale_factor, self.flip = Compose(transforms), float(scale_factor), bool(flip)
 
     def __call__(self, results):
         one = dict(results)
         one['scale_factor'], one['flip'], one['flip_direction'] = self.scale_factor, False, 'horizontal'
-        out = self.transforms(one)
-        return {key: [value] for key, value in out.items()}
+        if not self.flip:
+            return {key: [value] for key, value in self.transforms(one).items()}
+        two = {key: value.copy() if isinstance(value, (DeferredImage, list)) else value for key, value in results.items()}
+        two['scale_factor'], two['flip'], two['flip_direction'] = self.scale_factor, True, 'horizontal'
+        views = [self.transforms(one), self.transforms(two)]
+        return {key: [view[key] for view in views] for key in views[0]}
 
 
 def format_image(results):

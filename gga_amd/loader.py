@@ -369,7 +369,8 @@ def into_arena(payloads, align=64):
 def pack_collated(collated, arena=True):
     """Replaces the per-frame lists inside a collated batch's containers by ``PackedFrames`` (in place; what cannot be packed
     - stacked payloads, meta dicts - stays); ``arena``: all of them in one byte buffer (``into_arena``)."""
-    from .image_pipelines import DeferredImage, PackedImages
+    from .image_pipelines import DeferredImage, PackedImages, PackedView
+    deferred = lambda chunk: isinstance(chunk, list) and chunk and all(isinstance(f, DeferredImage) for f in chunk)
     made = []
     for key, value in collated.items():
         if isinstance(value, DataContainer) and not value.stack and isinstance(value.data, list):
@@ -380,11 +381,21 @@ def pack_collated(collated, arena=True):
                     made.append(packed)
         # deferred images (the mono3d branch), at train time and inside the test-time list over augmentations: the sources of
         # a chunk as one uint8 buffer of their own
-        for container in (value if isinstance(value, list) else [value]):
-            if isinstance(container, DataContainer) and not container.stack and isinstance(container.data, list):
-                for c, chunk in enumerate(container.data):
-                    if isinstance(chunk, list) and chunk and all(isinstance(f, DeferredImage) for f in chunk):
-                        container.data[c] = PackedImages(chunk)
+        containers = [v for v in (value if isinstance(value, list) else [value])
+                      if isinstance(v, DataContainer) and not v.stack and isinstance(v.data, list)]
+        if isinstance(value, list) and len(containers) == len(value) > 1 and len({len(v.data) for v in containers}) == 1:
+            # the views of a test-time sample (MultiScaleFlipAug(flip=True)): all views of a chunk in ONE buffer that holds every
+            # source once, view-major; the later views' places keep a marker
+            for c in range(len(containers[0].data)):
+                chunks = [v.data[c] for v in containers]
+                if all(deferred(ch) for ch in chunks) and len({len(ch) for ch in chunks}) == 1:
+                    containers[0].data[c] = PackedImages([f for ch in chunks for f in ch], n_views=len(chunks))
+                    for index, v in enumerate(containers[1:], 1):
+                        v.data[c] = PackedView(index)
+        for container in containers:
+            for c, chunk in enumerate(container.data):
+                if deferred(chunk):
+                    container.data[c] = PackedImages(chunk)
     if arena:
         into_arena(made)
     return collated
@@ -519,11 +530,19 @@ def _to_device(value, device, non_blocking):
 def _image_tensor(value, device, channels_last):
     """The ``img`` entry of a chunk -> the detector's image tensor: deferred images (``PackedImages`` or a list of
     ``DeferredImage``) through ``image_pipelines.image_batch``, a stacked tensor of the eager path moved to the device."""
-    from .image_pipelines import DeferredImage, PackedImages, image_batch
+    from .image_pipelines import DeferredImage, PackedImages, PackedView, image_batch
     if device is not None and torch.device(device).type != 'cuda':          # no GPU: the host arithmetic, the tensor stays where it is
         device = None
-    if isinstance(value, PackedImages) or (isinstance(value, list) and value and all(isinstance(v, DeferredImage) for v in value)):
+    deferred = lambda v: isinstance(v, list) and v and all(isinstance(f, DeferredImage) for f in v)
+    if isinstance(value, PackedImages) or deferred(value):
         return image_batch(value, device, channels_last)
+    if isinstance(value, list) and len(value) > 1 and all(deferred(v) for v in value) and len({len(v) for v in value}) == 1:
+        value = [PackedImages([f for v in value for f in v], n_views=len(value))] + [PackedView(i) for i in range(1, len(value))]
+    if isinstance(value, list) and value and isinstance(value[0], PackedImages) and value[0].n_views == len(value) > 1 and \
+            all(isinstance(v, PackedView) for v in value[1:]):
+        # the views of a test-time batch: one upload, one launch -> [V * B, 3, Hp, Wp], handed on as its V slices
+        both = image_batch(value[0], device, channels_last)
+        return list(both.split(both.shape[0] // len(value)))
     if isinstance(value, list):             # test-time: one entry per augmentation
         return [_image_tensor(v, device, channels_last) for v in value]
     if torch.is_tensor(value) and device is not None:

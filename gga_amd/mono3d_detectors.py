@@ -7,6 +7,8 @@ checkpoints load (parity unpinned: those modules are not in the reference tree).
 Dense 2D convolutions: the 3x3 / stride-1 ones of the residual blocks qualify for ``gga_dense_conv3x3_bn_bwd``
 (channels-last activations, 64 .. 512 channels); the rest (7x7 stem, 1x1, strided) are MIOpen's.
 """
+import os
+
 import torch
 from torch import nn
 
@@ -210,6 +212,11 @@ class FPN(nn.Module):
         return tuple(outs)
 
 
+def tta_merge_enabled():
+    """``GGA_MONO3D_TTA_MERGE=0`` makes ``aug_test`` merge the two views' maps with the eager restatement of the reference."""
+    return os.environ.get('GGA_MONO3D_TTA_MERGE', '1') != '0'
+
+
 @DETECTORS.register_module()
 class SingleStageMono3DDetector(nn.Module):
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
@@ -253,9 +260,12 @@ class SingleStageMono3DDetector(nn.Module):
     def simple_test(self, img, img_metas, rescale=False):
         """single_stage_mono3d.py:80-114: ``img_bbox`` (3D boxes, scores, labels) and - with a 2D branch -
         ``img_bbox2d`` (per-class arrays [n, 5]) per image."""
-        from .box3d import bbox3d2result
         outs = self.bbox_head(self.extract_feat(img))
-        bbox_outputs = self.bbox_head.get_bboxes(*outs, img_metas, rescale=rescale)
+        return self._results(self.bbox_head.get_bboxes(*outs, img_metas, rescale=rescale))
+
+    def _results(self, bbox_outputs):
+        """The per-image result dicts of ``get_bboxes``' output (host or device tensors)."""
+        from .box3d import bbox3d2result
         results = []
         for out in bbox_outputs:
             bboxes, scores, labels, attrs = out[:4]
@@ -266,10 +276,77 @@ class SingleStageMono3DDetector(nn.Module):
             results.append(r)
         return results
 
+    @staticmethod
+    def tta_merge_eager(outs, n_frames):
+        """single_stage_mono3d.py:141-181 restated operation by operation, frame by frame (the reference takes one frame):
+        ``outs`` is the head's output for the view-major ``[2 F, ...]`` batch."""
+        F_ = int(n_frames)
+        per_frame = []
+        for f in range(F_):
+            views = [[None if g[0] is None else [x[v * F_ + f:v * F_ + f + 1].clone() for x in g] for g in outs] for v in range(2)]
+            flipped = views[1]
+            for j in range(len(flipped)):
+                if flipped[j] is None:
+                    continue
+                for k in range(len(flipped[j])):
+                    flipped[j][k] = torch.flip(flipped[j][k], dims=[3])
+            for reg_feat in flipped[1]:       # offset_x (the reference also rewrites rotation and velo_x of the flipped view, channels
+                reg_feat[:, 0, :, :] = 1 - reg_feat[:, 0, :, :]          # 6 and 7: view 0's replace both below)
+            merged = []
+            for i in range(len(outs)):
+                if views[0][i] is None:
+                    merged.append(None)
+                    continue
+                feats = []
+                for j in range(len(views[0][i])):
+                    avg = torch.mean(torch.cat([v[i][j] for v in views]), dim=0, keepdim=True)
+                    if i == 1:          # rot / velo / key points / 2D distances keep the original
+                        avg[:, 6:, :, :] = views[0][i][j][:, 6:, :, :]
+                    if i == 2:          # dir_cls keeps the original
+                        avg = views[0][i][j]
+                    feats.append(avg)
+                merged.append(feats)
+            per_frame.append(merged)
+        return tuple([None] * len(g) if g[0] is None else [torch.cat([m[i][j] for m in per_frame]) for j in range(len(g))]
+                     for i, g in enumerate(outs))
+
+    def tta_head_outputs(self, imgs, img_metas):
+        """The head's output for the two views of a batch as ONE forward over the view-major ``[2 B, ...]`` batch (view ``v`` of
+        frame ``f`` at row ``v * B + f``; ``loader.to_step_inputs`` delivers the two views as the halves of one tensor)."""
+        if len(imgs) != 2 or len(img_metas) != 2 or imgs[0].shape != imgs[1].shape or len(img_metas[0]) != len(img_metas[1]):
+            raise ValueError('aug_test: two views of the same frames expected (MultiScaleFlipAug with one scale factor and flip=True)')
+        for view, flip in enumerate((False, True)):
+            if any(bool(m.get('pcd_horizontal_flip', False)) != flip or m.get('pcd_vertical_flip', False) for m in img_metas[view]):
+                raise ValueError('aug_test: view 0 must be the unflipped image and view 1 its horizontal flip')
+        a, b = imgs
+        base = a._base
+        if base is not None and base is b._base and base.dim() == a.dim() and base.shape[0] == 2 * a.shape[0] and \
+                base.shape[1:] == a.shape[1:] and a.data_ptr() == base.data_ptr() and b.data_ptr() == base[a.shape[0]:].data_ptr():
+            joined = base                           # the two halves of one tensor, as the loader builds them
+        else:
+            joined = torch.cat([a, b])
+        return self.bbox_head(self.extract_feat(joined))
+
+    @torch.no_grad()
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """single_stage_mono3d.py:136-204 for B >= 1 frames: the horizontal-flip view's maps are mirrored back and averaged
+        with the original's per frame (``functional.mono3d_tta_merge``, one launch; ``GGA_MONO3D_TTA_MERGE=0``: the eager
+        restatement), then ``get_bboxes`` on the merged maps with view 0's metas."""
+        from . import functional as F
+        n_frames = len(img_metas[0])
+        outs = self.tta_head_outputs(imgs, img_metas)
+        merge = F.mono3d_tta_merge if tta_merge_enabled() else self.tta_merge_eager
+        return self._results(self.bbox_head.get_bboxes(*merge(outs, n_frames), img_metas[0], rescale=rescale))
+
     def forward_test(self, imgs, img_metas, **kwargs):
-        if len(imgs) != 1:
-            raise NotImplementedError('test-time augmentation is not built')
-        return self.simple_test(imgs[0], img_metas[0], **kwargs)
+        if len(imgs) != len(img_metas):
+            raise ValueError(f'forward_test: {len(imgs)} image views but {len(img_metas)} lists of metas')
+        if len(imgs) == 1:
+            return self.simple_test(imgs[0], img_metas[0], **kwargs)
+        if len(imgs) == 2:
+            return self.aug_test(imgs, img_metas, **kwargs)
+        raise NotImplementedError(f'forward_test: {len(imgs)} views - one (simple_test) or two (the image and its horizontal flip, '
+                                  f'aug_test) are built')
 
     def forward(self, return_loss=True, **kwargs):
         if return_loss:

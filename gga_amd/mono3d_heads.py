@@ -9,7 +9,9 @@ MI355X side: the last tower convolutions are ``DCNv2`` (gga_amd/dcn.py, HIP samp
 O(points x boxes) target assignment of the whole batch is ONE launch (``gga_fcos3d_targets``) instead
 of ~60 broadcast tensor ops per image in a Python loop; the loss arithmetic on the few hundred
 positive points is plain device tensor code in the reference's order. Inference (``get_bboxes``, pgd_head.py:878-1130):
-per-level top-k, decoding, then per-class BEV NMS on the rotated-NMS kernel (``ops.box3d_multiclass_nms``).
+per-level top-k and decoding for the whole batch, per-class BEV NMS of all images in one pass (``gga_multiclass_nms3d``), the
+``max_per_img`` cut and the gathers in one launch (``gga_mono3d_collect``), one download; ``GGA_MONO3D_DETECT_BATCHED=0``: the loop
+over images with ``ops.box3d_multiclass_nms``.
 """
 import math
 
@@ -27,6 +29,11 @@ from .cnn import ConvModule
 from .registry import HEADS, build_bbox_coder, build_loss
 
 INF = 1e8
+
+
+def detect_batched():
+    """``GGA_MONO3D_DETECT_BATCHED=0`` keeps ``PGDHead.get_bboxes`` on the loop over images (``_get_bboxes_single``)."""
+    return os.environ.get('GGA_MONO3D_DETECT_BATCHED', '1') != '0'
 
 
 class _ShareParams(torch.autograd.Function):
@@ -602,6 +609,9 @@ class PGDHead(FCOSMono3DHead):
                    cfg=None, rescale=None):
         num_levels = len(cls_scores)
         mlvl_points = self.get_points([f.size()[-2:] for f in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
+        if detect_batched() and cls_scores[0].is_cuda:
+            return self._get_bboxes_batched(cls_scores, bbox_preds, dir_cls_preds, depth_cls_preds, weights, attr_preds, centernesses,
+                                            mlvl_points, img_metas, cfg, rescale)
         result_list = []
         for img_id in range(len(img_metas)):
             pick = lambda xs: [xs[i][img_id].detach() for i in range(num_levels)]
@@ -689,6 +699,122 @@ class PGDHead(FCOSMono3DHead):
         outputs = (out_boxes, out_scores, labels, attrs.to(labels.dtype) if self.pred_attrs else None)
         if self.pred_bbox2d:
             outputs = outputs + (torch.cat([results[-1], out_scores[:, None]], dim=1), )
+        return outputs
+
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, dir_cls_preds, depth_cls_preds, weights, attr_preds, centernesses,
+                            mlvl_points, img_metas, cfg, rescale=False):
+        """``_get_bboxes_single`` for all images of the batch at once, with one host wait: the download of the packed result.
+        The candidate stage is the loop's arithmetic on ``[B, ...]`` tensors - every operation elementwise or per row, so an
+        image's bits do not change; the per-row ``topk(nms_pre)`` and the ``mm`` of ``points_img2cam`` (one cam2img per image)
+        stay calls per image on the loop's shapes (launches, no waits). Every image of a batch has the padded size, hence
+        the same ``N`` candidates. Then one ``multiclass_nms3d`` (scene = image) on the xywhr boxes ``ops.nms_bev`` /
+        ``ops.nms_normal_bev`` would form, and ``mono3d_collect`` for the ``max_per_img`` cut and the gathers. The outputs are
+        host tensors, per image the tuple of ``_get_bboxes_single``."""
+        from . import ops
+        cfg = self.test_cfg if cfg is None else cfg
+        get = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+        B, code, dev, dtype = len(img_metas), self.bbox_coder.bbox_code_size, cls_scores[0].device, bbox_preds[0].dtype
+        assert cls_scores[0].shape[0] == B, f'{cls_scores[0].shape[0]} images in the maps, {B} metas'
+        views = [np.array(m['cam2img']) for m in img_metas]
+        flat = lambda x, c: x.detach().permute(0, 2, 3, 1).reshape(B, -1, c)
+        full = lambda ref, c, v=0: ref.new_full([B, c, *ref.shape[2:]], v)
+        pick = lambda x, idx: torch.gather(x, 1, idx if x.dim() == 2 else idx[..., None].expand(-1, -1, x.shape[2]))
+        nms_pre = get('nms_pre', -1)
+        # what differs per image, in one upload: scale factor, image size (the clamp of the 2D boxes), principal point and
+        # focal length (decode_yaw)
+        cam = np.stack([np.eye(4, dtype=np.float32) for _ in range(B)])
+        for b, view in enumerate(views):
+            cam[b, :view.shape[0], :view.shape[1]] = view
+        per_image = F.upload_many(dict(
+            sf=np.stack([np.asarray(m['scale_factor'], np.float32).reshape(-1) for m in img_metas]),
+            hw=np.array([[m['img_shape'][0], m['img_shape'][1]] for m in img_metas], np.float32), cam=cam[:, 0, [2, 0]]), dev)
+        sf = per_image['sf'][:, None, :]                  # [B, 1, 1 | 2 | 4]
+        max_h, max_w = per_image['hw'][:, 0:1], per_image['hw'][:, 1:2]
+        cam = per_image['cam']                            # [B, 2] = (cx, fx)
+        acc = dict(c2d=[], box=[], score=[], dir=[], attr=[], cen=[], dcls=[], dunc=[], b2d=[])
+        for lvl, points in enumerate(mlvl_points):
+            cls_score = cls_scores[lvl]
+            scores = flat(cls_score, self.cls_out_channels).sigmoid()
+            dir_cls_score = torch.max(flat(dir_cls_preds[lvl] if self.use_direction_classifier else full(cls_score, 2), 2), dim=-1)[1]
+            depth_cls_pred = flat(depth_cls_preds[lvl] if self.use_depth_classifier else full(cls_score, self.num_depth_cls),
+                                  self.num_depth_cls)
+            depth_cls_score = torch.softmax(depth_cls_pred, dim=-1).topk(k=2, dim=-1)[0].mean(dim=-1)
+            weight = flat(weights[lvl] if self.weight_dim != -1 else full(cls_score, 1), self.weight_dim if self.weight_dim != -1 else 1)
+            depth_uncertainty = torch.exp(-weight[..., -1])
+            attr_pred = attr_preds[lvl] if self.pred_attrs else full(cls_score, self.num_attrs, self.attr_background_label)
+            attr_score = torch.max(flat(attr_pred, self.num_attrs), dim=-1)[1]
+            centerness = flat(centernesses[lvl], 1)[..., 0].sigmoid()
+            bbox_pred = flat(bbox_preds[lvl], sum(self.group_reg_dims))
+            bbox_pred3d = bbox_pred[..., :code].clone()
+            bbox_pred2d = bbox_pred[..., -4:].clone() if self.pred_bbox2d else None
+            points = points[None].expand(B, -1, -1)
+            if nms_pre > 0 and scores.shape[1] > nms_pre:
+                merged = scores * centerness[..., None]
+                if self.use_depth_classifier:
+                    merged = merged * depth_cls_score[..., None]
+                    if self.weight_dim != -1:
+                        merged = merged * depth_uncertainty[..., None]
+                best = merged.max(dim=2)[0]
+                topk_inds = torch.stack([best[b].topk(nms_pre)[1] for b in range(B)])
+                points, bbox_pred3d, scores = pick(points, topk_inds), pick(bbox_pred3d, topk_inds), pick(scores, topk_inds)
+                depth_cls_pred, centerness, dir_cls_score = pick(depth_cls_pred, topk_inds), pick(centerness, topk_inds), pick(dir_cls_score, topk_inds)
+                depth_cls_score, depth_uncertainty, attr_score = pick(depth_cls_score, topk_inds), pick(depth_uncertainty, topk_inds), pick(attr_score, topk_inds)
+                if self.pred_bbox2d:
+                    bbox_pred2d = pick(bbox_pred2d, topk_inds)
+            bbox_pred3d[..., :2] = points - bbox_pred3d[..., :2]
+            if rescale:
+                bbox_pred3d[..., :2] /= sf
+                if self.pred_bbox2d:
+                    bbox_pred2d /= sf
+            if self.use_depth_classifier:
+                prob = self.bbox_coder.decode_prob_depth(depth_cls_pred, self.depth_range, self.depth_unit, self.division,
+                                                         self.num_depth_cls)
+                a = torch.sigmoid(self.fuse_lambda)
+                bbox_pred3d[..., 2] = a * bbox_pred3d[..., 2] + (1 - a) * prob
+            acc['c2d'].append(bbox_pred3d[..., :3].clone())
+            for b in range(B):
+                bbox_pred3d[b, :, :3] = points_img2cam(bbox_pred3d[b, :, :3], views[b])
+            acc['box'].append(bbox_pred3d), acc['score'].append(scores), acc['dir'].append(dir_cls_score)
+            acc['dcls'].append(depth_cls_score), acc['attr'].append(attr_score), acc['cen'].append(centerness)
+            acc['dunc'].append(depth_uncertainty)
+            if self.pred_bbox2d:
+                x1, y1 = points[..., 0] - bbox_pred2d[..., 0], points[..., 1] - bbox_pred2d[..., 1]
+                x2, y2 = points[..., 0] + bbox_pred2d[..., 2], points[..., 1] + bbox_pred2d[..., 3]
+                clip = lambda v, hi: torch.minimum(v.clamp(min=0), hi)            # distance2bbox(max_shape=img_shape), a bound per image
+                acc['b2d'].append(torch.stack([clip(x1, max_w), clip(y1, max_h), clip(x2, max_w), clip(y2, max_h)], -1))
+        cat = lambda k: torch.cat(acc[k], dim=1)
+        centers2d, bboxes, dir_scores = cat('c2d'), cat('box'), cat('dir')
+        N = bboxes.shape[1]
+        # decode_yaw with the principal point and the focal length of every image
+        yaw = limit_period(bboxes[..., 6] - self.dir_offset, 0, np.pi) + self.dir_offset + np.pi * dir_scores.to(dtype)
+        bboxes[..., 6] = torch.atan2(centers2d[..., 0] - cam[:, 0:1], cam[:, 1:2]) + yaw
+        box_type = img_metas[0]['box_type_3d']
+        centred = box_type(bboxes.reshape(B * N, code), box_dim=code, origin=(0.5, 0.5, 0.5))     # elementwise: all images at once
+        xyxyr = ops.xywhr2xyxyr(centred.bev)
+        rot = xyxyr[:, 4] if get('use_rotate_nms') else torch.zeros_like(xyxyr[:, 4])
+        zero = torch.zeros_like(rot)
+        for_nms = torch.stack(((xyxyr[:, 0] + xyxyr[:, 2]) / 2, (xyxyr[:, 1] + xyxyr[:, 3]) / 2, zero, xyxyr[:, 2] - xyxyr[:, 0],
+                               xyxyr[:, 3] - xyxyr[:, 1], zero, rot), dim=-1)
+        nms_scores = cat('score') * cat('cen')[..., None]
+        if self.use_depth_classifier:
+            nms_scores = nms_scores * cat('dcls')[..., None]
+            if self.weight_dim != -1:
+                nms_scores = nms_scores * cat('dunc')[..., None]
+        nms_scores = nms_scores.reshape(B * N, -1)
+        scene = F.const_tensor(np.repeat(np.arange(B, dtype=np.int64), N), dev, torch.int64)
+        rows, classes, count = F.multiclass_nms3d(for_nms, nms_scores, scene, B, get('score_thr'), get('nms_thr'))
+        bboxes2d = cat('b2d').reshape(B * N, 4) if self.pred_bbox2d else None
+        packed, views_of = F.mono3d_collect(rows, classes, count, nms_scores, centred.tensor, dir_scores.reshape(-1),
+                                            cat('attr').reshape(-1), bboxes2d, get('max_per_img'))
+        host = views_of(packed.cpu())                # the one wait of the batch
+        outputs = []
+        for b, n in enumerate(host['count'].tolist()):
+            out_scores, labels = host['scores'][b, :n].clone(), host['labels'][b, :n].long()
+            out = (box_type(host['boxes'][b, :n], box_dim=code), out_scores, labels,
+                   host['attr'][b, :n].to(labels.dtype) if self.pred_attrs else None)
+            if self.pred_bbox2d:
+                out = out + (torch.cat([host['boxes2d'][b, :n], out_scores[:, None]], dim=1), )
+            outputs.append(out)
         return outputs
 
     prepare_loss_before_forward = True      # SingleStageMono3DDetector.forward_train calls prepare_loss before the forward pass

@@ -978,6 +978,57 @@ typedef struct {
 } gga_tta_table;
 int gga_tta_merge_maps(const gga_tta_table* table, int n_frames, int H, int W, void* stream);
 
+/* Flip test-time augmentation of the mono3d detectors: the head maps of the two views of a batch merged in one launch.
+ * Restates mmdet3d/models/detectors/single_stage_mono3d.py:141-181 (aug_test: torch.flip(dims=[3]) of the flipped view,
+ * `1 - x` on its regression channel 0, torch.mean over the two views, the regression channels >= 6 taken from view 0) for
+ * every frame of a batch. One table entry per (output group, FPN level): src is a contiguous f32 [2 * n_frames, channels, H, W]
+ * map, view-major (view 0 = the unflipped image of frame f at row f, view 1 = its horizontal mirror at row n_frames + f); dst is
+ * [n_frames, channels, H, W]. With a = view 0 at (h, w) and b = view 1 at (h, W - 1 - w) - the whole padded map is mirrored, as
+ * torch.flip does -
+ *     GGA_MONO3D_TTA_MEAN: (a + b) * 0.5 in every channel
+ *     GGA_MONO3D_TTA_REG:  channel 0: (a + (1 - b)) * 0.5; channels 1..5: (a + b) * 0.5; channels >= 6: a
+ * each a single rounded f32 operation per step: the bits of the reference's sequence (its mean of two values is one addition and
+ * an exact halving). Entries may differ in channels, H and W; an entry is read and written with 16-byte accesses when its W is a
+ * multiple of 4 and its two pointers are 16-byte aligned, else element by element. (The direction-classifier group is view 0's
+ * own output and needs no entry.)
+ * GGA_ERR_INVALID_ARG before any HIP call for: a null table; n_maps outside 1..GGA_MONO3D_TTA_MAX_MAPS; n_frames <= 0; a null
+ * map pointer; H, W or channels <= 0; an unknown kind; a REG map with fewer than 7 channels. */
+#define GGA_MONO3D_TTA_MAX_MAPS 48
+enum { GGA_MONO3D_TTA_MEAN = 0, GGA_MONO3D_TTA_REG = 1 };
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t channels, H, W, kind;
+} gga_mono3d_tta_map;
+typedef struct {
+    int32_t n_maps, n_frames;
+    gga_mono3d_tta_map map[GGA_MONO3D_TTA_MAX_MAPS];
+} gga_mono3d_tta_table;
+int gga_mono3d_tta_merge(const gga_mono3d_tta_table* table, void* stream);
+
+/* The tail of a whole-batch mono3d `get_bboxes`: what box3d_multiclass_nms (mmdet3d/core/post_processing/box3d_nms.py:93-127)
+ * does after its per-class NMS, for every image of a batch in one launch and without a read-back. rows / classes
+ * [n_rows * n_classes] i32 and counts [n_images] i32 are the packed output of gga_multiclass_nms3d (scene = image): image i's kept
+ * (candidate row, class) pairs begin at the sum of the counts before it, class-ascending, by descending score within a class.
+ * Per-candidate arrays: scores f32 with score_stride >= n_classes floats per row, boxes f32 [n_rows, code], dir / attr i64
+ * [n_rows] (optional: null gives zeros), boxes2d f32 [n_rows, 4] (optional, together with out_boxes2d).
+ * Per image: a list of at most max_per_img pairs is taken in list order; a longer one is cut to its max_per_img highest
+ * scores in descending order, equal scores in list order (the reference's unstable sort leaves that order open). Outputs, fixed
+ * shape: out_boxes f32 [n_images, max_per_img, code], out_scores f32, out_labels / out_dir / out_attr i32 [n_images,
+ * max_per_img], out_boxes2d f32 [n_images, max_per_img, 4], out_count i32 [n_images] = min(count, max_per_img); the slots
+ * behind an image's last detection are zero. A pair whose row or class lies outside its range is not gathered.
+ * GGA_ERR_INVALID_ARG before any launch for: n_rows < 0; n_classes outside 1..GGA_MULTICLASS_NMS_MAX_CLASSES; n_images outside
+ * 1..GGA_MONO3D_COLLECT_MAX_IMAGES; n_rows * n_classes >= 2^31; code outside 1..64; max_per_img < 1 or max_per_img * n_images >=
+ * 2^24; score_stride < n_classes; a null counts or output pointer; boxes2d without out_boxes2d or the reverse; any other null
+ * pointer while n_rows > 0; a workspace smaller than gga_mono3d_collect_workspace_bytes (0 for sizes it refuses). */
+#define GGA_MONO3D_COLLECT_MAX_IMAGES 4096
+size_t gga_mono3d_collect_workspace_bytes(int64_t n_rows, int n_classes, int n_images);
+int gga_mono3d_collect(const int32_t* rows, const int32_t* classes, const int32_t* counts, int n_images, int64_t n_rows,
+                       int n_classes, const float* scores, int score_stride, const float* boxes, int code, const int64_t* dir,
+                       const int64_t* attr, const float* boxes2d, int max_per_img, float* out_boxes, float* out_scores,
+                       int32_t* out_labels, int32_t* out_dir, int32_t* out_attr, float* out_boxes2d, int32_t* out_count,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pseudo-label matching: image-plane IoU of every detection with the ground truths of its own
  * frame and the argmax, i.e. `calculate_iou_partly(dt_annos, gt_annos, metric=0)` followed by
  * `np.argmax(c_overlap, axis=-1)` in tools/utils_pseudo_labels_gga.py:44-59 (IoU arithmetic:

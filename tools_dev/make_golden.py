@@ -1849,6 +1849,56 @@ def golden_tta(ref):
     np.savez_compressed(os.path.join(OUT, 'tta.npz'), **out)
 
 
+MONO3D_TTA_GROUPS = ('cls_scores', 'bbox_preds', 'dir_cls_preds', 'depth_cls_preds', 'weights', 'attr_preds', 'centernesses')
+MONO3D_TTA_CASES = [
+    dict(levels=[(2, 4), (3, 5), (2, 3), (1, 1)], channels=(2, 11, 2, 3, 1, 2, 1), pred_velo=False),      # code 7 + four 2D distances
+    dict(levels=[(3, 6), (1, 4)], channels=(2, 9, 2, None, None, None, 1), pred_velo=True),                # code 9, optional groups off
+]
+
+
+def golden_mono3d_tta(ref):
+    """Flip test-time augmentation of the mono3d detectors: the merged head maps the body of the reference's ``aug_test``
+    (mmdet3d/models/detectors/single_stage_mono3d.py:136-204) hands to ``get_bboxes``. The method is taken out of its class by
+    name at run time and driven with a stub ``self`` whose head returns seeded random maps (view 0, then the flipped view) and
+    records what ``get_bboxes`` receives. One frame, as the reference supports. CPU float32. Arrays only."""
+    import ast
+    src = open(os.path.join(REF, 'mmdet3d/models/detectors/single_stage_mono3d.py')).read()
+    cls = [n for n in ast.parse(src).body if isinstance(n, ast.ClassDef)][0]
+    fns = [n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == 'aug_test']
+    ns = dict(torch=torch, np=np, bbox3d2result=lambda *a: dict())
+    exec(compile(ast.Module(body=fns, type_ignores=[]), 'single_stage_mono3d.py', 'exec'), ns)
+    rng = np.random.default_rng(4711)
+    out = {}
+    for c, case in enumerate(MONO3D_TTA_CASES):
+        maps = [[None if ch is None else [torch.from_numpy(rng.normal(size=(1, ch, h, w)).astype(np.float32)) for h, w in case['levels']]
+                 for ch in case['channels']] for _ in range(2)]
+        seen = []
+
+        class Head:
+            pred_velo, pred_bbox2d = case['pred_velo'], False
+
+            def __call__(self, x):          # `x` is the view's index; (the method writes into what it gets: hand out copies)
+                return [[None] * len(case['levels']) if g is None else [t.clone() for t in g] for g in maps[x]]
+
+            def get_bboxes(self, *args, rescale=False):
+                seen.append(args[:-1])
+                return [(None, None, None, None)]
+
+        fake = type('D', (), dict(bbox_head=Head(), extract_feats=lambda self, imgs: imgs))()
+        ns['aug_test'](fake, [0, 1], [[dict(pcd_horizontal_flip=False)], [dict(pcd_horizontal_flip=True)]])
+        assert len(seen) == 1 and len(seen[0]) == len(MONO3D_TTA_GROUPS)
+        for g, name in enumerate(MONO3D_TTA_GROUPS):
+            if case['channels'][g] is None:
+                assert all(x is None for x in seen[0][g])
+                continue
+            for l in range(len(case['levels'])):
+                out[f'in.{c}.{name}.{l}'] = np.concatenate([maps[0][g][l].numpy(), maps[1][g][l].numpy()])
+                out[f'out.{c}.{name}.{l}'] = seen[0][g][l].numpy().copy()
+        out[f'levels.{c}'] = np.array(case['levels'], np.int64)
+    print('  mono3d tta:', len(MONO3D_TTA_CASES), 'cases,', sum(k.startswith('out.') for k in out), 'merged maps')
+    np.savez_compressed(os.path.join(OUT, 'mono3d_tta.npz'), **out)
+
+
 INDOOR_CONFIG_SECTIONS = ('model', 'optimizer', 'optimizer_config', 'lr_config', 'runner', 'checkpoint_config', 'custom_hooks', 'data',
                           'train_pipeline', 'test_pipeline')
 INDOOR_CONFIGS = ('configs/fcaf3d/fcaf3d_8x2_scannet-3d-18class.py', 'configs/fcaf3d/fcaf3d_8x2_s3dis-3d-5class.py')
@@ -2180,6 +2230,7 @@ def main():
     golden_configs(ref)
     golden_dynamic_voxel(ref)
     golden_tta(ref)
+    golden_mono3d_tta(ref)
     golden_indoor_datasets(ref)
     golden_kitti_mono(ref)
     golden_kitti_raw(ref)
