@@ -85,6 +85,31 @@ class ImageDesc(C.Structure):
                 ('flip', C.c_int32), ('reserved', C.c_int32)]
 
 
+CENTER_MAX_CLASSES = 64     # GGA_CENTER_MAX_CLASSES
+CENTER_MAX_K = 512          # GGA_CENTER_MAX_K
+
+
+class CenterParams(C.Structure):
+    """gga_center_params: the train_cfg numbers and the class -> (task, index) table of gga_center_targets."""
+    _fields_ = [('pc_range', C.c_float * 2), ('voxel_size', C.c_float * 2), ('out_size_factor', C.c_float),
+                ('gaussian_overlap', C.c_float), ('min_radius', C.c_int32), ('K', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('n_tasks', C.c_int32), ('n_classes', C.c_int32), ('task_classes', C.c_int32 * MAX_TASKS),
+                ('task_class_base', C.c_int32 * MAX_TASKS), ('class_task', C.c_int32 * CENTER_MAX_CLASSES),
+                ('class_index', C.c_int32 * CENTER_MAX_CLASSES)]
+
+
+class CenterLossTask(C.Structure):
+    _fields_ = [('pred', vp), ('anno_box', vp), ('mask', vp), ('loss', vp), ('grad_loss', vp), ('grad_pred', vp)]
+
+
+class CenterLossTable(C.Structure):
+    _fields_ = [('n_tasks', C.c_int32), ('task', CenterLossTask * MAX_TASKS)]
+
+
+class CenterLossWeights(C.Structure):
+    _fields_ = [('code_weights', C.c_float * 8), ('loss_weight', C.c_float)]
+
+
 class LossParams(C.Structure):
     _fields_ = [('B', C.c_int32), ('K', C.c_int32), ('fm_w', C.c_int32),
                 ('voxel_size', C.c_float * 2), ('out_size_factor', C.c_float),
@@ -193,6 +218,9 @@ SIGNATURES = {
     'gga_box_losses_workspace_bytes': (sz, [i32, i32, i32]),
     'gga_box_losses_fwd': (i32, [C.POINTER(TaskTable), C.POINTER(LossParams), vp, sz, vp]),
     'gga_box_losses_bwd': (i32, [C.POINTER(TaskTable), i32, i32, vp]),
+    'gga_center_targets': (i32, [vp, vp, vp, i32, C.POINTER(CenterParams), vp, vp, vp, vp, vp, vp, i32, vp]),
+    'gga_center_reg_loss_fwd': (i32, [C.POINTER(CenterLossTable), i32, i32, C.POINTER(CenterLossWeights), vp]),
+    'gga_center_reg_loss_bwd': (i32, [C.POINTER(CenterLossTable), i32, i32, C.POINTER(CenterLossWeights), vp]),
     'gga_box_iou_rotated': (i32, [vp, i32, vp, i32, i32, i32, vp, vp]),
     'gga_nms_rotated_workspace_bytes': (sz, [i32]),
     'gga_nms_rotated_sorted': (i32, [vp, i32, f32, i32, vp, vp, vp, sz, vp]),

@@ -13,6 +13,7 @@ from . import ops
 
 class LiDARInstance3DBoxes:
     YAW_AXIS = 2
+    MOVES_WITH_POINTS = True          # GlobalRotScaleTrans / RandomFlip3D carry these boxes along with the points
 
     def __init__(self, tensor, box_dim=7, with_yaw=True, origin=(0.5, 0.5, 0)):
         if isinstance(tensor, torch.Tensor):
@@ -113,6 +114,36 @@ class LiDARInstance3DBoxes:
         """base_box3d.py:263-270, in place: centre, size and the columns past the yaw (velocity)."""
         self.tensor[:, :6] *= scale_factor
         self.tensor[:, 7:] *= scale_factor
+
+    def rotate(self, angle):
+        """lidar_box3d.py:91-129, in place: an angle about z, or the transposed rotation matrix [3, 3] the points were
+        multiplied by (``GlobalRotScaleTrans``' ``pcd_rotation``). Centres times the matrix, yaw plus its angle, the velocity
+        columns of a 9-column box times its upper 2 x 2."""
+        if not isinstance(angle, torch.Tensor):
+            angle = self.tensor.new_tensor(angle)
+        assert angle.shape == torch.Size([3, 3]) or angle.numel() == 1, f'invalid rotation angle shape {angle.shape}'
+        if angle.numel() == 1:
+            c, s = math.cos(float(angle)), math.sin(float(angle))
+            rot_mat_t = self.tensor.new_tensor([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]])
+            turn = float(angle)
+        else:
+            rot_mat_t = angle.to(self.tensor)
+            turn = math.atan2(float(rot_mat_t[0, 1]), float(rot_mat_t[0, 0]))
+        self.tensor[:, 0:3] = self.tensor[:, 0:3] @ rot_mat_t
+        self.tensor[:, 6] += turn
+        if self.tensor.shape[1] == 9:
+            self.tensor[:, 7:9] = self.tensor[:, 7:9] @ rot_mat_t[:2, :2]
+
+    def translate(self, trans_vector):
+        """base_box3d.py:232-240, in place."""
+        if not isinstance(trans_vector, torch.Tensor):
+            trans_vector = self.tensor.new_tensor(trans_vector)
+        self.tensor[:, :3] += trans_vector
+
+    def in_range_bev(self, box_range):
+        """base_box3d.py:290-306: centres strictly inside (x_min, y_min, x_max, y_max)."""
+        bev = self.tensor[:, :2]
+        return (bev[:, 0] > box_range[0]) & (bev[:, 1] > box_range[1]) & (bev[:, 0] < box_range[2]) & (bev[:, 1] < box_range[3])
 
     def limit_yaw(self, offset=0.5, period=math.pi):
         """base_box3d.py:272-279 / structures/utils.py:11-25: yaw -> [-offset*period, (1-offset)*period)."""

@@ -104,16 +104,7 @@ class KittiDataset_GGA_train:
         info = self.data_infos[index]
         rect = info['calib']['R0_rect'].astype(np.float32)
         Trv2c = info['calib']['Tr_velo_to_cam'].astype(np.float32)
-        plane_lidar = None
-        if 'plane' in info:          # ground plane (n, d) of the camera frame -> LiDAR frame: normal rotated, a point of it moved
-            cam2lidar = np.linalg.inv(rect @ Trv2c)
-            R, t = cam2lidar[:3, :3], cam2lidar[:3, 3]
-            normal_cam = info['plane'][:3]
-            on_plane_cam = -normal_cam * info['plane'][3]
-            normal = (R @ normal_cam[:, None])[:, 0]
-            on_plane = R @ on_plane_cam[:, None][:, 0] + t
-            plane_lidar = np.zeros_like(normal, shape=(4, ))
-            plane_lidar[:3], plane_lidar[3] = normal, -normal.T @ on_plane
+        plane_lidar = self._plane_lidar(info, rect, Trv2c)
         annos = self.remove_dontcare_GGA(info['annos'])      # other objects stay: collision tests when sampling
         difficulty = annos['difficulty']
         gt_names = annos['name']
@@ -135,6 +126,21 @@ class KittiDataset_GGA_train:
                     GGA_mask_boundary=gga['GGA_mask_boundary'], GGA_bdry_masks=gga['GGA_bdry_masks'],
                     GGA_in_box_points=in_box, GGA_init_pseudo_label=gga['GGA_init_pseudo_label'],
                     GGA_num_points_in_box2d=gga['GGA_num_points_in_box2d'])
+
+    @staticmethod
+    def _plane_lidar(info, rect, Trv2c):
+        if 'plane' not in info:
+            return None
+        # ground plane (n, d) of the camera frame -> LiDAR frame: normal rotated, a point of it moved
+        cam2lidar = np.linalg.inv(rect @ Trv2c)
+        R, t = cam2lidar[:3, :3], cam2lidar[:3, 3]
+        normal_cam = info['plane'][:3]
+        on_plane_cam = -normal_cam * info['plane'][3]
+        normal = (R @ normal_cam[:, None])[:, 0]
+        on_plane = R @ on_plane_cam[:, None][:, 0] + t
+        plane_lidar = np.zeros_like(normal, shape=(4, ))
+        plane_lidar[:3], plane_lidar[3] = normal, -normal.T @ on_plane
+        return plane_lidar
 
     def drop_arrays_by_name(self, gt_names, used_classes):
         return np.array([i for i, x in enumerate(gt_names) if x not in used_classes], dtype=np.int64)
@@ -329,6 +335,29 @@ class KittiDataset_GGA_train:
                         box3d_lidar=box_preds.tensor[valid_inds].numpy(), scores=scores[valid_inds].numpy(),
                         label_preds=labels[valid_inds].numpy(), sample_idx=sample_idx)
         return empty
+
+
+@DATASETS.register_module()
+class KittiDataset(KittiDataset_GGA_train):
+    """``KittiDataset`` (mmdet3d/datasets/kitti_dataset.py:143-225): any KITTI info list whose ``annos`` hold ``name /
+    location / dimensions / rotation_y / bbox`` - the ``kitti_infos_*_GGA.pkl`` files (their ``GGA_*`` fields are left alone) and
+    the pseudo-label file a GGA run writes (which has none). What a LiDAR detector is trained on in 3D; ``evaluate`` /
+    ``format_results`` are the parent's."""
+
+    def get_ann_info(self, index):
+        info = self.data_infos[index]
+        rect = info['calib']['R0_rect'].astype(np.float32)
+        Trv2c = info['calib']['Tr_velo_to_cam'].astype(np.float32)
+        annos = info['annos']
+        keep = self.drop_arrays_by_name(annos['name'], ['DontCare'])
+        gt_names = np.asarray(annos['name'])[keep]
+        cam = np.concatenate([np.asarray(annos['location']).reshape(-1, 3)[keep], np.asarray(annos['dimensions']).reshape(-1, 3)[keep],
+                              np.asarray(annos['rotation_y']).reshape(-1)[keep][..., np.newaxis]], axis=1).astype(np.float32)
+        gt_bboxes_3d = LiDARInstance3DBoxes(camera_boxes_to_lidar(cam, np.linalg.inv(rect @ Trv2c)))
+        gt_bboxes = np.asarray(annos['bbox']).reshape(-1, 4)[keep].astype('float32')
+        gt_labels = np.array([self.CLASSES.index(cat) if cat in self.CLASSES else -1 for cat in gt_names]).astype(np.int64)
+        return dict(gt_bboxes_3d=gt_bboxes_3d, gt_labels_3d=copy.deepcopy(gt_labels), bboxes=gt_bboxes, labels=gt_labels,
+                    gt_names=gt_names, plane=self._plane_lidar(info, rect, Trv2c), difficulty=annos.get('difficulty'))
 
 
 def _unwrap(x):

@@ -113,18 +113,14 @@ def gaussian_radius_np(height, width, min_overlap):
     return np.minimum(np.minimum(r1, r2), r3)
 
 
-@HEADS.register_module()
-class CenterHead_GGA(nn.Module):
-    def __init__(self, in_channels=[128], tasks=None, train_cfg=None, test_cfg=None, bbox_coder=None,
-                 common_heads=dict(), loss_cls=dict(type='GaussianFocalLoss', reduction='mean'),
-                 loss_bbox=dict(type='L1Loss', reduction='none', loss_weight=0.25),
-                 loss_center=dict(type='MarginL1Loss', reduction='mean'),
-                 separate_head=dict(type='SeparateHead', init_bias=-2.19, final_kernel=3),
-                 share_conv_channel=64, num_heatmap_convs=2, conv_cfg=dict(type='Conv2d'),
-                 norm_cfg=dict(type='BN2d'), bias='auto', norm_bbox=True, init_cfg=None,
-                 pal_backprop=False):
+class _CenterHeadBase(nn.Module):
+    """What ``CenterHead`` and ``CenterHead_GGA`` share: the modules (and with them the ``state_dict`` names), ``forward`` /
+    ``forward_single`` with the ``cells`` fast path, and ``get_bboxes``. A subclass adds its targets and losses."""
+
+    def _build(self, in_channels, tasks, train_cfg, test_cfg, bbox_coder, common_heads, loss_cls, loss_bbox, separate_head,
+               share_conv_channel, num_heatmap_convs, conv_cfg, norm_cfg, bias, norm_bbox, init_cfg):
         assert init_cfg is None, 'To prevent abnormal initialization behavior, init_cfg is not allowed to be set'
-        super().__init__()
+        nn.Module.__init__(self)
         num_classes = [len(t['class_names']) for t in tasks]
         self.class_names = [t['class_names'] for t in tasks]
         self.train_cfg = train_cfg
@@ -137,10 +133,6 @@ class CenterHead_GGA(nn.Module):
         self.bbox_coder = build_bbox_coder(bbox_coder) if bbox_coder is not None else None
         self.num_anchor_per_locs = [n for n in num_classes]
         self.fp16_enabled = False
-        # Stock mmdet's _parse_losses only back-propagates keys containing 'loss'; the PAL
-        # terms are stored as task{i}.distance* (head:697-699), i.e. logged, not trained.
-        # pal_backprop=True keeps the key names but lets the detector add them to the total.
-        self.pal_backprop = pal_backprop
 
         self.shared_conv = ConvModule(in_channels, share_conv_channel, kernel_size=3, padding=1,
                                       conv_cfg=conv_cfg, norm_cfg=norm_cfg, bias=bias)
@@ -152,7 +144,7 @@ class CenterHead_GGA(nn.Module):
             separate_head.update(in_channels=share_conv_channel, heads=heads, num_cls=num_cls)
             self.task_heads.append(build_head(separate_head))
         self.with_velocity = 'vel' in common_heads.keys()
-        assert not self.with_velocity, 'GGA does not support velocity (head:600-601)'
+        assert not self.with_velocity, self._NO_VELOCITY
         assert self.norm_bbox, 'the HIP loss path implements norm_bbox=True (log-dims), as every GGA config uses'
         # The fused loss kernels implement mmdet's reduction='mean' with avg_factor (what configs/gga/* set).
         # The constructor DEFAULT of the reference is loss_bbox reduction='none' (element-wise losses that
@@ -161,7 +153,7 @@ class CenterHead_GGA(nn.Module):
         for name in ('loss_cls', 'loss_bbox'):
             red = getattr(getattr(self, name), 'reduction', 'mean')
             if red != 'mean':
-                raise NotImplementedError(f"CenterHead_GGA: {name}.reduction={red!r}; the HIP loss path implements "
+                raise NotImplementedError(f"{type(self).__name__}: {name}.reduction={red!r}; the HIP loss path implements "
                                           f"reduction='mean' (configs/gga/gga_kitti_config.py:59-60)")
 
     # ------------------------------------------------------------------ forward
@@ -187,9 +179,9 @@ class CenterHead_GGA(nn.Module):
             # the loss reads a regression map at cells[task] only (gather_pred): one launch marks the tiles of all tasks, and
             # those branches compute nothing else; the heat-map stays dense (the focal loss reads all of it)
             if len(cells) != len(self.task_heads):
-                raise ValueError(f'CenterHead_GGA: cells for {len(cells)} tasks, the head has {len(self.task_heads)}')
+                raise ValueError(f'{type(self).__name__}: cells for {len(cells)} tasks, the head has {len(self.task_heads)}')
             if any(c.shape[0] != x.shape[0] for c in cells):
-                raise ValueError('CenterHead_GGA: cells must be [B, K] per task, with the batch size of the feature map')
+                raise ValueError(f'{type(self).__name__}: cells must be [B, K] per task, with the batch size of the feature map')
             maps = F.head_cell_tiles(list(cells), x.shape[2], x.shape[3])
             tile_maps = [None if head == 'heatmap' else maps[ti] for ti, head in keys]
         outs = (F.head_branches(x, branches, sparse_grad=[head != 'heatmap' for _, head in keys], tile_maps=tile_maps)
@@ -211,12 +203,148 @@ class CenterHead_GGA(nn.Module):
             return multi_apply(self.forward_single, feats)
         return multi_apply(self.forward_single, feats, cells=cells)
 
-    # ------------------------------------------------------------------ targets
     def _feature_map_size(self):
         g = self.train_cfg['grid_size']
         osf = self.train_cfg['out_size_factor']
         return int(g[0]) // int(osf), int(g[1]) // int(osf)      # (W, H)
 
+    # ------------------------------------------------------------------ inference (SURVEY.md §8(f) rank 1)
+    def get_bboxes(self, preds_dicts, img_metas, img=None, rescale=False):
+        """Decode + per-task rotated NMS + merge (head:725-817). ``img_metas[i]['box_type_3d']``
+        builds the box structure (default ``LiDARInstance3DBoxes``). Returns
+        ``[[bboxes, scores, labels], ...]`` per sample."""
+        from .box3d import LiDARInstance3DBoxes
+        fast = self._get_bboxes_batched(preds_dicts, img_metas)
+        if fast is not None:
+            return fast
+        rets = []
+        for task_id, preds_dict in enumerate(preds_dicts):
+            pd = preds_dict[0]
+            batch_size = pd['heatmap'].shape[0]
+            batch_dim = torch.exp(pd['dim']) if self.norm_bbox else pd['dim']
+            temp = self.bbox_coder.decode(pd['heatmap'].sigmoid(), pd['rot'][:, 0].unsqueeze(1),
+                                          pd['rot'][:, 1].unsqueeze(1), pd['height'], batch_dim, pd.get('vel'),
+                                          reg=pd['reg'], task_id=task_id)
+            assert self.test_cfg['nms_type'] in ['circle', 'rotate']
+            if self.test_cfg['nms_type'] == 'circle':
+                ret_task = []
+                for i in range(batch_size):
+                    keep = circle_nms(torch.cat([temp[i]['bboxes'][:, :2], temp[i]['scores'].view(-1, 1)], 1),
+                                      self.test_cfg['min_radius'][task_id], self.test_cfg['post_max_size'])
+                    ret_task.append({k: temp[i][k][keep] for k in ('bboxes', 'scores', 'labels')})
+                rets.append(ret_task)
+            else:
+                rets.append(self.get_task_detections(self.num_classes[task_id], [b['scores'] for b in temp],
+                                                     [b['bboxes'] for b in temp], [b['labels'] for b in temp],
+                                                     img_metas))
+        ret_list = []
+        for i in range(len(rets[0])):
+            bboxes = torch.cat([ret[i]['bboxes'] for ret in rets])
+            bboxes[:, 2] = bboxes[:, 2] - bboxes[:, 5] * 0.5          # gravity centre -> bottom centre
+            box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
+            bboxes = box_type(bboxes, self.bbox_coder.code_size)
+            scores = torch.cat([ret[i]['scores'] for ret in rets])
+            flag, labels = 0, []
+            for j, num_class in enumerate(self.num_classes):
+                labels.append(rets[j][i]['labels'].int() + flag)
+                flag += num_class
+            ret_list.append([bboxes, scores, torch.cat(labels)])
+        return ret_list
+
+    # Round 6: all frames and tasks in ONE launch behind the coder's batched top-k decode (csrc/postproc.hip::
+    # centerpoint_detect_kernel - the same masks, NMS boxes, greedy order, range filter and merge as the loop below, which stays
+    # as the path for circle NMS, coders without ``decode_dense``, > 128 candidates per task, and CPU tensors; the two are
+    # compared detection by detection in tests/test_postproc_gpu.py). GGA_DETECT_BATCHED=0: off.
+    BATCHED = os.environ.get('GGA_DETECT_BATCHED', '1') != '0'
+
+    def _get_bboxes_batched(self, preds_dicts, img_metas):
+        from .box3d import LiDARInstance3DBoxes
+        tc, coder = self.test_cfg, self.bbox_coder
+        heat0 = preds_dicts[0][0]['heatmap']
+        if not (self.BATCHED and tc['nms_type'] == 'rotate' and heat0.is_cuda and hasattr(coder, 'decode_dense')
+                and coder.max_num <= 128 and coder.post_center_range is not None):
+            return None
+        boxes, scores, labels = [], [], []
+        for task_id, preds_dict in enumerate(preds_dicts):
+            pd = preds_dict[0]
+            batch_dim = torch.exp(pd['dim']) if self.norm_bbox else pd['dim']
+            b, s, l = coder.decode_dense(pd['heatmap'].sigmoid(), pd['rot'][:, 0].unsqueeze(1), pd['rot'][:, 1].unsqueeze(1),
+                                         pd['height'], batch_dim, pd.get('vel'), reg=pd['reg'], task_id=task_id)
+            boxes.append(b), scores.append(s), labels.append(l)
+        if len({tuple(b.shape) for b in boxes}) != 1:
+            return None
+        out_boxes, out_scores, out_labels, count = F.centerpoint_detect(
+            torch.stack(boxes), torch.stack(scores), torch.stack(labels), coder.post_center_range, coder.score_threshold,
+            tc['score_threshold'], tc['post_center_limit_range'], tc['nms_thr'], tc['pre_max_size'], tc['post_max_size'],
+            self.num_classes)
+        counts = count.tolist()                            # the one host read of the batch
+        ret_list = _BatchedDetections()
+        for i, n in enumerate(counts):
+            box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
+            view = out_boxes[i, :n]
+            ret_list.append([LiDARInstance3DBoxes.wrap(view, coder.code_size) if box_type is LiDARInstance3DBoxes
+                             else box_type(view, coder.code_size), out_scores[i, :n], out_labels[i, :n]])
+        ret_list.packed = (out_boxes, out_scores, out_labels, counts)
+        return ret_list
+
+    def get_task_detections(self, num_class_with_bg, batch_cls_preds, batch_reg_preds, batch_cls_labels, img_metas):
+        """Score threshold -> BEV rotated NMS (HIP) -> range filter, per sample (head:819-934)."""
+        from .box3d import LiDARInstance3DBoxes
+        tc = self.test_cfg
+        pcr = tc['post_center_limit_range']
+        if len(pcr) > 0:
+            pcr = torch.tensor(pcr, dtype=batch_reg_preds[0].dtype, device=batch_reg_preds[0].device)
+        out = []
+        for i, (box_preds, cls_preds, cls_labels) in enumerate(zip(batch_reg_preds, batch_cls_preds, batch_cls_labels)):
+            top_scores = cls_preds.squeeze(-1)
+            top_labels = (torch.zeros(cls_preds.shape[0], device=cls_preds.device, dtype=torch.long)
+                          if num_class_with_bg == 1 else cls_labels.long())
+            if tc['score_threshold'] > 0.0:
+                keep = top_scores >= tc['score_threshold']
+                top_scores = top_scores[keep]
+                if top_scores.shape[0] != 0:
+                    box_preds, top_labels = box_preds[keep], top_labels[keep]
+            if top_scores.shape[0] != 0:
+                box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
+                boxes_for_nms = ops.xywhr2xyxyr(box_type(box_preds[:, :], self.bbox_coder.code_size).bev)
+                selected = ops.nms_bev(boxes_for_nms, top_scores, thresh=tc['nms_thr'], pre_max_size=tc['pre_max_size'],
+                                       post_max_size=tc['post_max_size'])
+            else:
+                selected = []
+            sb, sl, ss = box_preds[selected], top_labels[selected], top_scores[selected]
+            if sb.shape[0] != 0:
+                if len(pcr) > 0:
+                    m = (sb[:, :3] >= pcr[:3]).all(1) & (sb[:, :3] <= pcr[3:]).all(1)
+                    sb, ss, sl = sb[m], ss[m], sl[m]
+                out.append(dict(bboxes=sb, scores=ss, labels=sl))
+            else:
+                dt, dev = batch_reg_preds[0].dtype, batch_reg_preds[0].device
+                out.append(dict(bboxes=torch.zeros([0, self.bbox_coder.code_size], dtype=dt, device=dev),
+                                scores=torch.zeros([0], dtype=dt, device=dev),
+                                labels=torch.zeros([0], dtype=top_labels.dtype, device=dev)))
+        return out
+
+
+@HEADS.register_module()
+class CenterHead_GGA(_CenterHeadBase):
+    _NO_VELOCITY = 'GGA does not support velocity (head:600-601)'
+
+    def __init__(self, in_channels=[128], tasks=None, train_cfg=None, test_cfg=None, bbox_coder=None,
+                 common_heads=dict(), loss_cls=dict(type='GaussianFocalLoss', reduction='mean'),
+                 loss_bbox=dict(type='L1Loss', reduction='none', loss_weight=0.25),
+                 loss_center=dict(type='MarginL1Loss', reduction='mean'),
+                 separate_head=dict(type='SeparateHead', init_bias=-2.19, final_kernel=3),
+                 share_conv_channel=64, num_heatmap_convs=2, conv_cfg=dict(type='Conv2d'),
+                 norm_cfg=dict(type='BN2d'), bias='auto', norm_bbox=True, init_cfg=None,
+                 pal_backprop=False):
+        self._build(in_channels, tasks, train_cfg, test_cfg, bbox_coder, common_heads, loss_cls, loss_bbox, separate_head,
+                    share_conv_channel, num_heatmap_convs, conv_cfg, norm_cfg, bias, norm_bbox, init_cfg)
+        # Stock mmdet's _parse_losses only back-propagates keys containing 'loss'; the PAL
+        # terms are stored as task{i}.distance* (head:697-699), i.e. logged, not trained.
+        # pal_backprop=True keeps the key names but lets the detector add them to the total.
+        self.pal_backprop = pal_backprop
+
+    # ------------------------------------------------------------------ targets
     def draw_srl(self, batch_size):
         """One ``clamp(N(mu_t, sigma_t), 1e-3)`` per (frame, task) from the default CPU torch
         generator, frame-major / task-minor — the same calls in the same order as head:514-525,
@@ -433,121 +561,97 @@ class CenterHead_GGA(nn.Module):
                 loss_dict[f'task{task_id}.loss_ratio'] = l_srl
         return loss_dict
 
-    # ------------------------------------------------------------------ inference (SURVEY.md §8(f) rank 1)
-    def get_bboxes(self, preds_dicts, img_metas, img=None, rescale=False):
-        """Decode + per-task rotated NMS + merge (head:725-817). ``img_metas[i]['box_type_3d']``
-        builds the box structure (default ``LiDARInstance3DBoxes``). Returns
-        ``[[bboxes, scores, labels], ...]`` per sample."""
-        from .box3d import LiDARInstance3DBoxes
-        fast = self._get_bboxes_batched(preds_dicts, img_metas)
-        if fast is not None:
-            return fast
-        rets = []
-        for task_id, preds_dict in enumerate(preds_dicts):
-            pd = preds_dict[0]
-            batch_size = pd['heatmap'].shape[0]
-            batch_dim = torch.exp(pd['dim']) if self.norm_bbox else pd['dim']
-            temp = self.bbox_coder.decode(pd['heatmap'].sigmoid(), pd['rot'][:, 0].unsqueeze(1),
-                                          pd['rot'][:, 1].unsqueeze(1), pd['height'], batch_dim, pd.get('vel'),
-                                          reg=pd['reg'], task_id=task_id)
-            assert self.test_cfg['nms_type'] in ['circle', 'rotate']
-            if self.test_cfg['nms_type'] == 'circle':
-                ret_task = []
-                for i in range(batch_size):
-                    keep = circle_nms(torch.cat([temp[i]['bboxes'][:, :2], temp[i]['scores'].view(-1, 1)], 1),
-                                      self.test_cfg['min_radius'][task_id], self.test_cfg['post_max_size'])
-                    ret_task.append({k: temp[i][k][keep] for k in ('bboxes', 'scores', 'labels')})
-                rets.append(ret_task)
-            else:
-                rets.append(self.get_task_detections(self.num_classes[task_id], [b['scores'] for b in temp],
-                                                     [b['bboxes'] for b in temp], [b['labels'] for b in temp],
-                                                     img_metas))
-        ret_list = []
-        for i in range(len(rets[0])):
-            bboxes = torch.cat([ret[i]['bboxes'] for ret in rets])
-            bboxes[:, 2] = bboxes[:, 2] - bboxes[:, 5] * 0.5          # gravity centre -> bottom centre
-            box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
-            bboxes = box_type(bboxes, self.bbox_coder.code_size)
-            scores = torch.cat([ret[i]['scores'] for ret in rets])
-            flag, labels = 0, []
-            for j, num_class in enumerate(self.num_classes):
-                labels.append(rets[j][i]['labels'].int() + flag)
-                flag += num_class
-            ret_list.append([bboxes, scores, torch.cat(labels)])
-        return ret_list
 
-    # Round 6: all frames and tasks in ONE launch behind the coder's batched top-k decode (csrc/postproc.hip::
-    # centerpoint_detect_kernel - the same masks, NMS boxes, greedy order, range filter and merge as the loop below, which stays
-    # as the path for circle NMS, coders without ``decode_dense``, > 128 candidates per task, and CPU tensors; the two are
-    # compared detection by detection in tests/test_postproc_gpu.py). GGA_DETECT_BATCHED=0: off.
-    BATCHED = os.environ.get('GGA_DETECT_BATCHED', '1') != '0'
+@HEADS.register_module()
+class CenterHead(_CenterHeadBase):
+    """The supervised CenterPoint head (centerpoint_head.py:243-639): trained on 3D boxes - ground truth, or the pseudo labels
+    a GGA run wrote. The boxes and labels of a batch go up in one staging buffer; ONE launch builds every task's heat maps,
+    ``ind``, ``mask`` and ``anno_box`` (functional.center_targets) where the reference loops over the objects in Python."""
+    MAX_RADIUS = 128
+    _NO_VELOCITY = ('CenterHead: with_velocity (a vel head in common_heads) is not supported: the target and loss kernels carry '
+                    'the 8-entry box code (reg, height, dim, rot)')
 
-    def _get_bboxes_batched(self, preds_dicts, img_metas):
-        from .box3d import LiDARInstance3DBoxes
-        tc, coder = self.test_cfg, self.bbox_coder
-        heat0 = preds_dicts[0][0]['heatmap']
-        if not (self.BATCHED and tc['nms_type'] == 'rotate' and heat0.is_cuda and hasattr(coder, 'decode_dense')
-                and coder.max_num <= 128 and coder.post_center_range is not None):
-            return None
-        boxes, scores, labels = [], [], []
-        for task_id, preds_dict in enumerate(preds_dicts):
-            pd = preds_dict[0]
-            batch_dim = torch.exp(pd['dim']) if self.norm_bbox else pd['dim']
-            b, s, l = coder.decode_dense(pd['heatmap'].sigmoid(), pd['rot'][:, 0].unsqueeze(1), pd['rot'][:, 1].unsqueeze(1),
-                                         pd['height'], batch_dim, pd.get('vel'), reg=pd['reg'], task_id=task_id)
-            boxes.append(b), scores.append(s), labels.append(l)
-        if len({tuple(b.shape) for b in boxes}) != 1:
-            return None
-        out_boxes, out_scores, out_labels, count = F.centerpoint_detect(
-            torch.stack(boxes), torch.stack(scores), torch.stack(labels), coder.post_center_range, coder.score_threshold,
-            tc['score_threshold'], tc['post_center_limit_range'], tc['nms_thr'], tc['pre_max_size'], tc['post_max_size'],
-            self.num_classes)
-        counts = count.tolist()                            # the one host read of the batch
-        ret_list = _BatchedDetections()
-        for i, n in enumerate(counts):
-            box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
-            view = out_boxes[i, :n]
-            ret_list.append([LiDARInstance3DBoxes.wrap(view, coder.code_size) if box_type is LiDARInstance3DBoxes
-                             else box_type(view, coder.code_size), out_scores[i, :n], out_labels[i, :n]])
-        ret_list.packed = (out_boxes, out_scores, out_labels, counts)
-        return ret_list
+    def __init__(self, in_channels=[128], tasks=None, train_cfg=None, test_cfg=None, bbox_coder=None,
+                 common_heads=dict(), loss_cls=dict(type='GaussianFocalLoss', reduction='mean'),
+                 loss_bbox=dict(type='L1Loss', reduction='none', loss_weight=0.25),
+                 separate_head=dict(type='SeparateHead', init_bias=-2.19, final_kernel=3),
+                 share_conv_channel=64, num_heatmap_convs=2, conv_cfg=dict(type='Conv2d'),
+                 norm_cfg=dict(type='BN2d'), bias='auto', norm_bbox=True, init_cfg=None):
+        self._build(in_channels, tasks, train_cfg, test_cfg, bbox_coder, common_heads, loss_cls, loss_bbox, separate_head,
+                    share_conv_channel, num_heatmap_convs, conv_cfg, norm_cfg, bias, norm_bbox, init_cfg)
 
-    def get_task_detections(self, num_class_with_bg, batch_cls_preds, batch_reg_preds, batch_cls_labels, img_metas):
-        """Score threshold -> BEV rotated NMS (HIP) -> range filter, per sample (head:819-934)."""
-        from .box3d import LiDARInstance3DBoxes
-        tc = self.test_cfg
-        pcr = tc['post_center_limit_range']
-        if len(pcr) > 0:
-            pcr = torch.tensor(pcr, dtype=batch_reg_preds[0].dtype, device=batch_reg_preds[0].device)
-        out = []
-        for i, (box_preds, cls_preds, cls_labels) in enumerate(zip(batch_reg_preds, batch_cls_preds, batch_cls_labels)):
-            top_scores = cls_preds.squeeze(-1)
-            top_labels = (torch.zeros(cls_preds.shape[0], device=cls_preds.device, dtype=torch.long)
-                          if num_class_with_bg == 1 else cls_labels.long())
-            if tc['score_threshold'] > 0.0:
-                keep = top_scores >= tc['score_threshold']
-                top_scores = top_scores[keep]
-                if top_scores.shape[0] != 0:
-                    box_preds, top_labels = box_preds[keep], top_labels[keep]
-            if top_scores.shape[0] != 0:
-                box_type = (img_metas[i].get('box_type_3d') if isinstance(img_metas[i], dict) else None) or LiDARInstance3DBoxes
-                boxes_for_nms = ops.xywhr2xyxyr(box_type(box_preds[:, :], self.bbox_coder.code_size).bev)
-                selected = ops.nms_bev(boxes_for_nms, top_scores, thresh=tc['nms_thr'], pre_max_size=tc['pre_max_size'],
-                                       post_max_size=tc['post_max_size'])
-            else:
-                selected = []
-            sb, sl, ss = box_preds[selected], top_labels[selected], top_scores[selected]
-            if sb.shape[0] != 0:
-                if len(pcr) > 0:
-                    m = (sb[:, :3] >= pcr[:3]).all(1) & (sb[:, :3] <= pcr[3:]).all(1)
-                    sb, ss, sl = sb[m], ss[m], sl[m]
-                out.append(dict(bboxes=sb, scores=ss, labels=sl))
-            else:
-                dt, dev = batch_reg_preds[0].dtype, batch_reg_preds[0].device
-                out.append(dict(bboxes=torch.zeros([0, self.bbox_coder.code_size], dtype=dt, device=dev),
-                                scores=torch.zeros([0], dtype=dt, device=dev),
-                                labels=torch.zeros([0], dtype=top_labels.dtype, device=dev)))
-        return out
+    def pack_targets(self, gt_bboxes_3d, gt_labels_3d):
+        """Host half of ``get_targets``: the batch's boxes and labels as flat arrays, the frames' offsets, and a bound of the
+        gaussian radii (what the patch table has to reach). numpy only."""
+        tc = self.train_cfg
+        boxes = [_to_np(getattr(b, 'tensor', b), np.float32).reshape(-1, 7) for b in gt_bboxes_3d]
+        labels = [_to_np(l, np.int64).reshape(-1) for l in gt_labels_3d]
+        if len(boxes) != len(labels) or any(len(b) != len(l) for b, l in zip(boxes, labels)):
+            raise ValueError('CenterHead.get_targets: one label per box in every frame')
+        offs = np.zeros(len(boxes) + 1, np.int32)
+        offs[1:] = np.cumsum([len(b) for b in boxes])
+        boxes = np.concatenate(boxes) if boxes else np.zeros((0, 7), np.float32)
+        labels = np.concatenate(labels) if labels else np.zeros(0, np.int64)
+        max_radius = int(tc['min_radius'])
+        if len(boxes):
+            osf = float(tc['out_size_factor'])
+            w = boxes[:, 3].astype(np.float64) / float(tc['voxel_size'][0]) / osf
+            l = boxes[:, 4].astype(np.float64) / float(tc['voxel_size'][1]) / osf
+            ok = (w > 0) & (l > 0) & np.isfinite(w) & np.isfinite(l)
+            if ok.any():
+                # (a bound, not the radius: one more than the f64 value covers the f32 rounding of the scaled sizes)
+                max_radius = max(max_radius, int(min(gaussian_radius_np(l[ok], w[ok], tc['gaussian_overlap']).max() + 1, 1 << 20)))
+        return dict(boxes=boxes, labels=labels, frame_offsets=offs, max_radius=max_radius)
+
+    def get_targets(self, gt_bboxes_3d, gt_labels_3d, device=None):
+        """-> ``heatmaps, anno_boxes, inds, masks``: per-task lists of ``[B, n_cls_t, H, W]``, ``[B, K, 8]``, ``[B, K]`` i64 and
+        ``[B, K]`` u8 device tensors (centerpoint_head.py:388-583)."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        pk = self.pack_targets(gt_bboxes_3d, gt_labels_3d)
+        prm = F.center_params(self.train_cfg, self.num_classes)
+        if pk['max_radius'] > self.MAX_RADIUS:
+            raise ValueError(f"CenterHead.get_targets: a box with gaussian radius {pk['max_radius']} > {self.MAX_RADIUS} cells "
+                             f"(the patch table grows with the cube of the radius); filter such boxes out of the annotations")
+        up = F.upload_many({k: pk[k] for k in ('boxes', 'labels', 'frame_offsets')}, dev)
+        heat, anno, ind, mask = F.center_targets(up['boxes'], up['labels'], up['frame_offsets'], prm,
+                                                 max_radius=max(16, pk['max_radius']))
+        B, hw = len(gt_labels_3d), prm.H * prm.W
+        heatmaps, c = [], 0
+        for n in self.num_classes:
+            hm = heat[B * c * hw:B * (c + n) * hw]
+            if (B * c * hw) % 4:             # the focal loss reads 16-byte vectors
+                hm = hm.clone()
+            heatmaps.append(hm.view(B, n, prm.H, prm.W))
+            c += n
+        return heatmaps, list(anno.unbind(0)), list(ind.unbind(0)), list(mask.unbind(0))
+
+    def loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts, **kwargs):
+        heatmaps, anno_boxes, inds, masks = self.get_targets(gt_bboxes_3d, gt_labels_3d,
+                                                             device=preds_dicts[0][0]['heatmap'].device)
+        return self.loss_from_targets(preds_dicts, heatmaps, anno_boxes, inds, masks)
+
+    def loss_from_targets(self, preds_dicts, heatmaps, anno_boxes, inds, masks):
+        """Exactly ``task{i}.loss_heatmap`` and ``task{i}.loss_bbox`` per task (centerpoint_head.py:598-639). Every stage runs
+        once for all tasks, or task by task where their maps differ in size: the same values bit for bit."""
+        code_weights = self.train_cfg.get('code_weights', None)
+        if code_weights is None or len(code_weights) != 8:
+            raise ValueError(f'CenterHead: train_cfg.code_weights must hold 8 entries (reg 2, height, dim 3, rot 2), got {code_weights}')
+        weights = F.center_loss_weights(code_weights, self.loss_bbox.loss_weight)
+        loss_dict = dict()
+        T = len(preds_dicts)
+        groups = [range(T)] if CenterHead_GGA._tasks_share_a_launch(preds_dicts, inds) else [[t] for t in range(T)]
+        for group in groups:
+            pds = [preds_dicts[t][0] for t in group]
+            l_heat, _ = F.gaussian_focal_loss_tasks([pd['heatmap'] for pd in pds], [heatmaps[t] for t in group],
+                                                    alpha=self.loss_cls.alpha, gamma=self.loss_cls.gamma,
+                                                    scale=self.loss_cls.loss_weight)
+            preds = F.gather_pred_tasks([(pd['reg'], pd['height'], pd['dim'], pd['rot']) for pd in pds],
+                                        [inds[t] for t in group], [masks[t] for t in group])
+            l_box = F.center_reg_loss_tasks(preds, [anno_boxes[t] for t in group], [masks[t] for t in group], weights)
+            for task_id, loss_heatmap, loss_bbox in zip(group, l_heat, l_box):
+                loss_dict[f'task{task_id}.loss_heatmap'] = loss_heatmap
+                loss_dict[f'task{task_id}.loss_bbox'] = loss_bbox
+        return loss_dict
 
 
 class _BatchedDetections(list):

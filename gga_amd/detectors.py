@@ -386,3 +386,32 @@ class GGA(MVXTwoStageDetector_GGA):
     @property
     def with_velocity(self):
         return self.pts_bbox_head is not None and self.pts_bbox_head.with_velocity
+
+
+@DETECTORS.register_module()
+class CenterPoint(MVXTwoStageDetector_GGA):
+    """The supervised CenterPoint detector (mmdet3d/models/detectors/centerpoint.py:9-60): the machinery above - voxelise,
+    encoders, trunk, ``prepare_inputs``, the test paths and TTA - trained on 3D boxes through ``dense_heads.CenterHead``."""
+
+    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None, gt_bboxes=None,
+                      img=None, proposals=None, gt_bboxes_ignore=None):
+        img_feats, pts_feats = self.extract_feat(points, img=img, img_metas=img_metas)
+        losses = dict()
+        if pts_feats:
+            losses.update(self.forward_pts_train(pts_feats, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore))
+        return losses
+
+    def forward_pts_train(self, pts_feats, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore=None):
+        head = self.pts_bbox_head
+        if dense_heads.FWD_CELLS and isinstance(head, dense_heads.CenterHead):
+            # targets first (they depend on the ground truth alone), so that the head computes its regression maps only
+            # where the loss gathers them
+            targets = head.get_targets(gt_bboxes_3d, gt_labels_3d, device=pts_feats[0].device)
+            outs = head(pts_feats, cells=targets[2])
+            return head.loss_from_targets(outs, *targets)
+        outs = head(pts_feats)
+        return head.loss(gt_bboxes_3d, gt_labels_3d, outs)
+
+    @property
+    def with_velocity(self):
+        return self.pts_bbox_head is not None and self.pts_bbox_head.with_velocity

@@ -727,6 +727,134 @@ def box_losses(pred, ind, mask, anno_box, lidar2img, bound_mask, ibp_xy, ibp_off
     return torch.stack(terms), box_out
 
 
+# ----------------------------------------------------------------------------- supervised CenterPoint targets and loss
+_center_params_cache = {}
+
+
+def center_params(train_cfg, num_classes):
+    """The POD of ``gga_center_targets`` for a head whose task t holds ``num_classes[t]`` classes; built once per
+    (config object, layout)."""
+    key = (id(train_cfg), tuple(int(n) for n in num_classes))
+    hit = _center_params_cache.get(key)
+    if hit is not None and hit[0] is train_cfg:
+        return hit[1]
+    T, n_cls = len(num_classes), int(sum(num_classes))
+    if not 1 <= T <= _lib.MAX_TASKS or not 1 <= n_cls <= _lib.CENTER_MAX_CLASSES:
+        raise ValueError(f'center targets: {T} tasks / {n_cls} classes; a launch takes 1..{_lib.MAX_TASKS} tasks and '
+                         f'1..{_lib.CENTER_MAX_CLASSES} classes')
+    prm = _lib.CenterParams()
+    prm.pc_range[:] = [float(v) for v in train_cfg['point_cloud_range'][:2]]
+    prm.voxel_size[:] = [float(v) for v in train_cfg['voxel_size'][:2]]
+    prm.out_size_factor = float(train_cfg['out_size_factor'])
+    prm.gaussian_overlap = float(train_cfg['gaussian_overlap'])
+    prm.min_radius = int(train_cfg['min_radius'])
+    prm.K = int(train_cfg['max_objs']) * int(train_cfg['dense_reg'])
+    prm.W = int(train_cfg['grid_size'][0]) // int(train_cfg['out_size_factor'])
+    prm.H = int(train_cfg['grid_size'][1]) // int(train_cfg['out_size_factor'])
+    prm.n_tasks, prm.n_classes = T, n_cls
+    c = 0
+    for t, n in enumerate(num_classes):
+        prm.task_classes[t], prm.task_class_base[t] = int(n), c
+        for i in range(int(n)):
+            prm.class_task[c], prm.class_index[c] = t, i
+            c += 1
+    _center_params_cache[key] = (train_cfg, prm)
+    return prm
+
+
+@torch.no_grad()
+def center_targets(boxes, labels, frame_offsets, prm, max_radius=16):
+    """The supervised CenterPoint targets of a batch in one launch (centerpoint_head.py:435-583). ``boxes [N,7]`` f32,
+    ``labels [N]`` i64, ``frame_offsets [B+1]`` i32 on the device; ``max_radius``: a bound of the batch's gaussian radii (the
+    patch table reaches it). -> ``heat`` (flat, task t = the [B, n_cls_t, H, W] block at B * class base of t * H * W),
+    ``anno_box [T,B,K,8]``, ``ind [T,B,K]``, ``mask [T,B,K]``."""
+    _need_cuda(boxes, labels, frame_offsets)
+    dev = boxes.device
+    B = frame_offsets.numel() - 1
+    T, K = prm.n_tasks, prm.K
+    if boxes.dtype != torch.float32 or labels.dtype != torch.int64 or frame_offsets.dtype != torch.int32:
+        raise TypeError('center_targets: boxes f32, labels i64, frame_offsets i32')
+    if boxes.numel() != labels.numel() * 7:
+        raise ValueError('center_targets: boxes must be [N, 7] for labels [N]')
+    max_radius = max(int(max_radius), prm.min_radius)
+    table, offs = gaussian_patch_table(max_radius, dev)
+    heat = torch.empty(B * prm.n_classes * prm.H * prm.W, dtype=torch.float32, device=dev)
+    anno = torch.empty((T, B, K, 8), dtype=torch.float32, device=dev)
+    ind = torch.empty((T, B, K), dtype=torch.int64, device=dev)
+    mask = torch.empty((T, B, K), dtype=torch.uint8, device=dev)
+    boxes, labels, frame_offsets = boxes.contiguous(), labels.contiguous(), frame_offsets.contiguous()
+    check(_lib.lib().gga_center_targets(_p(boxes), _p(labels), _p(frame_offsets), B, C.byref(prm), _p(ind), _p(mask), _p(anno),
+                                        _p(heat), _p(table), _p(offs), max_radius, _stream()), 'gga_center_targets')
+    return heat, anno, ind, mask
+
+
+def center_loss_weights(code_weights, loss_weight):
+    w = _lib.CenterLossWeights()
+    code_weights = [float(v) for v in code_weights]
+    if len(code_weights) != 8:
+        raise ValueError(f'center_reg_loss: {len(code_weights)} code_weights; the box code has 8 entries')
+    w.code_weights[:] = code_weights
+    w.loss_weight = float(loss_weight)
+    return w
+
+
+class _CenterRegLoss(torch.autograd.Function):
+    """The code-weighted masked L1 of all tasks of a head: one launch each way (gga_center_reg_loss_*). Inputs: per task pred,
+    anno_box, mask; outputs: T losses."""
+
+    @staticmethod
+    def forward(ctx, w, *args):
+        T = len(args) // 3
+        _need_cuda(*args)
+        B, K = args[2].shape
+        keep = [a.contiguous() for a in args]
+        out = torch.empty((T, 2), dtype=torch.float32, device=args[0].device)
+        tb = _lib.CenterLossTable()
+        tb.n_tasks = T
+        for t in range(T):
+            e = tb.task[t]
+            e.pred, e.anno_box, e.mask, e.loss = _p(keep[3 * t]), _p(keep[3 * t + 1]), _p(keep[3 * t + 2]), out.data_ptr() + 8 * t
+        check(_lib.lib().gga_center_reg_loss_fwd(C.byref(tb), B, K, C.byref(w), _stream()), 'gga_center_reg_loss_fwd')
+        ctx.save_for_backward(out, *keep)
+        ctx.cfg = (w, T, B, K)
+        ctx.set_materialize_grads(False)
+        return tuple(out[:, 0].unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        out, *keep = ctx.saved_tensors
+        w, T, B, K = ctx.cfg
+        live = [t for t in range(T) if gs[t] is not None]
+        res = [None] * (1 + 3 * T)
+        if not live:
+            return tuple(res)
+        tb = _lib.CenterLossTable()
+        tb.n_tasks = len(live)
+        g = []
+        for j, t in enumerate(live):
+            g.append(gs[t].contiguous().float())
+            res[1 + 3 * t] = torch.empty((B, K, 8), dtype=torch.float32, device=out.device)
+            e = tb.task[j]
+            e.pred, e.anno_box, e.mask, e.loss = _p(keep[3 * t]), _p(keep[3 * t + 1]), _p(keep[3 * t + 2]), out.data_ptr() + 8 * t
+            e.grad_loss, e.grad_pred = _p(g[-1]), _p(res[1 + 3 * t])
+        check(_lib.lib().gga_center_reg_loss_bwd(C.byref(tb), B, K, C.byref(w), _stream()), 'gga_center_reg_loss_bwd')
+        return tuple(res)
+
+
+def center_reg_loss_tasks(preds, anno_boxes, masks, weights):
+    """``loss_weight * sum(mask * [anno not NaN] * code_weights * |pred - anno|) / (sum(mask) + 1e-4 + eps)`` of every task
+    (centerpoint_head.py:623-638 with L1Loss(reduction='mean')) in one launch each way; ``weights`` = ``center_loss_weights``.
+    ``preds[t]`` [B,K,8] (``gather_pred_tasks``), ``anno_boxes[t]`` [B,K,8], ``masks[t]`` [B,K] u8 -> T device scalars."""
+    if not 1 <= len(preds) <= _lib.MAX_TASKS:
+        raise ValueError(f'{len(preds)} tasks: the loss kernels take 1..{_lib.MAX_TASKS} per launch')
+    args = []
+    for p, a, m in zip(preds, anno_boxes, masks):
+        if p.shape != a.shape or p.shape[-1] != 8 or tuple(m.shape) != tuple(p.shape[:2]) or m.dtype != torch.uint8:
+            raise ValueError('center_reg_loss: pred and anno_box [B,K,8] f32, mask [B,K] u8')
+        args += [p, a, m]
+    return _CenterRegLoss.apply(weights, *args)
+
+
 # ----------------------------------------------------------------------------- fused BN (+res) (+ReLU)
 class _BNActBlocks(torch.autograd.Function):
     """``cat([act_i(bn_i(x_i) + residual_i)], dim=1)`` over ``n >= 1`` column blocks (gga_bn_relu_fwd / gga_bn_relu_bwd, whose

@@ -443,6 +443,46 @@ class ObjectRangeFilter_GGA:
         return d
 
 
+@PIPELINES.register_module()
+class ObjectRangeFilter:
+    """transforms_3d.py:890-938: keep the boxes whose centre lies strictly inside the BEV range; yaw to [-pi, pi)."""
+
+    def __init__(self, point_cloud_range):
+        self.pcd_range = np.array(point_cloud_range, dtype=np.float32)
+
+    def __call__(self, d):
+        boxes = d['gt_bboxes_3d']
+        if not isinstance(boxes, LiDARInstance3DBoxes):
+            raise NotImplementedError(f'ObjectRangeFilter: {type(boxes).__name__}; LiDAR boxes are supported')
+        mask = boxes.in_range_bev(self.pcd_range[[0, 1, 3, 4]])
+        boxes = boxes[mask]
+        boxes.limit_yaw(offset=0.5, period=2 * np.pi)
+        d['gt_bboxes_3d'] = boxes
+        d['gt_labels_3d'] = d['gt_labels_3d'][mask.numpy().astype(bool)]
+        return d
+
+    def __repr__(self):
+        return f'{type(self).__name__}(point_cloud_range={self.pcd_range.tolist()})'
+
+
+@PIPELINES.register_module()
+class ObjectNameFilter:
+    """transforms_3d.py:987-1020: keep the objects whose label is one of ``classes``' indices (drops label -1)."""
+
+    def __init__(self, classes):
+        self.classes = classes
+        self.labels = list(range(len(self.classes)))
+
+    def __call__(self, d):
+        mask = np.array([n in self.labels for n in d['gt_labels_3d']], dtype=np.bool_)
+        d['gt_bboxes_3d'] = d['gt_bboxes_3d'][torch.from_numpy(mask)]
+        d['gt_labels_3d'] = d['gt_labels_3d'][mask]
+        return d
+
+    def __repr__(self):
+        return f'{type(self).__name__}(classes={self.classes})'
+
+
 # ----------------------------------------------------------------------------- formatting
 @PIPELINES.register_module()
 class DefaultFormatBundle3D_GGA:
@@ -534,8 +574,8 @@ def _rotate_points_z(points, angle):
 
 def _move_boxes(d, what, *args):
     """The box fields follow the points through the box structure's method ``what``, for the structures that declare
-    ``MOVES_WITH_POINTS`` (the Depth boxes of the indoor pipelines; the GGA train pipeline has no such transform, and its
-    LiDAR boxes are refused as before)."""
+    ``MOVES_WITH_POINTS`` (the Depth boxes of the indoor pipelines and the LiDAR boxes of the supervised CenterPoint pipeline;
+    the GGA train pipeline has no such transform). The boxes draw nothing: the points' random stream is what it was."""
     for field in d.get('bbox3d_fields', []):
         if len(d[field]):
             if not getattr(d[field], 'MOVES_WITH_POINTS', False):

@@ -870,6 +870,74 @@ int gga_box_losses_fwd(const gga_task_table* tasks, const gga_loss_params* prm, 
 int gga_box_losses_bwd(const gga_task_table* tasks, int B, int K, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Supervised CenterPoint: the targets of a batch in one launch, and the      */
+/* code-weighted masked L1 of all tasks in one launch each way.               */
+/* Replaces the per-object Python loop of                                     */
+/* mmdet3d/models/dense_heads/centerpoint_head.py:435-583 (several tiny       */
+/* host-to-device copies per object) and the loss assembly of :623-638.       */
+/* ------------------------------------------------------------------------- */
+#define GGA_CENTER_MAX_CLASSES 64
+#define GGA_CENTER_MAX_K 512
+typedef struct {
+    float pc_range[2];            /* train_cfg.point_cloud_range[:2] */
+    float voxel_size[2];          /* train_cfg.voxel_size[:2] */
+    float out_size_factor;
+    float gaussian_overlap;
+    int32_t min_radius;
+    int32_t K;                    /* max_objs * dense_reg slots per (frame, task), 1 .. GGA_CENTER_MAX_K */
+    int32_t H, W;                 /* feature-map size */
+    int32_t n_tasks;              /* 1 .. GGA_MAX_TASKS */
+    int32_t n_classes;            /* 1 .. GGA_CENTER_MAX_CLASSES, the sum of task_classes */
+    int32_t task_classes[GGA_MAX_TASKS];        /* classes of task t */
+    int32_t task_class_base[GGA_MAX_TASKS];     /* classes of the tasks before t */
+    int32_t class_task[GGA_CENTER_MAX_CLASSES]; /* label -> task */
+    int32_t class_index[GGA_CENTER_MAX_CLASSES];/* label -> index inside its task */
+} gga_center_params;
+
+/* boxes [N,7] f32 (x, y, z bottom centre, dx, dy, dz, yaw) and labels [N] i64 of the whole batch, frame f being rows
+ * frame_offsets[f] .. frame_offsets[f+1] (frame_offsets [B+1] i32, on the device like the rest). One workgroup per (frame,
+ * task). An object goes to the task of its label (label < 0 or >= n_classes: dropped); its slot inside the (frame, task) is
+ * its rank class-major, then by object index; ranks >= K are dropped. An object whose scaled width or length is <= 0 or whose
+ * integer cell lies off the map keeps its slot, which stays empty. Outputs, every element written (zero where empty):
+ *   ind       [n_tasks, B, K] i64   cy * W + cx
+ *   mask      [n_tasks, B, K] u8
+ *   anno_box  [n_tasks, B, K, 8] f32  (cx_f - cx, cy_f - cy, z + dz / 2, log dx, log dy, log dz, sin yaw, cos yaw)
+ *   heatmaps  [B * n_classes * H * W] f32: task t is the [B, task_classes[t], H, W] block at B * task_class_base[t] * H * W;
+ *             cleared here, then max-splatted from patch_table / patch_offsets (as gga_heatmap_splat takes them) with
+ *             radius = max(min_radius, int(gaussian_radius((length, width), gaussian_overlap))). The table must reach the
+ *             largest radius of the batch: an object with radius > max_radius is not splatted. */
+int gga_center_targets(const float* boxes, const int64_t* labels, const int32_t* frame_offsets, int B,
+                       const gga_center_params* prm, int64_t* ind, uint8_t* mask, float* anno_box, float* heatmaps,
+                       const float* patch_table, const int32_t* patch_offsets, int max_radius, void* stream);
+
+typedef struct {
+    const float* pred;            /* [B,K,8] from gga_gather_pred_fwd */
+    const float* anno_box;        /* [B,K,8]; a NaN element has weight 0 in the loss and in the gradient */
+    const uint8_t* mask;          /* [B,K] */
+    float* loss;                  /* [2] = (loss, sum(mask)), written by the forward and read by the backward */
+    const float* grad_loss;       /* [1] d / d loss */
+    float* grad_pred;             /* [B,K,8], every element written */
+} gga_center_loss_task;
+
+typedef struct {
+    int32_t n_tasks;              /* 1 .. GGA_MAX_TASKS */
+    gga_center_loss_task task[GGA_MAX_TASKS];
+} gga_center_loss_table;
+
+typedef struct {
+    float code_weights[8];        /* train_cfg.code_weights */
+    float loss_weight;            /* L1Loss.loss_weight */
+} gga_center_loss_weights;
+
+/* loss[0] = loss_weight * sum(mask * [anno_box not NaN] * code_weights[c] * |pred - anno_box|) / ((sum(mask) + 1e-4) + eps_f32)
+ * per task, reduced in a fixed order without floating-point atomics: the same inputs give the same bits, and a task's value
+ * does not depend on the other tasks of the table. pred and anno_box must be 16-byte aligned. */
+int gga_center_reg_loss_fwd(const gga_center_loss_table* tasks, int B, int K, const gga_center_loss_weights* weights,
+                            void* stream);
+int gga_center_reg_loss_bwd(const gga_center_loss_table* tasks, int B, int K, const gga_center_loss_weights* weights,
+                            void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* SURVEY.md §8(f) rank 1 — inference / pseudo-label post-processing.        */
 /* ------------------------------------------------------------------------- */
 /* Rotated BEV IoU. Replaces mmcv.ops.box_iou_rotated as called by
