@@ -110,6 +110,26 @@ class CenterLossWeights(C.Structure):
     _fields_ = [('code_weights', C.c_float * 8), ('loss_weight', C.c_float)]
 
 
+ANCHOR_MAX_GROUPS = 16      # GGA_ANCHOR_MAX_GROUPS
+ANCHOR_LOSS_WORKSPACE_BYTES = 24576      # GGA_ANCHOR_LOSS_WORKSPACE_BYTES
+
+
+class AnchorParams(C.Structure):
+    """gga_anchor_params: the assigners' thresholds per anchor-size group and the head's target options."""
+    _fields_ = [('n_groups', C.c_int32), ('n_rot', C.c_int32), ('num_classes', C.c_int32), ('assign_per_class', C.c_int32),
+                ('pos_iou_thr', C.c_float * ANCHOR_MAX_GROUPS), ('neg_iou_thr', C.c_float * ANCHOR_MAX_GROUPS),
+                ('min_pos_iou', C.c_float * ANCHOR_MAX_GROUPS), ('pos_weight', C.c_float), ('dir_offset', C.c_float),
+                ('dir_limit_offset', C.c_float)]
+
+
+class AnchorLossParams(C.Structure):
+    """gga_anchor_loss_params: shapes, the (batch, channel, pixel) strides of the three prediction maps, loss constants."""
+    _fields_ = [('B', C.c_int32), ('HW', C.c_int32), ('n_anchors', C.c_int32), ('num_classes', C.c_int32),
+                ('diff_rad_by_sin', C.c_int32), ('reserved', C.c_int32), ('cls_stride', C.c_int64 * 3),
+                ('reg_stride', C.c_int64 * 3), ('dir_stride', C.c_int64 * 3), ('gamma', C.c_float), ('alpha', C.c_float),
+                ('beta', C.c_float), ('code_weight', C.c_float * 7), ('loss_weight', C.c_float * 3)]
+
+
 class LossParams(C.Structure):
     _fields_ = [('B', C.c_int32), ('K', C.c_int32), ('fm_w', C.c_int32),
                 ('voxel_size', C.c_float * 2), ('out_size_factor', C.c_float),
@@ -221,6 +241,11 @@ SIGNATURES = {
     'gga_center_targets': (i32, [vp, vp, vp, i32, C.POINTER(CenterParams), vp, vp, vp, vp, vp, vp, i32, vp]),
     'gga_center_reg_loss_fwd': (i32, [C.POINTER(CenterLossTable), i32, i32, C.POINTER(CenterLossWeights), vp]),
     'gga_center_reg_loss_bwd': (i32, [C.POINTER(CenterLossTable), i32, i32, C.POINTER(CenterLossWeights), vp]),
+    'gga_anchor_targets_workspace_bytes': (sz, [i64, i32]),
+    'gga_anchor_targets': (i32, [vp, i32, C.POINTER(AnchorParams), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'gga_anchor_loss_fwd': (i32, [C.POINTER(AnchorLossParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'gga_anchor_loss_bwd': (i32, [C.POINTER(AnchorLossParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'gga_anchor_decode': (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_int64 * 3), vp, C.POINTER(C.c_int64 * 3), vp, vp, vp, vp]),
     'gga_box_iou_rotated': (i32, [vp, i32, vp, i32, i32, i32, vp, vp]),
     'gga_nms_rotated_workspace_bytes': (sz, [i32]),
     'gga_nms_rotated_sorted': (i32, [vp, i32, f32, i32, vp, vp, vp, sz, vp]),

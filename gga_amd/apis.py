@@ -133,8 +133,9 @@ def generate_pseudo_labels(cfg, checkpoint, out=None, eval_metrics=('mAP',), eva
     if model is None:
         cfg.model['train_cfg'] = None
         mcfg = cfg.model
-        if channels_last and mcfg.get('pts_middle_encoder', {}).get('type') in ('PointPillarsScatter', 'SparseEncoder'):
-            mcfg['pts_middle_encoder']['channels_last'] = True
+        for key in ('pts_middle_encoder', 'middle_encoder'):          # (the second: VoxelNet's key)
+            if channels_last and (mcfg.get(key) or {}).get('type') in ('PointPillarsScatter', 'SparseEncoder'):
+                mcfg[key]['channels_last'] = True
         model = build_detector(mcfg, test_cfg=cfg.get('test_cfg'))
         meta = load_weights(model, checkpoint)
         model.CLASSES = meta.get('CLASSES', dataset.CLASSES)

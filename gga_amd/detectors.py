@@ -415,3 +415,53 @@ class CenterPoint(MVXTwoStageDetector_GGA):
     @property
     def with_velocity(self):
         return self.pts_bbox_head is not None and self.pts_bbox_head.with_velocity
+
+
+def _alias(name):
+    return property(lambda self: self._modules.get(name))
+
+
+@DETECTORS.register_module()
+class VoxelNet(MVXTwoStageDetector_GGA):
+    """The single-stage LiDAR detector of SECOND and PointPillars (mmdet3d/models/detectors/voxelnet.py:14-130,
+    single_stage.py:8-70): ``voxel_layer`` -> ``voxel_encoder`` -> ``middle_encoder`` -> ``backbone`` -> ``neck`` -> ``bbox_head``.
+    The modules are registered under those names, so the parameters are ``voxel_encoder.*``, ``middle_encoder.*``, ``backbone.*``,
+    ``neck.*`` and ``bbox_head.*`` as in the reference; the ``pts_*`` names of ``MVXTwoStageDetector_GGA`` are read-only aliases
+    of them, through which its machinery (batched voxelisation, ``prepare_inputs``, the trunk, results to the host) runs
+    unchanged. A frame's result is the plain ``dict(boxes_3d, scores_3d, labels_3d)``."""
+    pts_voxel_layer, pts_voxel_encoder, pts_middle_encoder = _alias('voxel_layer'), _alias('voxel_encoder'), _alias('middle_encoder')
+    pts_backbone, pts_neck, pts_bbox_head = _alias('backbone'), _alias('neck'), _alias('bbox_head')
+
+    def __init__(self, voxel_layer, voxel_encoder, middle_encoder, backbone, neck=None, bbox_head=None, train_cfg=None,
+                 test_cfg=None, init_cfg=None, pretrained=None):
+        nn.Module.__init__(self)
+        self.fp16_enabled = False
+        self.voxel_layer = Voxelization(**voxel_layer)
+        self.voxel_encoder = build_voxel_encoder(voxel_encoder)
+        self.middle_encoder = build_middle_encoder(middle_encoder)
+        self.backbone = build_backbone(backbone)
+        if neck is not None:
+            self.neck = build_neck(neck)
+        if bbox_head is not None:
+            self.bbox_head = build_head(dict(bbox_head, train_cfg=train_cfg, test_cfg=test_cfg))
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def extract_feat(self, points, img_metas=None):
+        """-> the neck's feature maps (voxelnet.py:37-48)."""
+        return self.extract_pts_feat(points, None, img_metas)
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes_ignore=None, **kwargs):
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        return self.bbox_head.loss(*outs, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+
+    @torch.no_grad()
+    def simple_test(self, points, img_metas, imgs=None, rescale=False):
+        from .box3d import bbox3d2result
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        bbox_list = self.bbox_head.get_bboxes(*outs, img_metas, rescale=rescale)
+        return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
+
+    def aug_test(self, points, img_metas, imgs=None, rescale=False):
+        raise NotImplementedError('VoxelNet.aug_test: test-time augmentation of the anchor head is not supported')

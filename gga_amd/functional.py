@@ -855,6 +855,165 @@ def center_reg_loss_tasks(preds, anno_boxes, masks, weights):
     return _CenterRegLoss.apply(weights, *args)
 
 
+# ----------------------------------------------------------------------------- Anchor3DHead: targets, losses, decode
+def anchor_params(pos_iou_thr, neg_iou_thr, min_pos_iou, n_rot, num_classes, assign_per_class, pos_weight, dir_offset,
+                  dir_limit_offset):
+    """The POD of ``gga_anchor_targets``: one (pos_iou_thr, neg_iou_thr, min_pos_iou) per assigner = anchor-size group."""
+    n_groups = len(pos_iou_thr)
+    if not 1 <= n_groups <= _lib.ANCHOR_MAX_GROUPS or len(neg_iou_thr) != n_groups or len(min_pos_iou) != n_groups:
+        raise ValueError(f'anchor targets: {n_groups} assigners; a launch takes 1..{_lib.ANCHOR_MAX_GROUPS}')
+    prm = _lib.AnchorParams()
+    prm.n_groups, prm.n_rot, prm.num_classes, prm.assign_per_class = n_groups, int(n_rot), int(num_classes), int(bool(assign_per_class))
+    for g in range(n_groups):
+        prm.pos_iou_thr[g], prm.neg_iou_thr[g], prm.min_pos_iou[g] = float(pos_iou_thr[g]), float(neg_iou_thr[g]), float(min_pos_iou[g])
+    prm.pos_weight, prm.dir_offset, prm.dir_limit_offset = float(pos_weight), float(dir_offset), float(dir_limit_offset)
+    return prm
+
+
+@torch.no_grad()
+def anchor_targets(anchors, prm, boxes, labels, frame_offsets, frame_offsets_host):
+    """The Anchor3DHead targets of a batch (train_mixins.py:12-316) in two launches and no read-back. ``anchors [A,7]`` f32 in
+    head order, ``boxes [N,7]`` f32, ``labels [N]`` i64, ``frame_offsets [B+1]`` i32 on the device, ``frame_offsets_host`` the
+    same offsets as an int32 numpy array (checked by the entry point before the launch). -> dict of ``labels [B,A]`` i64,
+    ``label_weights [B,A]``, ``bbox_targets [B,A,7]``, ``pos [B,A]`` u8, ``dir_targets [B,A]`` i64, ``dir_weights [B,A]``,
+    ``pos_count [B]`` i32."""
+    _need_cuda(anchors, boxes, labels, frame_offsets)
+    if anchors.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != torch.int64 or \
+            frame_offsets.dtype != torch.int32:
+        raise TypeError('anchor_targets: anchors and boxes f32, labels i64, frame_offsets i32')
+    if anchors.dim() != 2 or anchors.shape[1] != 7 or boxes.numel() != labels.numel() * 7:
+        raise ValueError('anchor_targets: anchors [A, 7], boxes [N, 7] for labels [N]')
+    host = np.ascontiguousarray(frame_offsets_host, dtype=np.int32)
+    if host.shape != (frame_offsets.numel(),):
+        raise ValueError('anchor_targets: frame_offsets_host must hold the same B + 1 offsets as frame_offsets')
+    dev, A, N, B = anchors.device, anchors.shape[0], labels.numel(), host.shape[0] - 1
+    anchors, boxes, labels, frame_offsets = anchors.contiguous(), boxes.contiguous(), labels.contiguous(), frame_offsets.contiguous()
+    out = dict(labels=torch.empty((B, A), dtype=torch.int64, device=dev), label_weights=torch.empty((B, A), dtype=torch.float32, device=dev),
+               bbox_targets=torch.empty((B, A, 7), dtype=torch.float32, device=dev), pos=torch.empty((B, A), dtype=torch.uint8, device=dev),
+               dir_targets=torch.empty((B, A), dtype=torch.int64, device=dev), dir_weights=torch.empty((B, A), dtype=torch.float32, device=dev),
+               pos_count=torch.empty(B, dtype=torch.int32, device=dev))
+    L = _lib.lib()
+    ws = _workspace('anchor_targets', max(L.gga_anchor_targets_workspace_bytes(N, prm.n_groups), 256), dev)
+    check(L.gga_anchor_targets(_p(anchors), A, C.byref(prm), _p(boxes), _p(labels), N, _p(frame_offsets), C.c_void_p(host.ctypes.data),
+                               B, _p(out['labels']), _p(out['label_weights']), _p(out['bbox_targets']), _p(out['pos']),
+                               _p(out['dir_targets']), _p(out['dir_weights']), _p(out['pos_count']), _p(ws), ws.numel(), _stream()),
+          'gga_anchor_targets')
+    return out
+
+
+def _anchor_map(x, channels):
+    """A prediction map [B, channels, H, W] as the anchor kernels read it: dense NCHW or channels-last memory (anything else is
+    copied), and its (batch, channel, pixel) strides in elements."""
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != channels:
+        raise ValueError(f'anchor head: a float32 map [B, {channels}, H, W] expected, got {x.dtype} {tuple(x.shape)}')
+    if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
+        x = x.contiguous()
+    if x.is_contiguous():
+        return x, (channels * x.shape[2] * x.shape[3], x.shape[2] * x.shape[3], 1)
+    return x, (channels * x.shape[2] * x.shape[3], 1, channels)
+
+
+def anchor_loss_params(shape, n_anchors, num_classes, strides, gamma, alpha, beta, code_weight, loss_weights, diff_rad_by_sin):
+    B, H, W = shape
+    prm = _lib.AnchorLossParams()
+    prm.B, prm.HW, prm.n_anchors, prm.num_classes, prm.diff_rad_by_sin = int(B), int(H) * int(W), int(n_anchors), int(num_classes), int(bool(diff_rad_by_sin))
+    for field, s in zip(('cls_stride', 'reg_stride', 'dir_stride'), strides):
+        getattr(prm, field)[:] = [int(v) for v in s] if s is not None else [0, 0, 0]
+    prm.gamma, prm.alpha, prm.beta = float(gamma), float(alpha), float(beta)
+    code_weight = [1.0] * 7 if not code_weight else [float(v) for v in code_weight]
+    if len(code_weight) != 7:
+        raise ValueError(f'anchor loss: {len(code_weight)} code weights; the box code has 7 entries')
+    prm.code_weight[:] = code_weight
+    prm.loss_weight[:] = [float(v) for v in loss_weights]
+    return prm
+
+
+class _AnchorLoss(torch.autograd.Function):
+    """The sigmoid focal, smooth-L1 and direction losses of a whole batch: ``gga_anchor_loss_fwd`` / ``_bwd``, one entry point
+    each way. ``cfg`` = (n_anchors, num_classes, gamma, alpha, beta, code_weight, loss_weights, diff_rad_by_sin)."""
+
+    @staticmethod
+    def forward(ctx, cfg, targets, cls_score, bbox_pred, dir_cls_pred):
+        n_anchors, num_classes = cfg[0], cfg[1]
+        _need_cuda(cls_score, bbox_pred, dir_cls_pred)
+        cls_score, s_cls = _anchor_map(cls_score, n_anchors * num_classes)
+        bbox_pred, s_reg = _anchor_map(bbox_pred, n_anchors * 7)
+        s_dir = None
+        if dir_cls_pred is not None:
+            dir_cls_pred, s_dir = _anchor_map(dir_cls_pred, n_anchors * 2)
+        B, _, H, W = cls_score.shape
+        if bbox_pred.shape[0] != B or tuple(bbox_pred.shape[2:]) != (H, W) or \
+                (dir_cls_pred is not None and (dir_cls_pred.shape[0] != B or tuple(dir_cls_pred.shape[2:]) != (H, W))):
+            raise ValueError('anchor loss: the three maps must share batch and map size')
+        if tuple(targets['labels'].shape) != (B, H * W * n_anchors):
+            raise ValueError(f"anchor loss: targets for {tuple(targets['labels'].shape)} anchors, maps for {(B, H * W * n_anchors)}")
+        prm = anchor_loss_params((B, H, W), n_anchors, num_classes, (s_cls, s_reg, s_dir), *cfg[2:])
+        out = torch.empty(4, dtype=torch.float32, device=cls_score.device)
+        ws = _workspace('anchor_loss', _lib.ANCHOR_LOSS_WORKSPACE_BYTES, cls_score.device)
+        t = targets
+        check(_lib.lib().gga_anchor_loss_fwd(C.byref(prm), _p(cls_score), _p(bbox_pred), _p(dir_cls_pred), _p(t['labels']),
+                                             _p(t['label_weights']), _p(t['pos']), _p(t['bbox_targets']), _p(t['dir_targets']),
+                                             _p(t['dir_weights']), _p(t['pos_count']), _p(out), _p(ws), ws.numel(), _stream()),
+              'gga_anchor_loss_fwd')
+        saved = [out, cls_score, bbox_pred] + ([dir_cls_pred] if dir_cls_pred is not None else [])
+        ctx.save_for_backward(*saved)
+        ctx.prm, ctx.targets = prm, targets
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, *gs):
+        out, cls_score, bbox_pred, *rest = ctx.saved_tensors
+        dir_cls_pred = rest[0] if rest else None
+        zero = _zero_scalar(out.device)
+        grad_out = torch.stack([zero if g is None else g.reshape(()).float() for g in gs])
+        g_cls, g_reg = torch.empty_like(cls_score), torch.empty_like(bbox_pred)
+        g_dir = torch.empty_like(dir_cls_pred) if dir_cls_pred is not None else None
+        assert g_cls.stride() == cls_score.stride() and g_reg.stride() == bbox_pred.stride()
+        t = ctx.targets
+        check(_lib.lib().gga_anchor_loss_bwd(C.byref(ctx.prm), _p(cls_score), _p(bbox_pred), _p(dir_cls_pred), _p(t['labels']),
+                                             _p(t['label_weights']), _p(t['pos']), _p(t['bbox_targets']), _p(t['dir_targets']),
+                                             _p(t['dir_weights']), _p(out), _p(grad_out), _p(g_cls), _p(g_reg), _p(g_dir), _stream()),
+              'gga_anchor_loss_bwd')
+        return None, None, g_cls, g_reg, g_dir
+
+
+def anchor_losses(cls_score, bbox_pred, dir_cls_pred, targets, n_anchors, num_classes, gamma, alpha, beta, code_weight,
+                  loss_weights, diff_rad_by_sin):
+    """``loss_cls``, ``loss_bbox``, ``loss_dir`` of ``Anchor3DHead.loss_single`` (anchor3d_head.py:194-278) for the whole batch,
+    from the maps as the head returns them ([B, n_anchors * C | 7 | 2, H, W], NCHW or channels-last memory) and the output of
+    :func:`anchor_targets`. ``avg_factor`` = sum_b max(pos_count[b], 1) is read on the device. -> three device scalars."""
+    cfg = (int(n_anchors), int(num_classes), gamma, alpha, beta, code_weight, loss_weights, diff_rad_by_sin)
+    return _AnchorLoss.apply(cfg, targets, cls_score, bbox_pred, dir_cls_pred)
+
+
+@torch.no_grad()
+def anchor_decode(inds, anchors, scores, bbox_pred, dir_cls_pred, n_anchors):
+    """``gga_anchor_decode``: the kept anchors ``inds [B,K]`` i64 of every frame -> (boxes [B*K,7] decoded by
+    DeltaXYZWLHRBBoxCoder, scores [B*K,C] gathered from ``scores [B,A,C]``, direction bit [B*K] i64) in one launch."""
+    _need_cuda(inds, anchors, scores, bbox_pred, dir_cls_pred)
+    B, K = inds.shape
+    A, nc = scores.shape[1], scores.shape[2]
+    if inds.dtype != torch.int64 or scores.dtype != torch.float32 or scores.shape[0] != B or tuple(anchors.shape) != (A, 7):
+        raise ValueError('anchor_decode: inds [B,K] i64, scores [B,A,C] f32, anchors [A,7]')
+    bbox_pred, s_reg = _anchor_map(bbox_pred, n_anchors * 7)
+    s_dir = None
+    if dir_cls_pred is not None:
+        dir_cls_pred, s_dir = _anchor_map(dir_cls_pred, n_anchors * 2)
+    if bbox_pred.shape[0] != B or bbox_pred.shape[2] * bbox_pred.shape[3] * n_anchors != A:
+        raise ValueError(f'anchor_decode: bbox_pred {tuple(bbox_pred.shape)} does not hold {A} anchors for {B} frames')
+    dev = inds.device
+    inds, anchors, scores = inds.contiguous(), anchors.float().contiguous(), scores.contiguous()
+    boxes = torch.empty((B * K, 7), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((B * K, nc), dtype=torch.float32, device=dev)
+    bits = torch.empty(B * K, dtype=torch.int64, device=dev)
+    arr = lambda s: None if s is None else (C.c_int64 * 3)(*[int(v) for v in s])
+    check(_lib.lib().gga_anchor_decode(_p(inds), B, K, _p(anchors), A, int(n_anchors), nc, _p(scores), _p(bbox_pred), arr(s_reg),
+                                       _p(dir_cls_pred), arr(s_dir), _p(boxes), _p(out_scores), _p(bits), _stream()),
+          'gga_anchor_decode')
+    return boxes, out_scores, bits
+
+
 # ----------------------------------------------------------------------------- fused BN (+res) (+ReLU)
 class _BNActBlocks(torch.autograd.Function):
     """``cat([act_i(bn_i(x_i) + residual_i)], dim=1)`` over ``n >= 1`` column blocks (gga_bn_relu_fwd / gga_bn_relu_bwd, whose

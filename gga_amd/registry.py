@@ -103,6 +103,11 @@ MODELS = Registry('models')
 BACKBONES = NECKS = HEADS = LOSSES = DETECTORS = MODELS
 VOXEL_ENCODERS = MIDDLE_ENCODERS = FUSION_LAYERS = MODELS
 BBOX_CODERS = Registry('bbox_coder')
+# mmdet.core: anchor generators (PRIOR_GENERATORS, ANCHOR_GENERATORS its older name), assigners, samplers, IoU calculators
+PRIOR_GENERATORS = ANCHOR_GENERATORS = Registry('Generator for anchors and points')
+BBOX_ASSIGNERS = Registry('bbox_assigner')
+BBOX_SAMPLERS = Registry('bbox_sampler')
+IOU_CALCULATORS = Registry('IoU calculator')
 CONV_LAYERS = Registry('conv layer')
 PIPELINES = Registry('pipeline')             # mmdet.datasets.builder.PIPELINES (mmdet3d/datasets/builder.py)
 OBJECTSAMPLERS = Registry('Object sampler')  # mmdet3d/datasets/builder.py:13
@@ -135,6 +140,22 @@ def build_middle_encoder(cfg):
 
 def build_bbox_coder(cfg, **default_args):
     return BBOX_CODERS.build(cfg, default_args=default_args or None)
+
+
+def build_prior_generator(cfg, default_args=None):
+    return PRIOR_GENERATORS.build(cfg, default_args=default_args)
+
+
+def build_assigner(cfg, **default_args):
+    return BBOX_ASSIGNERS.build(cfg, default_args=default_args or None)
+
+
+def build_sampler(cfg, **default_args):
+    return BBOX_SAMPLERS.build(cfg, default_args=default_args or None)
+
+
+def build_iou_calculator(cfg, default_args=None):
+    return IOU_CALCULATORS.build(cfg, default_args=default_args)
 
 
 def build_detector(cfg, train_cfg=None, test_cfg=None):

@@ -938,6 +938,91 @@ int gga_center_reg_loss_bwd(const gga_center_loss_table* tasks, int B, int K, co
                             void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Anchor3DHead (SECOND / PointPillars): the targets of a batch without a     */
+/* read-back, the three losses of a batch, the decode of the kept anchors.    */
+/* Replaces the per-frame, per-class assignment loop of                       */
+/* mmdet3d/models/dense_heads/train_mixins.py:63-80,126-183, the gathers and   */
+/* eager losses of anchor3d_head.py:194-278 and the per-frame decode of        */
+/* :427-516.                                                                  */
+/* ------------------------------------------------------------------------- */
+#define GGA_ANCHOR_MAX_GROUPS 16
+typedef struct {
+    int32_t n_groups;             /* assigners: 1, or one per anchor size (1 .. GGA_ANCHOR_MAX_GROUPS) */
+    int32_t n_rot;                /* rotations per size; the group of anchor a is (a / n_rot) % n_groups */
+    int32_t num_classes;          /* background label; a ground truth with a label outside [0, num_classes) takes no part */
+    int32_t assign_per_class;     /* != 0: group g sees only the ground truths with label g */
+    float pos_iou_thr[GGA_ANCHOR_MAX_GROUPS];
+    float neg_iou_thr[GGA_ANCHOR_MAX_GROUPS];
+    float min_pos_iou[GGA_ANCHOR_MAX_GROUPS];
+    float pos_weight;             /* train_cfg.pos_weight: > 0 is the label weight of a positive, otherwise that is 1 */
+    float dir_offset, dir_limit_offset;
+} gga_anchor_params;
+
+/* anchors [A,7] f32 in head order (h, w, size, rot); boxes [N,7] f32 / labels [N] i64 of the whole batch, frame f being rows
+ * frame_offsets[f] .. frame_offsets[f+1] (frame_offsets [B+1] i32 on the device; frame_offsets_host is the same array in host
+ * memory, checked here before anything is launched: non-negative, monotone, ending at or before N).
+ * IoU = mmdet's bbox_overlaps of the nearest-BEV boxes with eps 1e-6 on the union, in f32 with one rounded operation per tensor
+ * operation of the reference. Per (frame, group), over the ground truths the group sees, MaxIoUAssigner with
+ * match_low_quality and gt_max_assign_all: an anchor starts ignored (-1); 0 <= max IoU < neg_iou_thr makes it negative;
+ * max IoU >= pos_iou_thr assigns the argmax (the lowest index among equal values); then for every ground truth i in ascending
+ * order whose best IoU over the group's anchors is >= min_pos_iou, every anchor that reaches that best IoU goes to i. A group
+ * that sees no ground truth has only negatives. Outputs, every element written:
+ *   labels [B,A] i64 (num_classes for negatives and ignored anchors), label_weights [B,A] f32 (positive: pos_weight if > 0
+ *   else 1; negative 1; ignored 0), bbox_targets [B,A,7] f32 (DeltaXYZWLHRBBoxCoder.encode(anchor, gt) for positives, else 0),
+ *   pos_flag [B,A] u8, dir_targets [B,A] i64 (get_direction_target, two bins), dir_weights [B,A] f32, pos_count [B] i32.
+ * workspace: gga_anchor_targets_workspace_bytes(N, n_groups) bytes (0 for sizes it refuses). Launches: two memsets and two
+ * kernels, ordered by the stream; integer atomics only, so the same inputs give the same bits. */
+size_t gga_anchor_targets_workspace_bytes(int64_t N, int n_groups);
+int gga_anchor_targets(const float* anchors, int A, const gga_anchor_params* prm, const float* boxes, const int64_t* labels, int N,
+                       const int32_t* frame_offsets, const int32_t* frame_offsets_host, int B, int64_t* out_labels,
+                       float* label_weights, float* bbox_targets, uint8_t* pos_flag, int64_t* dir_targets, float* dir_weights,
+                       int32_t* pos_count, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct {
+    int32_t B, HW, n_anchors, num_classes;  /* A = HW * n_anchors anchors per frame, anchor i = pixel * n_anchors + a */
+    int32_t diff_rad_by_sin;
+    int32_t reserved;
+    int64_t cls_stride[3];        /* (batch, channel, pixel) strides in elements of cls_score [B, n_anchors * C, H, W] */
+    int64_t reg_stride[3];        /* of bbox_pred [B, n_anchors * 7, H, W] */
+    int64_t dir_stride[3];        /* of dir_cls_pred [B, n_anchors * 2, H, W] */
+    float gamma, alpha;           /* sigmoid focal loss */
+    float beta;                   /* smooth L1 */
+    float code_weight[7];
+    float loss_weight[3];         /* loss_cls, loss_bbox, loss_dir */
+} gga_anchor_loss_params;
+
+/* Anchor i of frame b reads channel a * C + c of cls_score, a * 7 + k of bbox_pred and a * 2 + d of dir_cls_pred at pixel i /
+ * n_anchors: the reference's permute(0, 2, 3, 1).reshape, through the strides, for NCHW and channels-last memory alike.
+ *   out[0] = loss_weight[0] * sum over anchors and classes of label_weights * sigmoid focal loss        / (avg + eps_f32)
+ *   out[1] = loss_weight[1] * sum over positives and k of code_weight[k] * smooth_l1(pred, target; beta) / (avg + eps_f32)
+ *            (diff_rad_by_sin: column 6 compares sin p * cos t with cos p * sin t)
+ *   out[2] = loss_weight[2] * sum over positives of dir_weights * two-way softmax cross entropy          / (avg + eps_f32)
+ *   out[3] = avg = sum_b max(pos_count[b], 1), read on the device
+ * dir_cls_pred may be null (no direction classifier): out[2] = 0. Reduced in a fixed order without floating-point atomics: the
+ * same inputs give the same bits (forward: a kernel of per-workgroup f64 partial sums, then one workgroup that adds them;
+ * backward: one kernel). workspace: GGA_ANCHOR_LOSS_WORKSPACE_BYTES. The backward reads out[3] and grad_out [3] f32
+ * (d / d out[0..2]) from the device and writes every element of the three gradient tensors, which have the strides of their
+ * inputs. */
+#define GGA_ANCHOR_LOSS_WORKSPACE_BYTES 24576
+int gga_anchor_loss_fwd(const gga_anchor_loss_params* prm, const float* cls_score, const float* bbox_pred, const float* dir_cls_pred,
+                        const int64_t* labels, const float* label_weights, const uint8_t* pos_flag, const float* bbox_targets,
+                        const int64_t* dir_targets, const float* dir_weights, const int32_t* pos_count, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int gga_anchor_loss_bwd(const gga_anchor_loss_params* prm, const float* cls_score, const float* bbox_pred, const float* dir_cls_pred,
+                        const int64_t* labels, const float* label_weights, const uint8_t* pos_flag, const float* bbox_targets,
+                        const int64_t* dir_targets, const float* dir_weights, const float* fwd_out, const float* grad_out,
+                        float* grad_cls, float* grad_bbox, float* grad_dir, void* stream);
+
+/* The kept anchors of a batch: inds [B,K] i64 (anchor index inside the frame; an index outside [0, A) gives a row of zeros),
+ * scores [B,A,C] f32 contiguous (the sigmoid scores the top-k was taken on). Row b * K + s of the outputs: out_boxes [.,7] =
+ * DeltaXYZWLHRBBoxCoder.decode(anchor, bbox_pred at the anchor) in the coder's order of f32 operations, out_scores [.,C] the
+ * gathered scores, out_dir i64 = 1 where the second direction logit is the larger (0 without dir_cls_pred). bbox_stride /
+ * dir_stride: host arrays of the (batch, channel, pixel) strides in elements. */
+int gga_anchor_decode(const int64_t* inds, int B, int K, const float* anchors, int A, int n_anchors, int num_classes,
+                      const float* scores, const float* bbox_pred, const int64_t* bbox_stride, const float* dir_cls_pred,
+                      const int64_t* dir_stride, float* out_boxes, float* out_scores, int64_t* out_dir, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* SURVEY.md §8(f) rank 1 — inference / pseudo-label post-processing.        */
 /* ------------------------------------------------------------------------- */
 /* Rotated BEV IoU. Replaces mmcv.ops.box_iou_rotated as called by

@@ -81,8 +81,9 @@ def main():
     logger(f'Distributed training: {distributed} ({world} rank(s)); seed {seed}; work_dir {cfg.work_dir}')
 
     mcfg = cfg.model
-    if mcfg.get('pts_middle_encoder', {}).get('type') in ('PointPillarsScatter', 'SparseEncoder'):
-        mcfg['pts_middle_encoder']['channels_last'] = True        # the layout the matrix kernels take (same values)
+    for key in ('pts_middle_encoder', 'middle_encoder'):          # (the second: VoxelNet's key)
+        if (mcfg.get(key) or {}).get('type') in ('PointPillarsScatter', 'SparseEncoder'):
+            mcfg[key]['channels_last'] = True                     # the layout the matrix kernels take (same values)
     model = build_model(mcfg, train_cfg=cfg.get('train_cfg'), test_cfg=cfg.get('test_cfg'))
     if hasattr(model, 'init_weights'):
         model.init_weights()
