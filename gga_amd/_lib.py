@@ -110,6 +110,8 @@ class CenterLossWeights(C.Structure):
     _fields_ = [('code_weights', C.c_float * 8), ('loss_weight', C.c_float)]
 
 
+FPS_REGISTER_MAX_N = 20480  # GGA_FPS_REGISTER_MAX_N
+GROUP_MAX_SAMPLES = 256     # GGA_GROUP_MAX_SAMPLES
 ANCHOR_MAX_GROUPS = 16      # GGA_ANCHOR_MAX_GROUPS
 ANCHOR_LOSS_WORKSPACE_BYTES = 24576      # GGA_ANCHOR_LOSS_WORKSPACE_BYTES
 
@@ -281,6 +283,15 @@ SIGNATURES = {
     'gga_dcn_im2col': (i32, [vp, vp, vp] + [i32] * 12 + [vp, vp]),
     'gga_dcn_im2col_amax': (i32, [vp, vp, vp] + [i32] * 12 + [vp, vp, vp]),
     'gga_dcn_col2im': (i32, [vp, vp, vp, vp] + [i32] * 12 + [vp, vp, vp, vp]),
+    'gga_furthest_point_sample': (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+    'gga_ball_query': (i32, [vp, vp, i32, i32, i32, f32, f32, i32, vp, vp]),
+    'gga_group_points_fwd': (i32, [vp, vp, i32, i32, i32, i64, vp, vp]),
+    'gga_group_points_bwd': (i32, [vp, vp, i32, i32, i32, i64, vp, vp]),
+    'gga_three_nn': (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    'gga_three_interpolate_fwd': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    'gga_three_interpolate_bwd': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    'gga_query_and_group': (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp, vp, vp]),
+    'gga_query_and_group_bwd': (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp]),
 }
 
 

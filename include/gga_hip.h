@@ -1419,6 +1419,57 @@ int gga_fcos3d_targets(const float* points, int n_points, int n_levels, const in
                        int64_t* labels_3d, float* bbox_targets_3d, float* centerness_targets, int64_t* attr_targets,
                        void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Point operators of the PointNet++ family (mmcv.ops furthest_point_sample,  */
+/* ball_query, grouping_operation, gather_points, three_nn, three_interpolate */
+/* and QueryAndGroup, as mmdet3d/ops/pointnet_modules/point_sa_module.py and  */
+/* point_fp_module.py call them). mmcv's sources are not part of the          */
+/* reference tree: the definitions below ARE the contract (DESIGN.md "Point   */
+/* operators"). All tensors f32 / i32, contiguous. Every squared distance is  */
+/* d2 = (dx*dx + dy*dy) + dz*dz in float32, one rounding per operation, no    */
+/* fused multiply-add.                                                        */
+/* ------------------------------------------------------------------------- */
+#define GGA_FPS_REGISTER_MAX_N 20480    /* largest N of the register path of gga_furthest_point_sample */
+#define GGA_GROUP_MAX_SAMPLES 256       /* largest sample_num of gga_query_and_group */
+/* Furthest point sampling. xyz [B,N,3] -> out [B,num_points] i32; 1 <= num_points <= N. The first sample is index 0; every
+ * point's running minimum starts at 1e10; each round takes min(minimum, d2 to the last sample) and picks the largest minimum,
+ * the LOWEST index among equal maxima. N <= GGA_FPS_REGISTER_MAX_N keeps coordinates and minima in registers; a larger N, or
+ * general != 0, takes the general path, which needs temp [B,N] f32 (any content). Both paths give the same indices. */
+int gga_furthest_point_sample(const float* xyz, int B, int N, int num_points, int general, float* temp, int32_t* out,
+                              void* stream);
+/* Ball query. xyz [B,N,3], center_xyz [B,M,3] -> idx [B,M,sample_num] i32. Candidates in ascending index; a hit has
+ * d2 < max_radius^2 and (d2 == 0 or d2 >= min_radius^2), the squares taken in float32. Slot j holds the j-th hit, every slot no
+ * hit reached holds the first hit, and a centre without any hit holds index 0 everywhere (mmcv's behaviour: point 0 is then
+ * grouped although it lies outside). */
+int gga_ball_query(const float* xyz, const float* center_xyz, int B, int N, int M, float min_radius, float max_radius,
+                   int sample_num, int32_t* idx, void* stream);
+/* out[b,c,j] = features[b,c,idx[b,j]]: features [B,C,N], idx [B,J] -> out [B,C,J]. gather_points is J = M,
+ * grouping_operation J = M * sample_num. The backward adds grad_out into grad_features (zeroed by the caller) with float
+ * atomics. An index outside [0,N) reads as 0 and receives nothing. */
+int gga_group_points_fwd(const float* features, const int32_t* idx, int B, int C, int N, int64_t J, float* out, void* stream);
+int gga_group_points_bwd(const float* grad_out, const int32_t* idx, int B, int C, int N, int64_t J, float* grad_features,
+                         void* stream);
+/* The three nearest source points of every target point: target [B,n,3], source [B,m,3], m >= 3 -> dist [B,n,3] =
+ * sqrtf(d2) ascending, idx [B,n,3]. Found with strict '<' in ascending index: the earlier index wins on ties. */
+int gga_three_nn(const float* target, const float* source, int B, int n, int m, float* dist, int32_t* idx, void* stream);
+/* out[b,c,i] = (w0*f[i0] + w1*f[i1]) + w2*f[i2]: features [B,C,m], idx / weight [B,n,3] -> out [B,C,n]. The backward adds
+ * grad_out * w into grad_features (zeroed by the caller) with float atomics. */
+int gga_three_interpolate_fwd(const float* features, const int32_t* idx, const float* weight, int B, int C, int m, int n,
+                              float* out, void* stream);
+int gga_three_interpolate_bwd(const float* grad_out, const int32_t* idx, const float* weight, int B, int C, int m, int n,
+                              float* grad_features, void* stream);
+/* QueryAndGroup in one launch: the ball query above (query != 0; idx is written) or a given idx (query == 0), then
+ * out [B, (use_xyz ? 3 : 0) + C, M, sample_num] = cat((xyz[idx] - centre) [/ max_radius when normalize_xyz: a true float32
+ * division], features[:, idx]). features [B,C,N] may be NULL with C = 0. sample_num <= GGA_GROUP_MAX_SAMPLES. */
+int gga_query_and_group(const float* xyz, const float* center_xyz, const float* features, int B, int N, int M, int C,
+                        float min_radius, float max_radius, int sample_num, int use_xyz, int normalize_xyz, int query,
+                        int32_t* idx, float* out, void* stream);
+/* Its backward: grad_out in the layout of out -> grad_xyz [B,N,3] and grad_features [B,C,N] (both zeroed by the caller,
+ * float atomics), grad_center [B,M,3] (written). Any of the three may be NULL. */
+int gga_query_and_group_bwd(const float* grad_out, const int32_t* idx, int B, int N, int M, int C, float max_radius,
+                            int sample_num, int use_xyz, int normalize_xyz, float* grad_xyz, float* grad_center,
+                            float* grad_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
