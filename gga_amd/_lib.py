@@ -292,6 +292,8 @@ SIGNATURES = {
     'gga_three_interpolate_bwd': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     'gga_query_and_group': (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp, vp, vp]),
     'gga_query_and_group_bwd': (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp]),
+    'gga_group_max_fwd': (i32, [vp, i32, i32, i32, i32, i64, i64, i64, i64, vp, vp, vp]),
+    'gga_group_max_bwd': (i32, [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, vp, vp]),
 }
 
 

@@ -1,6 +1,7 @@
 """``SECOND`` backbone and ``SECONDFPN`` neck (reference mmdet3d/models/backbones/
 second.py:24-91, necks/second_fpn.py:26-91): every convolution on the repo's own matrix kernels
-(dense_conv.py: 3x3 stride 1; strided_conv.py: stride-2 3x3 and the transposed convolutions; pillar_conv.py: the first one)."""
+(dense_conv.py: 3x3 stride 1; strided_conv.py: stride-2 3x3 and the transposed convolutions; pillar_conv.py: the first one).
+``PointNet2SASSG`` (backbones/pointnet2_sa_ssg.py, base_pointnet.py) on the modules of pointnet_modules.py."""
 import numpy as np
 import torch
 from torch import nn
@@ -45,6 +46,66 @@ class SECOND(nn.Module):
                 x = run_conv_bn_relu(blk, x)
             outs.append(x)
         return tuple(outs)
+
+
+@BACKBONES.register_module()
+class PointNet2SASSG(nn.Module):
+    """PointNet++ with single-scale grouping (reference mmdet3d/models/backbones/pointnet2_sa_ssg.py, base_pointnet.py):
+    ``len(sa_channels)`` set abstraction levels, then ``len(fp_channels)`` feature propagation levels back up.
+    forward(points [B, N, 3 + C]) -> dict of lists: ``sa_xyz`` / ``sa_features`` / ``sa_indices`` hold the input (features None
+    without extra channels) and every level below it, ``fp_xyz`` / ``fp_features`` / ``fp_indices`` the deepest level and every
+    propagated one. The index lists are int64 indices into the input cloud."""
+
+    def __init__(self, in_channels, num_points=(2048, 1024, 512, 256), radius=(0.2, 0.4, 0.8, 1.2), num_samples=(64, 32, 16, 16),
+                 sa_channels=((64, 64, 128), (128, 128, 256), (128, 128, 256), (128, 128, 256)),
+                 fp_channels=((256, 256), (256, 256)), norm_cfg=dict(type='BN2d'),
+                 sa_cfg=dict(type='PointSAModule', pool_mod='max', use_xyz=True, normalize_xyz=True), init_cfg=None,
+                 pretrained=None):
+        super().__init__()
+        from .pointnet_modules import PointFPModule, build_sa_module
+        assert not (init_cfg and pretrained), 'init_cfg and pretrained cannot be setting at the same time'
+        self.fp16_enabled = False
+        self.num_sa, self.num_fp = len(sa_channels), len(fp_channels)
+        assert len(num_points) == len(radius) == len(num_samples) == len(sa_channels)
+        assert len(sa_channels) >= len(fp_channels)
+        widths = [in_channels - 3]                    # feature channels of the input and of every level, without xyz
+        self.SA_modules = nn.ModuleList()
+        for i in range(self.num_sa):
+            self.SA_modules.append(build_sa_module(num_point=num_points[i], radius=radius[i], num_sample=num_samples[i],
+                                                   mlp_channels=[widths[-1], *sa_channels[i]], norm_cfg=norm_cfg, cfg=sa_cfg))
+            widths.append(sa_channels[i][-1])
+        # propagation i takes level num_sa - i (or the previous propagation's output) up to level num_sa - i - 1
+        self.FP_modules = nn.ModuleList()
+        source = widths[-1]
+        for i in range(self.num_fp):
+            self.FP_modules.append(PointFPModule(mlp_channels=[source + widths[self.num_sa - i - 1], *fp_channels[i]]))
+            source = fp_channels[i][-1]
+
+    @staticmethod
+    def _split_point_feats(points):
+        """points [B, N, 3 + C] -> (xyz [B,N,3], features [B,C,N] or None), both contiguous."""
+        xyz = points[..., 0:3].contiguous()
+        features = points[..., 3:].transpose(1, 2).contiguous() if points.size(-1) > 3 else None
+        return xyz, features
+
+    def forward(self, points):
+        xyz, features = self._split_point_feats(points)
+        batch, n = xyz.shape[:2]
+        sa_xyz, sa_features = [xyz], [features]
+        sa_indices = [torch.arange(n, device=xyz.device).unsqueeze(0).repeat(batch, 1)]
+        for sa in self.SA_modules:
+            cur_xyz, cur_features, cur_indices = sa(sa_xyz[-1], sa_features[-1])
+            sa_xyz.append(cur_xyz)
+            sa_features.append(cur_features)
+            sa_indices.append(torch.gather(sa_indices[-1], 1, cur_indices.long()))
+        fp_xyz, fp_features, fp_indices = [sa_xyz[-1]], [sa_features[-1]], [sa_indices[-1]]
+        for i, fp in enumerate(self.FP_modules):
+            lower, upper = self.num_sa - i, self.num_sa - i - 1
+            fp_features.append(fp(sa_xyz[upper], sa_xyz[lower], sa_features[upper], fp_features[-1]))
+            fp_xyz.append(sa_xyz[upper])
+            fp_indices.append(sa_indices[upper])
+        return dict(fp_xyz=fp_xyz, fp_features=fp_features, fp_indices=fp_indices, sa_xyz=sa_xyz, sa_features=sa_features,
+                    sa_indices=sa_indices)
 
 
 @NECKS.register_module()

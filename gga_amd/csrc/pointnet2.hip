@@ -479,3 +479,265 @@ extern "C" int gga_query_and_group_bwd(const float* grad_out, const int32_t* idx
     }
     return GGA_OK;
 }
+
+// ------------------------------------------------------------------------------ group max pool
+// y[b,c,m] = max over k of x[b,c,m,k], arg = its position, by the scan of include/gga_hip.h: from (x[0], 0), x[k] replaces the
+// best when x[k] > best, or when x[k] is NaN and the best is not. gmax_better orders (value, position) pairs so that any
+// reduction tree gives that scan's answer: a NaN beats every number, of two NaNs or two equal values (+0 == -0) the lower
+// position wins. Positions of a group are distinct, so the order is total; the filler (-inf, K) of a lane without an element
+// loses to every element. x and gx are addressed through the caller's element strides, in 64-bit arithmetic.
+// Two lane layouts, both correct for any strides, each coalesced for one memory format:
+//   _k_: L = min(64, the power of two >= K) lanes scan one group along k (contiguous k: NCHW). A wave takes 64 consecutive
+//        groups, 64 / L of them per step, and hands every result to the lane of its group, so y and arg leave as one store.
+//        The forward has a form with four samples per lane (one 16 B load, L from K / 4) for 16 B aligned groups: the
+//        one-sample form is bound by its compare and shuffle instructions, not by memory (1.4 TB/s at K = 64).
+//   _c_: lanes along 64 channels (contiguous channels: channels-last), a workgroup pools a 64 channel x 16 centre tile and
+//        turns it through LDS (rows padded by a word: the column writes and the row reads are conflict-free), so the
+//        [B, C, M] store runs along m.
+#define GMAX_TILE 64         // channels of a tile of the _c_ kernels
+#define GMAX_TILE_M 16       // centres of a tile: four per wave. Small on purpose: the pool shapes of a VoteNet step give 512 to
+                             // 8192 workgroups, several rounds over the chip, where 64-centre tiles left 128 to 2048
+
+__device__ __forceinline__ bool gmax_better(float v, int k, float bv, int bk) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || k < bk);
+    return v > bv || (v == bv && k < bk);
+}
+
+// element offset of group g = (b * C + c) * M + m, or -1 past the end
+__device__ __forceinline__ int64_t gmax_base(int64_t g, int64_t groups, int C, int M, int64_t sb, int64_t sc, int64_t sm) {
+    if (g >= groups) return -1;
+    const int64_t bc = g / M, m = g - bc * M, b = bc / C, c = bc - b * C;
+    return b * sb + c * sc + m * sm;
+}
+
+template <int L, int V>
+__global__ __launch_bounds__(256) void group_max_fwd_k_kernel(const float* __restrict__ x, int C, int M, int K, int64_t sb,
+                                                              int64_t sc, int64_t sm, int64_t sk, int64_t groups,
+                                                              float* __restrict__ y, uint8_t* __restrict__ arg) {
+    constexpr int G = GGA_WAVE / L, U = L >= 4 ? 4 : L;
+    const int lane = threadIdx.x & 63, sub = lane / L, l = lane % L;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), step = (int64_t)gridDim.x * 4 * GGA_WAVE;
+    for (int64_t g0 = wave * GGA_WAVE; g0 < groups; g0 += step) {
+        const int64_t g = g0 + lane;
+        const long long base = gmax_base(g, groups, C, M, sb, sc, sm);
+        float rv = 0.f;
+        int rk = 0;
+#pragma unroll U
+        for (int j = 0; j < L; ++j) {
+            const long long gb = __shfl(base, j * G + sub, 64);      // the group this sub-wave scans in step j
+            float bv = -INFINITY;
+            int bk = K;
+            if (gb >= 0) {
+                if (V == 4) {                                        // sk == 1, K % 4 == 0, every group 16 B aligned
+                    for (int k = l * 4; k < K; k += L * 4) {
+                        const float4 q = *reinterpret_cast<const float4*>(x + gb + k);
+                        const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (gmax_better(v[i], k + i, bv, bk)) { bv = v[i]; bk = k + i; }
+                    }
+                } else {
+                    for (int k = l; k < K; k += L) {
+                        const float v = x[gb + (int64_t)k * sk];
+                        if (gmax_better(v, k, bv, bk)) { bv = v; bk = k; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = L / 2; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int ok = __shfl_xor(bk, o, 64);
+                if (gmax_better(ov, ok, bv, bk)) { bv = ov; bk = ok; }
+            }
+            // lane t owns group g0 + t: scanned in step t / G by sub-wave t % G
+            const float tv = __shfl(bv, (lane % G) * L, 64);
+            const int tk = __shfl(bk, (lane % G) * L, 64);
+            if (lane / G == j) { rv = tv; rk = tk; }
+        }
+        if (g < groups) {
+            y[g] = rv;
+            arg[g] = (uint8_t)rk;
+        }
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void group_max_bwd_k_kernel(const float* __restrict__ gy, const uint8_t* __restrict__ arg, int C,
+                                                              int M, int K, int64_t sb, int64_t sc, int64_t sm, int64_t sk,
+                                                              int64_t groups, float* __restrict__ gx) {
+    constexpr int G = GGA_WAVE / L, U = L >= 4 ? 4 : L;
+    const int lane = threadIdx.x & 63, sub = lane / L, l = lane % L;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), step = (int64_t)gridDim.x * 4 * GGA_WAVE;
+    for (int64_t g0 = wave * GGA_WAVE; g0 < groups; g0 += step) {
+        const int64_t g = g0 + lane;
+        const long long base = gmax_base(g, groups, C, M, sb, sc, sm);
+        const float mine = g < groups ? gy[g] : 0.f;
+        const int mine_k = g < groups ? (int)arg[g] : 0;
+#pragma unroll U
+        for (int j = 0; j < L; ++j) {
+            const int src = j * G + sub;
+            const long long gb = __shfl(base, src, 64);
+            const float v = __shfl(mine, src, 64);
+            const int a = __shfl(mine_k, src, 64);
+            if (gb >= 0)
+                for (int k = l; k < K; k += L) gx[gb + (int64_t)k * sk] = k == a ? v : 0.f;
+        }
+    }
+}
+
+// blockIdx.x = (b * mtiles + mt) * ctiles + ct: the workgroups that share a centre's rows are neighbours
+__global__ __launch_bounds__(256) void group_max_fwd_c_kernel(const float* __restrict__ x, int C, int M, int K, int64_t sb,
+                                                              int64_t sc, int64_t sm, int64_t sk, int mtiles, int ctiles,
+                                                              float* __restrict__ y, uint8_t* __restrict__ arg) {
+    __shared__ float sv[GMAX_TILE][GMAX_TILE_M + 1];
+    __shared__ uint8_t sa[GMAX_TILE][GMAX_TILE_M + 4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t t = blockIdx.x;
+    const int ct = (int)(t % ctiles);
+    t /= ctiles;
+    const int mt = (int)(t % mtiles);
+    const int64_t b = t / mtiles;
+    const int c = ct * GMAX_TILE + lane, m0 = mt * GMAX_TILE_M;
+    for (int i = 0; i < GMAX_TILE_M / 4; ++i) {
+        const int ml = w * (GMAX_TILE_M / 4) + i, m = m0 + ml;
+        if (m >= M) break;                                           // the same for the whole wave
+        float bv = -INFINITY;
+        int bk = K;
+        if (c < C) {
+            const float* p = x + (b * sb + (int64_t)c * sc + (int64_t)m * sm);
+#pragma unroll 8
+            for (int k = 0; k < K; ++k) {
+                const float v = p[(int64_t)k * sk];
+                if (gmax_better(v, k, bv, bk)) { bv = v; bk = k; }
+            }
+        }
+        sv[lane][ml] = bv;
+        sa[lane][ml] = (uint8_t)bk;
+    }
+    __syncthreads();
+    // the turned tile: 16 consecutive threads along m
+    const int ml = threadIdx.x % GMAX_TILE_M, m = m0 + ml;
+    for (int cl = threadIdx.x / GMAX_TILE_M; cl < GMAX_TILE; cl += 256 / GMAX_TILE_M) {
+        const int cc = ct * GMAX_TILE + cl;
+        if (cc < C && m < M) {
+            const int64_t o = (b * C + cc) * M + m;
+            y[o] = sv[cl][ml];
+            arg[o] = sa[cl][ml];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void group_max_bwd_c_kernel(const float* __restrict__ gy, const uint8_t* __restrict__ arg, int C,
+                                                              int M, int K, int64_t sb, int64_t sc, int64_t sm, int64_t sk,
+                                                              int mtiles, int ctiles, float* __restrict__ gx) {
+    __shared__ float sv[GMAX_TILE][GMAX_TILE_M + 1];
+    __shared__ uint8_t sa[GMAX_TILE][GMAX_TILE_M + 4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t t = blockIdx.x;
+    const int ct = (int)(t % ctiles);
+    t /= ctiles;
+    const int mt = (int)(t % mtiles);
+    const int64_t b = t / mtiles;
+    const int m0 = mt * GMAX_TILE_M;
+    for (int cl = threadIdx.x / GMAX_TILE_M; cl < GMAX_TILE; cl += 256 / GMAX_TILE_M) {
+        const int cc = ct * GMAX_TILE + cl, ml = threadIdx.x % GMAX_TILE_M, m = m0 + ml;
+        const bool in = cc < C && m < M;
+        const int64_t o = in ? (b * C + cc) * M + m : 0;
+        sv[cl][ml] = in ? gy[o] : 0.f;
+        sa[cl][ml] = in ? arg[o] : (uint8_t)0;
+    }
+    __syncthreads();
+    const int c = ct * GMAX_TILE + lane;
+    if (c >= C) return;
+    for (int i = 0; i < GMAX_TILE_M / 4; ++i) {
+        const int ml = w * (GMAX_TILE_M / 4) + i, m = m0 + ml;
+        if (m >= M) break;
+        const float v = sv[lane][ml];
+        const int a = sa[lane][ml];
+        float* p = gx + (b * sb + (int64_t)c * sc + (int64_t)m * sm);
+#pragma unroll 8
+        for (int k = 0; k < K; ++k) p[(int64_t)k * sk] = k == a ? v : 0.f;
+    }
+}
+
+struct GmaxPlan {
+    int channels_on_lanes, lanes, mtiles, ctiles;
+    int64_t groups;
+    unsigned blocks;
+};
+
+static int gmax_plan(const char* name, const void* p0, const void* p1, const void* p2, int B, int C, int M, int K, int64_t sb,
+                     int64_t sc, int64_t sm, int64_t sk, GmaxPlan* plan) {
+    GGA_REQUIRE(p0 && p1 && p2, "%s: null pointer argument", name);
+    GGA_REQUIRE(B >= 1 && C >= 1 && M >= 1, "%s: bad sizes (B %d, C %d, M %d)", name, B, C, M);
+    GGA_REQUIRE(K >= 1 && K <= GGA_GROUP_MAX_SAMPLES, "%s: K %d not in 1..%d", name, K, GGA_GROUP_MAX_SAMPLES);
+    GGA_REQUIRE(sb >= 0 && sc >= 0 && sm >= 0 && sk >= 0, "%s: negative stride (%lld, %lld, %lld, %lld)", name, (long long)sb,
+                (long long)sc, (long long)sm, (long long)sk);
+    plan->groups = (int64_t)B * C * M;
+    plan->channels_on_lanes = sc == 1 && C > 1 && !(sk == 1 && K > 1);
+    plan->lanes = 1;
+    while (plan->lanes < K && plan->lanes < GGA_WAVE) plan->lanes *= 2;
+    plan->mtiles = (M + GMAX_TILE_M - 1) / GMAX_TILE_M;
+    plan->ctiles = (C + GMAX_TILE - 1) / GMAX_TILE;
+    if (plan->channels_on_lanes) {
+        const int64_t blocks = (int64_t)B * plan->mtiles * plan->ctiles;
+        GGA_REQUIRE(blocks <= 0x7FFFFFFF, "%s: B * C * M too large for one launch (%lld workgroups)", name, (long long)blocks);
+        plan->blocks = (unsigned)blocks;
+    } else {
+        const int64_t blocks = (plan->groups + 255) / 256;
+        plan->blocks = (unsigned)(blocks < 65536 ? blocks : 65536);
+    }
+    return GGA_OK;
+}
+
+#define GMAX_COMMA ,
+#define GMAX_LAUNCH_K(kernel, lanes, TAIL, ...)                                                                                           \
+    switch (lanes) {                                                                                                          \
+        case 1: hipLaunchKernelGGL((kernel<1 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                        \
+        case 2: hipLaunchKernelGGL((kernel<2 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                        \
+        case 4: hipLaunchKernelGGL((kernel<4 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                        \
+        case 8: hipLaunchKernelGGL((kernel<8 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                        \
+        case 16: hipLaunchKernelGGL((kernel<16 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                      \
+        case 32: hipLaunchKernelGGL((kernel<32 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                      \
+        default: hipLaunchKernelGGL((kernel<64 TAIL>), dim3(plan.blocks), dim3(256), 0, s, __VA_ARGS__); break;                      \
+    }
+
+extern "C" int gga_group_max_fwd(const float* x, int B, int C, int M, int K, int64_t sb, int64_t sc, int64_t sm, int64_t sk,
+                                 float* y, uint8_t* arg, void* stream) {
+    GmaxPlan plan;
+    if (int rc = gmax_plan("gga_group_max_fwd", x, y, arg, B, C, M, K, sb, sc, sm, sk, &plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (plan.channels_on_lanes) {
+        hipLaunchKernelGGL(group_max_fwd_c_kernel, dim3(plan.blocks), dim3(256), 0, s, x, C, M, K, sb, sc, sm, sk, plan.mtiles,
+                           plan.ctiles, y, arg);
+    } else {
+        // four consecutive samples per lane as one 16 B load where every group starts on a 16 B boundary: a quarter of the
+        // lanes per group, and of the cross-lane steps per byte
+        const bool wide = sk == 1 && K % 4 == 0 && sb % 4 == 0 && sc % 4 == 0 && sm % 4 == 0 && ((uintptr_t)x & 15) == 0;
+        if (wide) {
+            int lanes = 1;
+            while (lanes * 4 < K) lanes *= 2;
+            GMAX_LAUNCH_K(group_max_fwd_k_kernel, lanes, GMAX_COMMA 4, x, C, M, K, sb, sc, sm, sk, plan.groups, y, arg)
+        } else {
+            GMAX_LAUNCH_K(group_max_fwd_k_kernel, plan.lanes, GMAX_COMMA 1, x, C, M, K, sb, sc, sm, sk, plan.groups, y, arg)
+        }
+    }
+    GGA_CHECK_LAUNCH("gga_group_max_fwd");
+    return GGA_OK;
+}
+
+extern "C" int gga_group_max_bwd(const float* grad_y, const uint8_t* arg, int B, int C, int M, int K, int64_t sb, int64_t sc,
+                                 int64_t sm, int64_t sk, float* grad_x, void* stream) {
+    GmaxPlan plan;
+    if (int rc = gmax_plan("gga_group_max_bwd", grad_y, arg, grad_x, B, C, M, K, sb, sc, sm, sk, &plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (plan.channels_on_lanes) {
+        hipLaunchKernelGGL(group_max_bwd_c_kernel, dim3(plan.blocks), dim3(256), 0, s, grad_y, arg, C, M, K, sb, sc, sm, sk,
+                           plan.mtiles, plan.ctiles, grad_x);
+    } else {
+        GMAX_LAUNCH_K(group_max_bwd_k_kernel, plan.lanes, , grad_y, arg, C, M, K, sb, sc, sm, sk, plan.groups, grad_x)
+    }
+    GGA_CHECK_LAUNCH("gga_group_max_bwd");
+    return GGA_OK;
+}

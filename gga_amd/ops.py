@@ -10,7 +10,8 @@ gga_amd/csrc/postproc.hip, with the call signatures the reference uses:
 * ``DynamicScatter(voxel_size, point_cloud_range, average_points)`` — ``mmcv.ops.DynamicScatter`` as the dynamic voxel
   encoders use it (voxel_encoders/voxel_encoder.py:64,155-174), on gga_amd/csrc/dynamic_voxel.hip
 * the PointNet++ point operators (``furthest_point_sample``, ``ball_query``, ``grouping_operation``, ``gather_points``,
-  ``three_nn``, ``three_interpolate``, ``QueryAndGroup``, ``GroupAll``, ``PointsSampler``) — re-exported from pointnet2.py
+  ``three_nn``, ``three_interpolate``, ``QueryAndGroup``, ``GroupAll``, ``PointsSampler``) and ``group_max_pool`` —
+  re-exported from pointnet2.py
 """
 import torch
 from torch import nn
@@ -19,7 +20,7 @@ from . import _lib
 from . import functional as F
 from ._lib import check
 from .pointnet2 import (GroupAll, PointsSampler, QueryAndGroup, ball_query, furthest_point_sample, gather_points,  # noqa: F401
-                        grouping_operation, three_interpolate, three_nn)
+                        group_max_pool, grouping_operation, three_interpolate, three_nn)
 
 
 def xywhr2xyxyr(boxes_xywhr):

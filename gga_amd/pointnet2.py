@@ -9,6 +9,8 @@ point_fp_module.py:4, models/model_utils/vote_module.py, models/dense_heads/vote
 * ``three_nn(target [B,n,3], source [B,m,3]) -> (dist [B,n,3], idx int32 [B,n,3])``
 * ``three_interpolate(features [B,C,m], indices [B,n,3], weight [B,n,3]) -> [B,C,n]``
 * ``QueryAndGroup``, ``GroupAll``, ``PointsSampler`` (``D-FPS`` only)
+* ``group_max_pool(x [B,C,M,K]) -> [B,C,M]``: the pool over a group's samples (not an mmcv op: the reference calls
+  ``F.max_pool2d`` there)
 
 mmcv's sources are not part of the reference tree, so the definitions are this project's (include/gga_hip.h "Point
 operators", DESIGN.md "Point operators"): float32 ``d2 = (dx*dx + dy*dy) + dz*dz`` rounded per operation, furthest point
@@ -26,6 +28,7 @@ from ._lib import check
 
 GROUP_FUSED = os.environ.get('GGA_SA_GROUP_FUSED', '1') != '0'      # QueryAndGroup as one launch (0: the separate ops)
 FPS_GENERAL = os.environ.get('GGA_FPS_GENERAL', '0') != '0'         # force the any-N path of furthest point sampling
+SA_POOL = os.environ.get('GGA_SA_POOL', '1') != '0'                 # group_max_pool on the pool kernel (0: F.max_pool2d)
 
 
 def _f32(t):
@@ -208,6 +211,47 @@ def query_and_group(points_xyz, center_xyz, features, min_radius, max_radius, sa
     if features is not None:
         parts.append(grouping_operation(features, idx))
     return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)), idx
+
+
+class _GroupMaxPool(torch.autograd.Function):
+    """gga_group_max_fwd / gga_group_max_bwd: x [B,C,M,K] in contiguous or channels-last memory -> [B,C,M] contiguous; the
+    positions of the maxima are kept as one byte each, and the gradient comes back in x's memory format."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, C, M, K = x.shape
+        y = torch.empty((B, C, M), dtype=torch.float32, device=x.device)
+        arg = torch.empty((B, C, M), dtype=torch.uint8, device=x.device)
+        check(_lib.lib().gga_group_max_fwd(F._p(x), B, C, M, K, *x.stride(), F._p(y), F._p(arg), F._stream()),
+              'gga_group_max_fwd')
+        ctx.save_for_backward(arg)
+        ctx.layout = (tuple(x.shape), tuple(x.stride()))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        arg, = ctx.saved_tensors
+        (B, C, M, K), stride = ctx.layout
+        g = _f32(grad_y)
+        grad_x = torch.empty_strided((B, C, M, K), stride, dtype=torch.float32, device=g.device)
+        check(_lib.lib().gga_group_max_bwd(F._p(g), F._p(arg), B, C, M, K, *stride, F._p(grad_x), F._stream()),
+              'gga_group_max_bwd')
+        return grad_x
+
+
+def _eager_max_pool(x):
+    return torch.nn.functional.max_pool2d(x, kernel_size=[1, x.shape[3]]).squeeze(-1).contiguous()
+
+
+def group_max_pool(x):
+    """The max over the samples of every group, x [B,C,M,K] -> [B,C,M] contiguous: what the reference's set abstraction
+    modules take from ``F.max_pool2d(kernel_size=[1, K])`` (point_sa_module.py:146-168). A float32 CUDA tensor in contiguous
+    or channels-last memory with K <= 256 runs on the pool kernel (first maximum on ties, a NaN wins); anything else, or
+    ``GGA_SA_POOL=0``, is the framework's pool."""
+    own = (SA_POOL and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.numel() > 0
+           and x.shape[3] <= _lib.GROUP_MAX_SAMPLES
+           and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)))
+    return _GroupMaxPool.apply(x) if own else _eager_max_pool(x)
 
 
 class QueryAndGroup(nn.Module):

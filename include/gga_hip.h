@@ -1430,7 +1430,7 @@ int gga_fcos3d_targets(const float* points, int n_points, int n_levels, const in
 /* fused multiply-add.                                                        */
 /* ------------------------------------------------------------------------- */
 #define GGA_FPS_REGISTER_MAX_N 20480    /* largest N of the register path of gga_furthest_point_sample */
-#define GGA_GROUP_MAX_SAMPLES 256       /* largest sample_num of gga_query_and_group */
+#define GGA_GROUP_MAX_SAMPLES 256       /* largest sample_num of gga_query_and_group, largest K of gga_group_max_* */
 /* Furthest point sampling. xyz [B,N,3] -> out [B,num_points] i32; 1 <= num_points <= N. The first sample is index 0; every
  * point's running minimum starts at 1e10; each round takes min(minimum, d2 to the last sample) and picks the largest minimum,
  * the LOWEST index among equal maxima. N <= GGA_FPS_REGISTER_MAX_N keeps coordinates and minima in registers; a larger N, or
@@ -1469,6 +1469,18 @@ int gga_query_and_group(const float* xyz, const float* center_xyz, const float* 
 int gga_query_and_group_bwd(const float* grad_out, const int32_t* idx, int B, int N, int M, int C, float max_radius,
                             int sample_num, int use_xyz, int normalize_xyz, float* grad_xyz, float* grad_center,
                             float* grad_features, void* stream);
+/* Max pool over the samples of a group (the tail of a set abstraction level): x [B,C,M,K] f32, read through the element strides
+ * (sb, sc, sm, sk) of its four dimensions (contiguous NCHW and channels-last memory alike, no copy) -> y [B,C,M] f32 and
+ * arg [B,C,M] u8, both contiguous; 1 <= K <= GGA_GROUP_MAX_SAMPLES, so a position fits a byte. The definition is the scan
+ * k = 0 .. K-1 from best = x[0], arg = 0 that takes x[k] when x[k] > best, or when x[k] is NaN and best is not: the lowest k
+ * among equal maxima (+0 and -0 are equal), NaN at the first NaN's position for a group with a NaN, -inf at 0 for a group of
+ * -inf. Strides must be non-negative. */
+int gga_group_max_fwd(const float* x, int B, int C, int M, int K, int64_t sb, int64_t sc, int64_t sm, int64_t sk, float* y,
+                      uint8_t* arg, void* stream);
+/* Its backward: grad_x [B,C,M,K] through the same four strides, every element written exactly once (grad_y[b,c,m] at
+ * k == arg[b,c,m], zero elsewhere): no memset before it, no atomics, the same bits on every run. */
+int gga_group_max_bwd(const float* grad_y, const uint8_t* arg, int B, int C, int M, int K, int64_t sb, int64_t sc, int64_t sm,
+                      int64_t sk, float* grad_x, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,12 @@ synchronised; ``--warmup`` untimed calls of every variant first, then ``--reps``
 alternating inside one run; the median and the spread (min .. max) in milliseconds. Points: half on the floor and two walls of
 a 5 x 5 x 2.5 m room, half anywhere in it, from a seed. Needs the GPU: there is no fallback.
 
-    python tools_dev/bench_votenet.py [--reps 30] [--warmup 5] [--batch 16] [--json out.json]
+Sections (``--sections``, default all three): ``ops`` = the above; ``pool`` = ``pointnet2.group_max_pool`` against ``F.max_pool2d``
+at the five pool shapes of the config (the four levels and the vote aggregation) in contiguous and channels-last memory, forward
+and forward + backward, with the achieved fraction of the HBM peak; ``modules`` = the first set abstraction level and the whole
+``PointNet2SASSG`` backbone, forward + backward, with ``GGA_SA_POOL`` 1 and 0.
+
+    python tools_dev/bench_votenet.py [--reps 30] [--warmup 5] [--batch 16] [--sections ops,pool,modules] [--json out.json]
 """
 import argparse
 import json
@@ -20,6 +25,7 @@ import sys
 
 import numpy as np
 import torch
+import torch.nn.functional as tF
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -28,6 +34,12 @@ from gga_amd import pointnet2 as P  # noqa: E402
 SA = [(2048, 0.2, 64, 1), (1024, 0.4, 32, 128), (512, 0.8, 16, 256), (256, 1.2, 16, 256)]      # centres, radius, samples, channels in
 FP = [(512, 256, 256), (1024, 512, 256)]                                                           # target n, source m, channels
 VOTE = (256, 0.3, 16, 256)
+POOL = [(128, 2048, 64), (256, 1024, 32), (256, 512, 16), (256, 256, 16), (128, 256, 16)]        # C, M, K: SA1-4, vote aggregation
+HBM_PEAK_TB_S = 8.0
+BACKBONE = dict(type='PointNet2SASSG', in_channels=4, num_points=(2048, 1024, 512, 256), radius=(0.2, 0.4, 0.8, 1.2),
+                num_samples=(64, 32, 16, 16), sa_channels=((64, 64, 128), (128, 128, 256), (128, 128, 256), (128, 128, 256)),
+                fp_channels=((256, 256), (256, 256)), norm_cfg=dict(type='BN2d'),
+                sa_cfg=dict(type='PointSAModule', pool_mod='max', use_xyz=True, normalize_xyz=True))
 
 
 def room(rng, batch, n):
@@ -64,6 +76,7 @@ def main():
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--points', type=int, default=20000)
     ap.add_argument('--json', default=None)
+    ap.add_argument('--sections', default='ops,pool,modules', help='comma-separated: ops, pool, modules')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_votenet.py measures on the GPU only'
     dev = torch.device('cuda:0')
@@ -80,6 +93,19 @@ def main():
         report(name, timed(variants, args.warmup, args.reps))
 
     xyz = torch.from_numpy(room(rng, B, args.points)).to(dev)
+    sections = args.sections.split(',')
+    assert set(sections) <= {'ops', 'pool', 'modules'}, args.sections
+    if 'ops' in sections:
+        bench_ops(args, run, rng, xyz)
+    if 'pool' in sections:
+        bench_pool(args, run, rows)
+    if 'modules' in sections:
+        bench_modules(args, run, xyz)
+    write_json(args, rows)
+
+
+def bench_ops(args, run, rng, xyz):
+    dev, B = xyz.device, args.batch
     feats = torch.randn(B, 1, args.points, device=dev)
     levels = []                                             # (xyz, features) going into each set abstraction level
     for M, radius, K, C in SA:
@@ -138,6 +164,75 @@ def main():
         assert torch.equal(a[1], b[1]) and torch.equal(a[0], b[0]), f'{tag}: fused and composed forward differ'
         run(tag + ' fwd', fused=lambda: fwd(True), composed=lambda: fwd(False))
         run(tag + ' fwd+bwd', fused=lambda: fwd_bwd(True), composed=lambda: fwd_bwd(False))
+
+def bench_pool(args, run, rows):
+    """The group max pool against F.max_pool2d at the five pool shapes of the VoteNet config, in both memory layouts; the rate
+    is the kernel's own traffic (4*B*C*M*K + 5*B*C*M bytes each way) over the median, as a fraction of the 8 TB/s HBM peak
+    (about 6.3 TB/s is what a float4 copy reaches on this part)."""
+    dev = torch.device('cuda:0')
+    eager = lambda t: tF.max_pool2d(t, kernel_size=[1, t.shape[3]]).squeeze(-1).contiguous()      # noqa: E731
+    for C, M, K in POOL:
+        for layout, fmt in (('nchw', torch.contiguous_format), ('channels_last', torch.channels_last)):
+            x = torch.randn(args.batch, C, M, K, device=dev).contiguous(memory_format=fmt).requires_grad_(True)
+            g = torch.randn(args.batch, C, M, device=dev)
+            assert torch.equal(P.group_max_pool(x), eager(x))
+
+            def fwd(fn):
+                with torch.no_grad():
+                    return fn(x)
+
+            def fwd_bwd(fn):
+                x.grad = None
+                fn(x).backward(g)
+            tag = f'group_max_pool [{args.batch},{C},{M},{K}] {layout}'
+            nbytes = 4 * x.numel() + 5 * g.numel()
+            for name, fn, passes in (('fwd', fwd, 1), ('fwd+bwd', fwd_bwd, 2)):
+                first = len(rows)
+                run(f'{tag} {name}', kernel=lambda: fn(P.group_max_pool), max_pool2d=lambda: fn(eager))
+                for r in rows[first:]:
+                    r['tb_per_s'] = round(passes * nbytes / (r['ms'] * 1e-3) / 1e12, 3)
+                    r['of_hbm_peak'] = round(r['tb_per_s'] / HBM_PEAK_TB_S, 3)
+                    print(f'    {r["variant"]:12s} {r["tb_per_s"]:.3f} TB/s of the kernel\'s own traffic = {r["of_hbm_peak"]:.3f} of '
+                          f'{HBM_PEAK_TB_S} TB/s', flush=True)
+            del x, g
+            torch.cuda.empty_cache()
+
+
+def bench_modules(args, run, xyz):
+    """The first set abstraction level and the whole backbone of the VoteNet config, forward + backward, with the pool kernel
+    (GGA_SA_POOL=1) and with F.max_pool2d (GGA_SA_POOL=0)."""
+    from gga_amd.pointnet_modules import PointSAModule
+    from gga_amd.registry import build_backbone
+    dev = xyz.device
+    torch.manual_seed(0)
+    M, radius, K, _ = SA[0]
+    sa = PointSAModule(mlp_channels=[1, 64, 64, 128], num_point=M, radius=radius, num_sample=K, normalize_xyz=True).to(dev).train()
+    feats = torch.randn(xyz.shape[0], 1, xyz.shape[1], device=dev, requires_grad=True)
+    g = torch.randn(xyz.shape[0], 128, M, device=dev)
+    backbone = build_backbone(BACKBONE).to(dev).train()
+    points = torch.cat([xyz, torch.randn(xyz.shape[0], xyz.shape[1], 1, device=dev)], dim=2).requires_grad_(True)
+    gb = torch.randn(xyz.shape[0], 256, SA[1][0], device=dev)
+    was = P.SA_POOL
+
+    def level(own):
+        P.SA_POOL = own
+        feats.grad = None
+        sa.zero_grad(set_to_none=True)
+        sa(xyz, feats)[1].backward(g)
+
+    def whole(own):
+        P.SA_POOL = own
+        points.grad = None
+        backbone.zero_grad(set_to_none=True)
+        backbone(points)['fp_features'][-1].backward(gb)
+    try:
+        run(f'PointSAModule SA1 N={xyz.shape[1]} M={M} K={K} fwd+bwd', pool_kernel=lambda: level(True), max_pool2d=lambda: level(False))
+        run(f'PointNet2SASSG N={xyz.shape[1]} fwd+bwd', pool_kernel=lambda: whole(True), max_pool2d=lambda: whole(False))
+    finally:
+        P.SA_POOL = was
+
+
+def write_json(args, rows):
     if args.json:
         with open(args.json, 'w') as fh:
             for r in rows:
