@@ -24,6 +24,9 @@ class VoxelParams(C.Structure):
                 ('max_points', C.c_int32), ('max_voxels', C.c_int32)]
 
 
+PFN_SAVED_DOUBLES = 239     # PFN_SAVED_ROWS + 1
+
+
 class PfnParams(C.Structure):
     _fields_ = [('voxel_size', C.c_float * 3), ('offsets', C.c_float * 3), ('eps', C.c_float),
                 ('momentum', C.c_float), ('training', C.c_int32), ('in_features', C.c_int32),

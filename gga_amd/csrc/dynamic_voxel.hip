@@ -22,6 +22,7 @@
 // read from `order` / `point2voxel` / arg-max is bounded by construction (order is a permutation of [0, n), voxel ids are
 // < the device-side voxel count <= n) and the voxel count is clamped to the rows the caller allocated.
 #include "gga_common.h"
+#include "pfn_common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -469,162 +470,72 @@ extern "C" int gga_dynamic_scatter_bwd(const float* grad_out, int channels, int6
 
 // ---- fused DynamicPillarFeatureNet ----------------------------------------------------------------------------------
 // The shipped form only: one layer, 4 point features -> 64 channels, mode = 'max', cluster and voxel centre, no distance,
-// affine BatchNorm1d with running statistics, fp32 (pillar_encoder.py:276-323). The structure of pfn.hip without the padding:
+// affine BatchNorm1d with running statistics, fp32 (pillar_encoder.py:276-323). The structure of pfn.hip without the padding;
+// constants, the layout of `saved`, the voxel centre, the weight load, the count clamps and the two block-reduction tails
+// are pfn_common.h's, and the statistics and backward-close kernels are pfn.hip's own (one definition for both fronts):
 //
 //   pass 0  per-voxel mean of the points: the mean scatter above on the 4 point features (x, y, z used).
 //   pass 1  dpfn_moments_kernel  first (10) and second (55) moments of the decorated features over the kept points, f64, in a
 //                                fixed order (grid-stride over the sorted positions, shuffle tree, block partials).
-//           dpfn_stats_kernel    z = W f is linear, so the BatchNorm batch statistics over the R = kept points follow from
-//                                the moments; scale / shift per channel; running statistics updated.
+//           pfn_launch_stats     z = W f is linear, so the BatchNorm batch statistics over the R = kept points follow from
+//                                the moments; scale / shift per channel; running statistics updated unless R = 0.
 //   pass 2  dpfn_tile_kernel     long segments (more than DV_CHUNK points): one wave per tile of sorted positions, lane =
 //                                channel, partial max + arg-max of the (at most two) long segments that meet the tile.
 //           dpfn_voxel_kernel    one wave per voxel, lane = channel, the 10 weights in registers: relu(z scale + shift),
 //                                running max with its arg-max point (i32; strict >, so the lowest point index keeps a tie),
 //                                or the tile partials combined in tile order; one 256 B store per voxel.
 //   backward dpfn_bwd_kernel     per channel A = sum g, Bx = sum g xhat, G[10] = sum g f(arg-max point);
-//           dpfn_bwd_final_kernel closes the BatchNorm backward analytically from the moments (as pfn_bwd_final_kernel).
+//           pfn_launch_bwd_final closes the BatchNorm backward analytically from the moments.
 // Decoration: (x, y, z, r, x-mx, y-my, z-mz, x-cx, y-cy, z-cz) - no legacy in-place quirk in the dynamic class.
-#define DPFN_C 64
-#define DPFN_F 10
-#define DPFN_NM 65            // 10 first moments + 55 second moments
-#define DPFN_SAVED 238        // S1[10] S2[100] mean[64] invstd[64] (doubles); saved[238] = rows normalised over
-#define DPFN_BW 12            // per-channel accumulators of the backward: A, Bx, G[10]
-
-struct DpfnGeom {
-    float vx, vy, vz, xo, yo, zo;
-};
-
-__device__ __forceinline__ void dpfn_decorate(const float4 p, const int4 co, const float4 mu, const DpfnGeom g, float f[DPFN_F]) {
-    // coors * v + offset as TWO rounded f32 ops like the eager ops (see pfn.hip: a 1-ulp difference of the ~70 m centre is
-    // amplified by gamma * invstd downstream): the product passes through an empty asm so that it is not fused into the sum
-    float tx = (float)co.w * g.vx, ty = (float)co.z * g.vy, tz = (float)co.y * g.vz;
-    asm volatile("" : "+v"(tx), "+v"(ty), "+v"(tz));
+// counts = {voxels, kept points} of the map on the device: pfn_clamped(counts, rows) voxels, pfn_clamped(counts + 1, n) points.
+__device__ __forceinline__ void dpfn_decorate(const float4 p, const int4 co, const float4 mu, const PfnGeom g, float f[PFN_F]) {
+    float cen[3];
+    pfn_centre(co, g, cen);
     f[0] = p.x; f[1] = p.y; f[2] = p.z; f[3] = p.w;
     f[4] = p.x - mu.x; f[5] = p.y - mu.y; f[6] = p.z - mu.z;
-    f[7] = p.x - (tx + g.xo); f[8] = p.y - (ty + g.yo); f[9] = p.z - (tz + g.zo);
+    f[7] = p.x - cen[0]; f[8] = p.y - cen[1]; f[9] = p.z - cen[2];
 }
 
-__device__ __forceinline__ float dpfn_z(const float f[DPFN_F], const float w[DPFN_F]) {
+__device__ __forceinline__ float dpfn_z(const float f[PFN_F], const float w[PFN_F]) {
     float z = 0.0f;
 #pragma unroll
-    for (int a = 0; a < DPFN_F; ++a) z = fmaf(f[a], w[a], z);       // explicit: the same bits wherever a point is evaluated
+    for (int a = 0; a < PFN_F; ++a) z = fmaf(f[a], w[a], z);       // explicit: the same bits wherever a point is evaluated
     return z;
-}
-
-__device__ __forceinline__ int64_t dpfn_kept(const int32_t* __restrict__ counts, int64_t n) {
-    const int64_t v = counts[1];
-    return v < 0 ? 0 : (v < n ? v : n);
-}
-__device__ __forceinline__ int64_t dpfn_voxels(const int32_t* __restrict__ counts, int64_t rows) {
-    const int64_t v = counts[0];
-    return v < 0 ? 0 : (v < rows ? v : rows);
 }
 
 __global__ __launch_bounds__(256) void dpfn_moments_kernel(const float4* __restrict__ points, const int4* __restrict__ coors,
                                                           int64_t n, int64_t rows, const int32_t* __restrict__ order,
                                                           const int32_t* __restrict__ p2v, const int32_t* __restrict__ counts,
-                                                          const float4* __restrict__ mean, DpfnGeom g,
+                                                          const float4* __restrict__ mean, PfnGeom g,
                                                           double* __restrict__ partials) {
-    const int64_t nv = dpfn_kept(counts, n);
-    double acc[DPFN_NM];
+    const int64_t nv = pfn_clamped(counts + 1, n);
+    double acc[PFN_NM];
 #pragma unroll
-    for (int i = 0; i < DPFN_NM; ++i) acc[i] = 0.0;
+    for (int i = 0; i < PFN_NM; ++i) acc[i] = 0.0;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < nv; j += (int64_t)gridDim.x * 256) {
         const int32_t p = order[j];
         const int32_t v = p2v[p];
         if (v < 0 || v >= rows) continue;
-        float f[DPFN_F];
+        float f[PFN_F];
         dpfn_decorate(points[p], coors[p], mean[v], g, f);
-        int k = DPFN_F;
+        int k = PFN_F;
 #pragma unroll
-        for (int a = 0; a < DPFN_F; ++a) {
+        for (int a = 0; a < PFN_F; ++a) {
             acc[a] += (double)f[a];
 #pragma unroll
-            for (int b = a; b < DPFN_F; ++b) acc[k++] += (double)f[a] * (double)f[b];
+            for (int b = a; b < PFN_F; ++b) acc[k++] += (double)f[a] * (double)f[b];
         }
     }
-    __shared__ double sh[4][DPFN_NM];
-#pragma unroll
-    for (int i = 0; i < DPFN_NM; ++i) {
-        const double s = wave_sum(acc[i]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < DPFN_NM)
-        partials[(int64_t)blockIdx.x * DPFN_NM + threadIdx.x] =
-            (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-
-// one block of 64 threads (lane = channel)
-__global__ __launch_bounds__(64) void dpfn_stats_kernel(const double* __restrict__ partials, int nblocks, int64_t n,
-                                                       const int32_t* __restrict__ counts, const float* __restrict__ weight,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                       float momentum, int training, float* __restrict__ running_mean,
-                                                       float* __restrict__ running_var, double* __restrict__ saved,
-                                                       float* __restrict__ scale_shift) {
-    __shared__ double S[DPFN_NM];
-    const int c = threadIdx.x;
-    double rows = (double)dpfn_kept(counts, n);
-    const bool empty = rows < 1.0;
-    rows = empty ? 1.0 : rows;
-    if (c == 0) saved[DPFN_SAVED] = rows;
-    if (training) {
-        for (int i = c; i < DPFN_NM; i += 64) {
-            double s = 0.0;
-#pragma unroll 16
-            for (int b = 0; b < nblocks; ++b) s += partials[(int64_t)b * DPFN_NM + i];   // fixed order
-            S[i] = s;
-        }
-        __syncthreads();
-        double S1[DPFN_F], S2[DPFN_F][DPFN_F];
-        int k = DPFN_F;
-        for (int a = 0; a < DPFN_F; ++a) {
-            S1[a] = S[a];
-            for (int b = a; b < DPFN_F; ++b) { S2[a][b] = S[k]; S2[b][a] = S[k]; ++k; }
-        }
-        double w[DPFN_F];
-        for (int a = 0; a < DPFN_F; ++a) w[a] = (double)weight[c * DPFN_F + a];
-        double m1 = 0.0, m2 = 0.0;
-        for (int a = 0; a < DPFN_F; ++a) {
-            m1 += w[a] * S1[a];
-            double t = 0.0;
-            for (int b = 0; b < DPFN_F; ++b) t += S2[a][b] * w[b];
-            m2 += w[a] * t;
-        }
-        const double mean = m1 / rows;
-        double var = m2 / rows - mean * mean;          // biased, as BatchNorm normalises with
-        var = var > 0.0 ? var : 0.0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        if (c == 0)
-            for (int a = 0; a < DPFN_F; ++a) {
-                saved[a] = S1[a];
-                for (int b = 0; b < DPFN_F; ++b) saved[DPFN_F + a * DPFN_F + b] = S2[a][b];
-            }
-        saved[110 + c] = mean;
-        saved[174 + c] = invstd;
-        const float sc = gamma[c] * (float)invstd;
-        scale_shift[c] = sc;
-        scale_shift[DPFN_C + c] = beta[c] - (float)mean * sc;
-        if (!empty) {       // running stats: momentum update with the UNBIASED variance (torch BatchNorm); no rows, no update
-            const double unb = rows > 1.0 ? var * rows / (rows - 1.0) : var;
-            running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
-            running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unb;
-        }
-    } else {
-        const float invstd = 1.0f / sqrtf(running_var[c] + eps);
-        const float sc = gamma[c] * invstd;
-        scale_shift[c] = sc;
-        scale_shift[DPFN_C + c] = beta[c] - running_mean[c] * sc;
-    }
+    pfn_moments_commit(acc, partials);
 }
 
 // running max of relu(z scale + shift) over the sorted positions [lo, hi) of voxel v; lane = channel
 __device__ __forceinline__ void dpfn_walk(const float4* __restrict__ points, const int4* __restrict__ coors,
                                           const int32_t* __restrict__ order, int64_t lo, int64_t hi, const float4 mu,
-                                          const DpfnGeom g, const float w[DPFN_F], float sc, float sh, DvAcc& a) {
+                                          const PfnGeom g, const float w[PFN_F], float sc, float sh, DvAcc& a) {
     for (int64_t j = lo; j < hi; ++j) {
         const int32_t p = order[j];                      // wave-uniform
-        float f[DPFN_F];
+        float f[PFN_F];
         dpfn_decorate(points[p], coors[p], mu, g, f);
         const float y = fmaxf(fmaf(dpfn_z(f, w), sc, sh), 0.0f);
         dv_take<true>(a, y, p);
@@ -635,21 +546,20 @@ __global__ __launch_bounds__(256) void dpfn_tile_kernel(const float4* __restrict
                                                        int64_t n, int64_t rows, int64_t ntiles, const int32_t* __restrict__ order,
                                                        const int32_t* __restrict__ p2v, const int32_t* __restrict__ voxel_start,
                                                        const int32_t* __restrict__ counts, const float4* __restrict__ mean,
-                                                       DpfnGeom g, const float* __restrict__ weight,
+                                                       PfnGeom g, const float* __restrict__ weight,
                                                        const float* __restrict__ scale_shift, float* __restrict__ part_v,
                                                        int32_t* __restrict__ part_i) {
     const int lane = threadIdx.x & 63;
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= ntiles) return;
-    const int64_t nv = dpfn_kept(counts, n);
+    const int64_t nv = pfn_clamped(counts + 1, n);
     const int64_t t0 = t * DV_CHUNK;
     if (t0 >= nv) return;
     const int64_t t1 = (t0 + DV_CHUNK < nv) ? t0 + DV_CHUNK : nv;
     const int32_t va = p2v[order[t0]], vb = p2v[order[t1 - 1]];
-    float w[DPFN_F];
-#pragma unroll
-    for (int a = 0; a < DPFN_F; ++a) w[a] = weight[lane * DPFN_F + a];
-    const float sc = scale_shift[lane], sh = scale_shift[DPFN_C + lane];
+    float w[PFN_F];
+    pfn_load_weights(weight, lane, w);
+    const float sc = scale_shift[lane], sh = scale_shift[PFN_C + lane];
     for (int slot = 0; slot < 2; ++slot) {
         const int32_t v = slot == 0 ? va : vb;
         if (v < 0 || v >= rows || (slot == 1 && vb == va)) continue;
@@ -657,24 +567,23 @@ __global__ __launch_bounds__(256) void dpfn_tile_kernel(const float4* __restrict
         if (e - s <= DV_CHUNK) continue;
         DvAcc a = {0.0f, DV_NO_POINT};
         dpfn_walk(points, coors, order, s > t0 ? s : t0, e < t1 ? e : t1, mean[v], g, w, sc, sh, a);
-        part_v[(t * 2 + slot) * DPFN_C + lane] = a.v;
-        part_i[(t * 2 + slot) * DPFN_C + lane] = a.idx;
+        part_v[(t * 2 + slot) * PFN_C + lane] = a.v;
+        part_i[(t * 2 + slot) * PFN_C + lane] = a.idx;
     }
 }
 
 __global__ __launch_bounds__(256) void dpfn_voxel_kernel(const float4* __restrict__ points, const int4* __restrict__ coors,
                                                         int64_t rows, const int32_t* __restrict__ order,
                                                         const int32_t* __restrict__ voxel_start, const int32_t* __restrict__ counts,
-                                                        const float4* __restrict__ mean, DpfnGeom g,
+                                                        const float4* __restrict__ mean, PfnGeom g,
                                                         const float* __restrict__ weight, const float* __restrict__ scale_shift,
                                                         const float* __restrict__ part_v, const int32_t* __restrict__ part_i,
                                                         float* __restrict__ out, int32_t* __restrict__ argmax) {
     const int lane = threadIdx.x & 63;
-    const int64_t m = dpfn_voxels(counts, rows);
-    float w[DPFN_F];
-#pragma unroll
-    for (int a = 0; a < DPFN_F; ++a) w[a] = weight[lane * DPFN_F + a];
-    const float sc = scale_shift[lane], sh = scale_shift[DPFN_C + lane];
+    const int64_t m = pfn_clamped(counts, rows);
+    float w[PFN_F];
+    pfn_load_weights(weight, lane, w);
+    const float sc = scale_shift[lane], sh = scale_shift[PFN_C + lane];
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); v < m; v += nwaves) {
         const int64_t s = voxel_start[v], e = voxel_start[v + 1];
@@ -684,112 +593,64 @@ __global__ __launch_bounds__(256) void dpfn_voxel_kernel(const float4* __restric
         } else {
             const int64_t ta = s / DV_CHUNK, tb = (e - 1) / DV_CHUNK;
             for (int64_t t = ta; t <= tb; ++t) {
-                const int64_t q = (t * 2 + ((s <= t * DV_CHUNK) ? 0 : 1)) * DPFN_C + lane;
+                const int64_t q = (t * 2 + ((s <= t * DV_CHUNK) ? 0 : 1)) * PFN_C + lane;
                 dv_merge<true>(a, part_v[q], part_i[q]);
             }
         }
-        out[v * DPFN_C + lane] = a.v;
-        argmax[v * DPFN_C + lane] = a.idx;
+        out[v * PFN_C + lane] = a.v;
+        argmax[v * PFN_C + lane] = a.idx;
     }
 }
 
 __global__ __launch_bounds__(256) void dpfn_bwd_kernel(const float4* __restrict__ points, const int4* __restrict__ coors, int64_t n,
                                                       int64_t rows, const int32_t* __restrict__ counts,
-                                                      const float4* __restrict__ mean, DpfnGeom g, const float* __restrict__ weight,
+                                                      const float4* __restrict__ mean, PfnGeom g, const float* __restrict__ weight,
                                                       const double* __restrict__ saved, const float* __restrict__ out,
                                                       const int32_t* __restrict__ argmax, const float* __restrict__ grad_out,
                                                       float* __restrict__ partials) {
     const int lane = threadIdx.x & 63;
-    float w[DPFN_F];
+    float w[PFN_F];
+    pfn_load_weights(weight, lane, w);
+    const float mean_c = (float)saved[PFN_SAVED_MEAN + lane], invstd_c = (float)saved[PFN_SAVED_INVSTD + lane];
+    float acc[PFN_BW];
 #pragma unroll
-    for (int a = 0; a < DPFN_F; ++a) w[a] = weight[lane * DPFN_F + a];
-    const float mean_c = (float)saved[110 + lane], invstd_c = (float)saved[174 + lane];
-    float acc[DPFN_BW];
-#pragma unroll
-    for (int i = 0; i < DPFN_BW; ++i) acc[i] = 0.0f;
-    const int64_t m = dpfn_voxels(counts, rows);
+    for (int i = 0; i < PFN_BW; ++i) acc[i] = 0.0f;
+    const int64_t m = pfn_clamped(counts, rows);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); v < m; v += nwaves) {
-        const float y = out[v * DPFN_C + lane];
-        const float gy = y > 0.0f ? grad_out[v * DPFN_C + lane] : 0.0f;    // ReLU gate
-        const int32_t bi = argmax[v * DPFN_C + lane];
+        const float y = out[v * PFN_C + lane];
+        const float gy = y > 0.0f ? grad_out[v * PFN_C + lane] : 0.0f;    // ReLU gate
+        const int32_t bi = argmax[v * PFN_C + lane];
         if (bi < 0 || bi >= n) continue;                                     // (never: every voxel has a point)
-        float f[DPFN_F];
+        float f[PFN_F];
         dpfn_decorate(points[bi], coors[bi], mean[v], g, f);
         const float xhat = (dpfn_z(f, w) - mean_c) * invstd_c;
         acc[0] += gy;
         acc[1] += gy * xhat;
 #pragma unroll
-        for (int a = 0; a < DPFN_F; ++a) acc[2 + a] += gy * f[a];
+        for (int a = 0; a < PFN_F; ++a) acc[2 + a] += gy * f[a];
     }
-    __shared__ float sh[4][DPFN_BW][DPFN_C];
-#pragma unroll
-    for (int i = 0; i < DPFN_BW; ++i) sh[threadIdx.x >> 6][i][lane] = acc[i];
-    __syncthreads();
-    for (int t = threadIdx.x; t < DPFN_BW * DPFN_C; t += 256) {
-        const int i = t / DPFN_C, c = t - i * DPFN_C;
-        partials[(int64_t)blockIdx.x * DPFN_BW * DPFN_C + t] = (sh[0][i][c] + sh[1][i][c]) + (sh[2][i][c] + sh[3][i][c]);
-    }
+    pfn_bwd_commit(acc, partials);
 }
 
-__global__ __launch_bounds__(768) void dpfn_bwd_final_kernel(const float* __restrict__ partials, int nblocks,
-                                                            const float* __restrict__ weight, const float* __restrict__ gamma,
-                                                            const double* __restrict__ saved, float* __restrict__ grad_weight,
-                                                            float* __restrict__ grad_gamma, float* __restrict__ grad_beta) {
-    __shared__ double red[DPFN_BW][DPFN_C];
-    {
-        const int t = threadIdx.x;
-        double s = 0.0;
-#pragma unroll 16
-        for (int b = 0; b < nblocks; ++b) s += (double)partials[(int64_t)b * DPFN_BW * DPFN_C + t];     // fixed order
-        red[t / DPFN_C][t % DPFN_C] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x >= DPFN_C) return;
-    const int c = threadIdx.x;
-    const double A = red[0][c], Bx = red[1][c];
-    const double rows = saved[DPFN_SAVED];
-    const double mean = saved[110 + c], invstd = saved[174 + c];
-    grad_beta[c] = (float)A;
-    grad_gamma[c] = (float)Bx;
-    const double k = (double)gamma[c] * invstd;
-    for (int a = 0; a < DPFN_F; ++a) {
-        double s2w = 0.0;
-        for (int b = 0; b < DPFN_F; ++b) s2w += saved[DPFN_F + a * DPFN_F + b] * (double)weight[c * DPFN_F + b];
-        const double xf = invstd * (s2w - mean * saved[a]);                  // sum over the rows of xhat_row * f_row[a]
-        grad_weight[c * DPFN_F + a] = (float)(k * (red[2 + a][c] - A / rows * saved[a] - Bx / rows * xf));
-    }
-}
-
-static int dpfn_blocks(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
-}
-static int dpfn_wave_blocks(int64_t rows) {
-    int64_t b = (rows + 3) / 4;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
-}
 // workspace: mean scatter | block partials (moments f64 / backward f32) | tile partials (value, point) | scale, shift
 static size_t dpfn_ws_scatter(int64_t n) { return gga_align_up(gga_dynamic_scatter_workspace_bytes(n, 4), 256); }
 static size_t dpfn_ws_partials(int64_t n) {
-    const size_t a = (size_t)dpfn_blocks(n) * DPFN_NM * sizeof(double);
-    const size_t b = (size_t)dpfn_wave_blocks(n) * DPFN_BW * DPFN_C * sizeof(float);
+    const size_t a = (size_t)pfn_blocks(n) * PFN_NM * sizeof(double);
+    const size_t b = (size_t)pfn_wave_blocks(n) * PFN_BW * PFN_C * sizeof(float);
     return gga_align_up(a > b ? a : b, 256);
 }
-static size_t dpfn_ws_tiles(int64_t n) { return gga_align_up((size_t)dv_tiles(n) * 2 * DPFN_C * 4, 256); }
+static size_t dpfn_ws_tiles(int64_t n) { return gga_align_up((size_t)dv_tiles(n) * 2 * PFN_C * 4, 256); }
 
 extern "C" size_t gga_dynamic_pfn_workspace_bytes(int64_t n_points) {
     if (n_points < 1) return 0;
-    return dpfn_ws_scatter(n_points) + dpfn_ws_partials(n_points) + 2 * dpfn_ws_tiles(n_points) + 2 * DPFN_C * sizeof(float);
+    return dpfn_ws_scatter(n_points) + dpfn_ws_partials(n_points) + 2 * dpfn_ws_tiles(n_points) + 2 * PFN_C * sizeof(float);
 }
 
 static int dpfn_check(const char* fn, const gga_pfn_params* prm, int64_t n, int64_t rows) {
-    GGA_REQUIRE(prm, "%s: null params", fn);
+    if (int rc = pfn_check_params(fn, prm)) return rc;
     GGA_REQUIRE(n >= 1 && n < (1ll << 30) && rows >= 1 && rows <= n, "%s: bad sizes (n_points=%lld out_rows=%lld)", fn,
                 (long long)n, (long long)rows);
-    GGA_REQUIRE(prm->channels == DPFN_C && prm->in_features == 4,
-                "%s: the fused kernel is specialised for 4 point features -> %d channels (got %d -> %d)", fn, DPFN_C,
-                prm->in_features, prm->channels);
     return GGA_OK;
 }
 
@@ -803,12 +664,8 @@ extern "C" int gga_dynamic_pfn_fwd(const float* points, const int32_t* coors, in
     GGA_REQUIRE(points && coors && order && point2voxel && voxel_start && counts && weight && gamma && beta && running_mean &&
                     running_var && out && argmax && mean && saved && workspace,
                 "gga_dynamic_pfn_fwd: null pointer argument");
-    if (workspace_bytes < gga_dynamic_pfn_workspace_bytes(n_points)) {
-        gga_set_error("gga_dynamic_pfn_fwd: workspace %zu B < required %zu B", workspace_bytes,
-                      gga_dynamic_pfn_workspace_bytes(n_points));
-        return GGA_ERR_WORKSPACE;
-    }
-    const DpfnGeom g = {prm->voxel_size[0], prm->voxel_size[1], prm->voxel_size[2], prm->offsets[0], prm->offsets[1], prm->offsets[2]};
+    GGA_REQUIRE_WORKSPACE("gga_dynamic_pfn_fwd", workspace_bytes, gga_dynamic_pfn_workspace_bytes(n_points));
+    const PfnGeom g = pfn_geom(prm);
     char* w = (char*)workspace;
     void* ws_scatter = w;               w += dpfn_ws_scatter(n_points);
     double* partials = (double*)w;      w += dpfn_ws_partials(n_points);
@@ -818,21 +675,21 @@ extern "C" int gga_dynamic_pfn_fwd(const float* points, const int32_t* coors, in
     if (int rc = gga_dynamic_scatter_fwd(points, 4, n_points, order, point2voxel, voxel_start, counts, out_rows, GGA_DYNAMIC_MEAN,
                                          mean, nullptr, ws_scatter, dpfn_ws_scatter(n_points), stream_))
         return rc;
-    const int nb = dpfn_blocks(n_points);
+    const int nb = pfn_blocks(n_points);
     if (prm->training) {
         hipLaunchKernelGGL(dpfn_moments_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)points, (const int4*)coors, n_points,
                            out_rows, order, point2voxel, counts, (const float4*)mean, g, partials);
         GGA_CHECK_LAUNCH("dpfn_moments_kernel");
     }
-    hipLaunchKernelGGL(dpfn_stats_kernel, dim3(1), dim3(64), 0, stream, partials, nb, n_points, counts, weight, gamma, beta, prm->eps,
-                       prm->momentum, prm->training, running_mean, running_var, saved, scale_shift);
-    GGA_CHECK_LAUNCH("dpfn_stats_kernel");
+    if (int rc = pfn_launch_stats(partials, nb, counts + 1, n_points, 1, 0, weight, gamma, beta, prm, running_mean, running_var, saved,
+                                  scale_shift, stream))
+        return rc;
     const int64_t ntiles = dv_tiles(n_points);
     hipLaunchKernelGGL(dpfn_tile_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, stream, (const float4*)points,
                        (const int4*)coors, n_points, out_rows, ntiles, order, point2voxel, voxel_start, counts, (const float4*)mean, g,
                        weight, scale_shift, part_v, part_i);
     GGA_CHECK_LAUNCH("dpfn_tile_kernel");
-    hipLaunchKernelGGL(dpfn_voxel_kernel, dim3(dpfn_wave_blocks(out_rows)), dim3(256), 0, stream, (const float4*)points,
+    hipLaunchKernelGGL(dpfn_voxel_kernel, dim3(pfn_wave_blocks(out_rows)), dim3(256), 0, stream, (const float4*)points,
                        (const int4*)coors, out_rows, order, voxel_start, counts, (const float4*)mean, g, weight, scale_shift, part_v,
                        part_i, out, argmax);
     GGA_CHECK_LAUNCH("dpfn_voxel_kernel");
@@ -850,19 +707,12 @@ extern "C" int gga_dynamic_pfn_bwd(const float* points, const int32_t* coors, in
                     grad_gamma && grad_beta && workspace,
                 "gga_dynamic_pfn_bwd: null pointer argument");
     GGA_REQUIRE(prm->training, "gga_dynamic_pfn_bwd: backward is defined for training-mode batch statistics");
-    if (workspace_bytes < gga_dynamic_pfn_workspace_bytes(n_points)) {
-        gga_set_error("gga_dynamic_pfn_bwd: workspace %zu B < required %zu B", workspace_bytes,
-                      gga_dynamic_pfn_workspace_bytes(n_points));
-        return GGA_ERR_WORKSPACE;
-    }
-    const DpfnGeom g = {prm->voxel_size[0], prm->voxel_size[1], prm->voxel_size[2], prm->offsets[0], prm->offsets[1], prm->offsets[2]};
+    GGA_REQUIRE_WORKSPACE("gga_dynamic_pfn_bwd", workspace_bytes, gga_dynamic_pfn_workspace_bytes(n_points));
+    const PfnGeom g = pfn_geom(prm);
     float* partials = (float*)((char*)workspace + dpfn_ws_scatter(n_points));
-    const int nb = dpfn_wave_blocks(out_rows);
+    const int nb = pfn_wave_blocks(out_rows);
     hipLaunchKernelGGL(dpfn_bwd_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)points, (const int4*)coors, n_points, out_rows,
                        counts, (const float4*)mean, g, weight, saved, out, argmax, grad_out, partials);
     GGA_CHECK_LAUNCH("dpfn_bwd_kernel");
-    hipLaunchKernelGGL(dpfn_bwd_final_kernel, dim3(1), dim3(DPFN_BW * DPFN_C), 0, stream, (const float*)partials, nb, weight, gamma,
-                       saved, grad_weight, grad_gamma, grad_beta);
-    GGA_CHECK_LAUNCH("dpfn_bwd_final_kernel");
-    return GGA_OK;
+    return pfn_launch_bwd_final(partials, nb, weight, gamma, saved, grad_weight, grad_gamma, grad_beta, stream);
 }

@@ -30,6 +30,14 @@ int gga_bn_bwd_finalize(const double* partials, int nblocks, int channels, int64
         }                                           \
     } while (0)
 
+#define GGA_REQUIRE_WORKSPACE(fn, have, need)                                                                   \
+    do {                                                                                                        \
+        if ((have) < (need)) {                                                                                  \
+            gga_set_error("%s: workspace %zu B < required %zu B", fn, (size_t)(have), (size_t)(need));          \
+            return GGA_ERR_WORKSPACE;                                                                           \
+        }                                                                                                       \
+    } while (0)
+
 #define GGA_CHECK_LAUNCH(name)                                                    \
     do {                                                                          \
         hipError_t e_ = hipGetLastError();                                        \

@@ -24,24 +24,13 @@
 //                                dW_c = gamma*invstd*(G - A/R*S1 - Bx/R*invstd*(S2 w_c - mean*S1)).
 // HBM traffic: the voxel buffer is read twice (only the lines holding valid points), the
 // [M,64] output written once; nothing of size M*P*64 ever exists.
-#include "gga_common.h"
-
-// rows the caller marks valid: min(m, *num_valid) when a device count is given (capacity-sized
-// buffers of the sync-free voxelizer), m otherwise
-__device__ __forceinline__ int64_t pfn_valid_rows(int64_t m, const int32_t* __restrict__ num_valid) {
-    if (!num_valid) return m;
-    const int64_t v = *num_valid;
-    return v < m ? (v < 0 ? 0 : v) : m;
-}
-
-#define PFN_C 64
-#define PFN_F 10
-#define PFN_NM 65            // 10 first moments + 55 second moments
-#define PFN_SAVED 238        // S1[10] S2[100] mean[64] invstd[64]  (doubles); saved[238] = rows normalised over
-
-struct PfnGeom {
-    float vx, vy, vz, xo, yo, zo;
-};
+//
+// pfn_common.h holds what this front shares with the fused DynamicPillarFeatureNet of dynamic_voxel.hip: the constants
+// and the layout of `saved`, the pillar centre, the weight load, the count clamp and the two block-reduction tails.
+// pfn_stats_kernel and pfn_bwd_final_kernel are defined here and serve both fronts (pfn_launch_stats,
+// pfn_launch_bwd_final). The rows the caller marks valid are pfn_clamped(num_valid, m): min(m, *num_valid) when a
+// device count is given (capacity-sized buffers of the sync-free voxelizer), m otherwise.
+#include "pfn_common.h"
 
 // decorated feature vector of one point (pillar_encoder.py:106-150, legacy=True):
 // (x-cx, y-cy, z-cz, r, x-mx, y-my, z-mz, x-cx, y-cy, z-cz)
@@ -57,13 +46,7 @@ __device__ __forceinline__ void pfn_pillar_consts(const float4* __restrict__ pts
     for (int p = 0; p < n; ++p) { const float4 q = pts[p]; sx += q.x; sy += q.y; sz += q.z; }
     const float fn = (float)n;
     mean[0] = sx / fn; mean[1] = sy / fn; mean[2] = sz / fn;       // sum(dim=1) / num_points
-    // coors[:,3]*vx + x_offset as TWO rounded f32 ops like the reference: a 1-ulp difference of the
-    // ~70 m centre is amplified by gamma*invstd ~ 30-60 downstream. HIP's __fmul_rn/__fadd_rn are
-    // plain * and + and hipcc fuses them under its default -ffp-contract=fast, so the product is
-    // passed through an empty asm to keep it a separately rounded value.
-    float tx = (float)co.w * g.vx, ty = (float)co.z * g.vy, tz = (float)co.y * g.vz;
-    asm volatile("" : "+v"(tx), "+v"(ty), "+v"(tz));
-    cen[0] = tx + g.xo; cen[1] = ty + g.yo; cen[2] = tz + g.zo;
+    pfn_centre(co, g, cen);
 }
 
 __global__ __launch_bounds__(256) void pfn_moments_kernel(const float4* __restrict__ voxels,
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(256) void pfn_moments_kernel(const float4* __restri
                                                          const int4* __restrict__ coors, int64_t m,
                                                          const int32_t* __restrict__ num_valid, int P,
                                                          PfnGeom g, double* __restrict__ partials) {
-    m = pfn_valid_rows(m, num_valid);
+    m = pfn_clamped(num_valid, m);
     double acc[PFN_NM];
 #pragma unroll
     for (int i = 0; i < PFN_NM; ++i) acc[i] = 0.0;
@@ -99,31 +82,23 @@ __global__ __launch_bounds__(256) void pfn_moments_kernel(const float4* __restri
 #pragma unroll
         for (int i = 0; i < PFN_NM; ++i) acc[i] += (double)loc[i];
     }
-    __shared__ double sh[4][PFN_NM];
-#pragma unroll
-    for (int i = 0; i < PFN_NM; ++i) {
-        const double s = wave_sum(acc[i]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < PFN_NM)
-        partials[(int64_t)blockIdx.x * PFN_NM + threadIdx.x] =
-            (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    pfn_moments_commit(acc, partials);
 }
 
-// one block of 64 threads (lane = channel)
+// one block of 64 threads (lane = channel); rows = pfn_clamped(count, cap) * rows_per_item
 __global__ __launch_bounds__(64) void pfn_stats_kernel(const double* __restrict__ partials, int nblocks,
-                                                      int64_t m, const int32_t* __restrict__ num_valid, int P,
-                                                      const float* __restrict__ weight,
+                                                      const int32_t* __restrict__ count, int64_t cap, int rows_per_item,
+                                                      int update_when_empty, const float* __restrict__ weight,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float eps, float momentum, int training,
                                                       float* __restrict__ running_mean, float* __restrict__ running_var,
                                                       double* __restrict__ saved, float* __restrict__ scale_shift) {
     __shared__ double S[PFN_NM];
     const int c = threadIdx.x;
-    double rows = (double)pfn_valid_rows(m, num_valid) * (double)P;
-    rows = rows > 0.0 ? rows : 1.0;
-    if (c == 0) saved[PFN_SAVED] = rows;
+    double rows = (double)pfn_clamped(count, cap) * (double)rows_per_item;
+    const bool empty = rows < 1.0;
+    rows = empty ? 1.0 : rows;
+    if (c == 0) saved[PFN_SAVED_ROWS] = rows;
     if (training) {
         for (int i = c; i < PFN_NM; i += 64) {
             double s = 0.0;
@@ -154,18 +129,19 @@ __global__ __launch_bounds__(64) void pfn_stats_kernel(const double* __restrict_
         const double invstd = 1.0 / sqrt(var + (double)eps);
         if (c == 0)
             for (int a = 0; a < PFN_F; ++a) {
-                saved[a] = S1[a];
-                for (int b = 0; b < PFN_F; ++b) saved[PFN_F + a * PFN_F + b] = S2[a][b];
+                saved[PFN_SAVED_S1 + a] = S1[a];
+                for (int b = 0; b < PFN_F; ++b) saved[PFN_SAVED_S2 + a * PFN_F + b] = S2[a][b];
             }
-        saved[110 + c] = mean;
-        saved[174 + c] = invstd;
+        saved[PFN_SAVED_MEAN + c] = mean;
+        saved[PFN_SAVED_INVSTD + c] = invstd;
         const float sc = gamma[c] * (float)invstd;
         scale_shift[c] = sc;
         scale_shift[PFN_C + c] = beta[c] - (float)mean * sc;
-        // running stats: momentum update with the UNBIASED variance (torch BatchNorm)
-        const double unb = rows > 1.0 ? var * rows / (rows - 1.0) : var;
-        running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
-        running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unb;
+        if (!empty || update_when_empty) {      // running stats: momentum update with the UNBIASED variance (torch BatchNorm)
+            const double unb = rows > 1.0 ? var * rows / (rows - 1.0) : var;
+            running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
+            running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unb;
+        }
     } else {
         const float invstd = 1.0f / sqrtf(running_var[c] + eps);
         const float sc = gamma[c] * invstd;
@@ -183,10 +159,9 @@ __global__ __launch_bounds__(256) void pfn_apply_kernel(const float4* __restrict
                                                        const float* __restrict__ scale_shift,
                                                        float* __restrict__ out, uint8_t* __restrict__ argmax) {
     const int lane = threadIdx.x & 63;
-    const int64_t mv = pfn_valid_rows(m, num_valid);
+    const int64_t mv = pfn_clamped(num_valid, m);
     float w[PFN_F];
-#pragma unroll
-    for (int a = 0; a < PFN_F; ++a) w[a] = weight[lane * PFN_F + a];
+    pfn_load_weights(weight, lane, w);
     const float sc = scale_shift[lane], sh = scale_shift[PFN_C + lane];
     const float ypad = fmaxf(sh, 0.0f);               // a zero (padding) row after BN + ReLU
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -223,8 +198,6 @@ __global__ __launch_bounds__(256) void pfn_apply_kernel(const float4* __restrict
     }
 }
 
-#define PFN_BW 12   // per-channel accumulators of the backward: A, Bx, G[10]
-
 __global__ __launch_bounds__(256) void pfn_bwd_kernel(const float4* __restrict__ voxels,
                                                      const int32_t* __restrict__ num_points,
                                                      const int4* __restrict__ coors, int64_t m,
@@ -234,13 +207,12 @@ __global__ __launch_bounds__(256) void pfn_bwd_kernel(const float4* __restrict__
                                                      const float* __restrict__ grad_out, float* __restrict__ partials) {
     const int lane = threadIdx.x & 63;
     float w[PFN_F];
-#pragma unroll
-    for (int a = 0; a < PFN_F; ++a) w[a] = weight[lane * PFN_F + a];
-    const float mean_c = (float)saved[110 + lane], invstd_c = (float)saved[174 + lane];
+    pfn_load_weights(weight, lane, w);
+    const float mean_c = (float)saved[PFN_SAVED_MEAN + lane], invstd_c = (float)saved[PFN_SAVED_INVSTD + lane];
     float acc[PFN_BW];
 #pragma unroll
     for (int i = 0; i < PFN_BW; ++i) acc[i] = 0.0f;
-    m = pfn_valid_rows(m, num_valid);
+    m = pfn_clamped(num_valid, m);
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     for (int64_t v = wave0; v < m; v += nwaves) {
@@ -271,14 +243,7 @@ __global__ __launch_bounds__(256) void pfn_bwd_kernel(const float4* __restrict__
 #pragma unroll
         for (int a = 0; a < PFN_F; ++a) acc[2 + a] += gy * f[a];
     }
-    __shared__ float sh[4][PFN_BW][PFN_C];
-#pragma unroll
-    for (int i = 0; i < PFN_BW; ++i) sh[threadIdx.x >> 6][i][lane] = acc[i];
-    __syncthreads();
-    for (int t = threadIdx.x; t < PFN_BW * PFN_C; t += 256) {
-        const int i = t / PFN_C, c = t - i * PFN_C;
-        partials[(int64_t)blockIdx.x * PFN_BW * PFN_C + t] = (sh[0][i][c] + sh[1][i][c]) + (sh[2][i][c] + sh[3][i][c]);
-    }
+    pfn_bwd_commit(acc, partials);
 }
 
 __global__ __launch_bounds__(768) void pfn_bwd_final_kernel(const float* __restrict__ partials, int nblocks,
@@ -302,26 +267,37 @@ __global__ __launch_bounds__(768) void pfn_bwd_final_kernel(const float* __restr
     if (threadIdx.x >= PFN_C) return;
     const int c = threadIdx.x;
     const double A = red[0][c], Bx = red[1][c];
-    const double rows = saved[PFN_SAVED];
-    const double mean = saved[110 + c], invstd = saved[174 + c];
+    const double rows = saved[PFN_SAVED_ROWS];
+    const double mean = saved[PFN_SAVED_MEAN + c], invstd = saved[PFN_SAVED_INVSTD + c];
     grad_beta[c] = (float)A;
     grad_gamma[c] = (float)Bx;
     const double k = (double)gamma[c] * invstd;
+    const double* S1 = saved + PFN_SAVED_S1;
     for (int a = 0; a < PFN_F; ++a) {
         double s2w = 0.0;
-        for (int b = 0; b < PFN_F; ++b) s2w += saved[PFN_F + a * PFN_F + b] * (double)weight[c * PFN_F + b];
-        const double xf = invstd * (s2w - mean * saved[a]);                  // sum_rows xhat_row * f_row[a]
-        grad_weight[c * PFN_F + a] = (float)(k * (red[2 + a][c] - A / rows * saved[a] - Bx / rows * xf));
+        for (int b = 0; b < PFN_F; ++b) s2w += saved[PFN_SAVED_S2 + a * PFN_F + b] * (double)weight[c * PFN_F + b];
+        const double xf = invstd * (s2w - mean * S1[a]);                     // sum_rows xhat_row * f_row[a]
+        grad_weight[c * PFN_F + a] = (float)(k * (red[2 + a][c] - A / rows * S1[a] - Bx / rows * xf));
     }
 }
 
-static int pfn_blocks(int64_t m) {
-    int64_t b = (m + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
+int pfn_launch_stats(const double* partials, int nblocks, const int32_t* count, int64_t cap, int rows_per_item,
+                     int update_when_empty, const float* weight, const float* gamma, const float* beta,
+                     const gga_pfn_params* prm, float* running_mean, float* running_var, double* saved, float* scale_shift,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL(pfn_stats_kernel, dim3(1), dim3(64), 0, stream, partials, nblocks, count, cap, rows_per_item,
+                       update_when_empty, weight, gamma, beta, prm->eps, prm->momentum, prm->training, running_mean,
+                       running_var, saved, scale_shift);
+    GGA_CHECK_LAUNCH("pfn_stats_kernel");
+    return GGA_OK;
 }
-static int pfn_wave_blocks(int64_t m) {
-    int64_t b = (m + 3) / 4;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
+
+int pfn_launch_bwd_final(const float* partials, int nblocks, const float* weight, const float* gamma, const double* saved,
+                         float* grad_weight, float* grad_gamma, float* grad_beta, hipStream_t stream) {
+    hipLaunchKernelGGL(pfn_bwd_final_kernel, dim3(1), dim3(PFN_BW * PFN_C), 0, stream, partials, nblocks, weight, gamma,
+                       saved, grad_weight, grad_gamma, grad_beta);
+    GGA_CHECK_LAUNCH("pfn_bwd_final_kernel");
+    return GGA_OK;
 }
 
 extern "C" size_t gga_pfn_workspace_bytes(int64_t m) {
@@ -331,11 +307,8 @@ extern "C" size_t gga_pfn_workspace_bytes(int64_t m) {
 }
 
 static int pfn_check(const char* fn, const gga_pfn_params* prm, int64_t m, int P) {
-    GGA_REQUIRE(prm, "%s: null params", fn);
+    if (int rc = pfn_check_params(fn, prm)) return rc;
     GGA_REQUIRE(m >= 1 && P >= 1 && P <= 254, "%s: bad sizes (m=%lld, max_points=%d; need 1..254)", fn, (long long)m, P);
-    GGA_REQUIRE(prm->channels == PFN_C && prm->in_features == 4,
-                "%s: the fused kernel is specialised for 4 point features -> %d channels (got %d -> %d)", fn, PFN_C,
-                prm->in_features, prm->channels);
     return GGA_OK;
 }
 
@@ -348,12 +321,8 @@ extern "C" int gga_pfn_fwd(const float* voxels, const int32_t* num_points, const
     GGA_REQUIRE(voxels && num_points && coors && weight && gamma && beta && running_mean && running_var && out &&
                     argmax && saved && workspace,
                 "gga_pfn_fwd: null pointer argument");
-    if (workspace_bytes < gga_pfn_workspace_bytes(m)) {
-        gga_set_error("gga_pfn_fwd: workspace %zu B < required %zu B", workspace_bytes, gga_pfn_workspace_bytes(m));
-        return GGA_ERR_WORKSPACE;
-    }
-    const PfnGeom g = { prm->voxel_size[0], prm->voxel_size[1], prm->voxel_size[2],
-                        prm->offsets[0], prm->offsets[1], prm->offsets[2] };
+    GGA_REQUIRE_WORKSPACE("gga_pfn_fwd", workspace_bytes, gga_pfn_workspace_bytes(m));
+    const PfnGeom g = pfn_geom(prm);
     double* partials = (double*)workspace;
     float* scale_shift = (float*)((char*)workspace + gga_pfn_workspace_bytes(m) - 2 * PFN_C * sizeof(float));
     const int nb = pfn_blocks(m);
@@ -362,10 +331,9 @@ extern "C" int gga_pfn_fwd(const float* voxels, const int32_t* num_points, const
                            (const int4*)coors, m, num_valid, P, g, partials);
         GGA_CHECK_LAUNCH("pfn_moments_kernel");
     }
-    hipLaunchKernelGGL(pfn_stats_kernel, dim3(1), dim3(64), 0, stream, partials, nb, m, num_valid, P, weight,
-                       gamma, beta, prm->eps, prm->momentum, prm->training, running_mean, running_var, saved,
-                       scale_shift);
-    GGA_CHECK_LAUNCH("pfn_stats_kernel");
+    if (int rc = pfn_launch_stats(partials, nb, num_valid, m, P, 1, weight, gamma, beta, prm, running_mean, running_var, saved,
+                                  scale_shift, stream))
+        return rc;
     hipLaunchKernelGGL(pfn_apply_kernel, dim3(pfn_wave_blocks(m)), dim3(256), 0, stream, (const float4*)voxels,
                        num_points, (const int4*)coors, m, num_valid, P, g, weight, scale_shift, out, argmax);
     GGA_CHECK_LAUNCH("pfn_apply_kernel");
@@ -383,18 +351,11 @@ extern "C" int gga_pfn_bwd(const float* voxels, const int32_t* num_points, const
                     grad_weight && grad_gamma && grad_beta && workspace,
                 "gga_pfn_bwd: null pointer argument");
     GGA_REQUIRE(prm->training, "gga_pfn_bwd: backward is defined for training-mode batch statistics");
-    if (workspace_bytes < gga_pfn_workspace_bytes(m)) {
-        gga_set_error("gga_pfn_bwd: workspace %zu B < required %zu B", workspace_bytes, gga_pfn_workspace_bytes(m));
-        return GGA_ERR_WORKSPACE;
-    }
-    const PfnGeom g = { prm->voxel_size[0], prm->voxel_size[1], prm->voxel_size[2],
-                        prm->offsets[0], prm->offsets[1], prm->offsets[2] };
+    GGA_REQUIRE_WORKSPACE("gga_pfn_bwd", workspace_bytes, gga_pfn_workspace_bytes(m));
     const int nb = pfn_wave_blocks(m);
     hipLaunchKernelGGL(pfn_bwd_kernel, dim3(nb), dim3(256), 0, stream, (const float4*)voxels, num_points,
-                       (const int4*)coors, m, num_valid, P, g, weight, saved, out, argmax, grad_out, (float*)workspace);
+                       (const int4*)coors, m, num_valid, P, pfn_geom(prm), weight, saved, out, argmax, grad_out,
+                       (float*)workspace);
     GGA_CHECK_LAUNCH("pfn_bwd_kernel");
-    hipLaunchKernelGGL(pfn_bwd_final_kernel, dim3(1), dim3(PFN_BW * PFN_C), 0, stream, (const float*)workspace, nb,
-                       weight, gamma, saved, grad_weight, grad_gamma, grad_beta);
-    GGA_CHECK_LAUNCH("pfn_bwd_final_kernel");
-    return GGA_OK;
+    return pfn_launch_bwd_final((const float*)workspace, nb, weight, gamma, saved, grad_weight, grad_gamma, grad_beta, stream);
 }

@@ -160,7 +160,7 @@ class _FusedDynamicPFN(torch.autograd.Function):
         out = torch.zeros((rows, 64), dtype=torch.float32, device=dev)
         argmax = torch.zeros((rows, 64), dtype=torch.int32, device=dev)
         mean = torch.empty((rows, 4), dtype=torch.float32, device=dev)
-        saved = torch.empty(239, dtype=torch.float64, device=dev)
+        saved = torch.empty(_lib.PFN_SAVED_DOUBLES, dtype=torch.float64, device=dev)
         ws = F._workspace('dvpfn', L.gga_dynamic_pfn_workspace_bytes(n), dev)
         w = weight.contiguous()
         check(L.gga_dynamic_pfn_fwd(F._p(points), F._p(coors), n, F._p(vmap.order), F._p(vmap.point2voxel), F._p(vmap.voxel_start),

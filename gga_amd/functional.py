@@ -304,7 +304,7 @@ class _FusedPFN(torch.autograd.Function):
         L = _lib.lib()
         out = torch.empty((m, 64), dtype=torch.float32, device=dev)
         argmax = torch.empty((m, 64), dtype=torch.uint8, device=dev)
-        saved = torch.empty(239, dtype=torch.float64, device=dev)
+        saved = torch.empty(_lib.PFN_SAVED_DOUBLES, dtype=torch.float64, device=dev)
         ws = _workspace('pfn', L.gga_pfn_workspace_bytes(m), dev)
         w = weight.contiguous()
         check(L.gga_pfn_fwd(_p(voxels), _p(num_points), _p(coors), m, _p(num_valid), P, C.byref(prm), _p(w), _p(gamma),

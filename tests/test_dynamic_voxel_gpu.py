@@ -453,6 +453,31 @@ def test_dynamic_pillar_encoder_with_dropped_points_and_eval_mode(golden, traini
     np.testing.assert_allclose(bn.running_var.cpu().numpy(), r['running'][0][1].numpy(), rtol=1e-5)
 
 
+def test_dynamic_pfn_with_no_kept_point():
+    """Every point out of range (kept count 0), training mode: the statistics kernel that the hard and the dynamic fused fronts
+    share takes its `no rows, no running-statistics update` branch, which only the dynamic front asks for."""
+    coors = _coors_case('all_out').to(DEV)
+    n = coors.shape[0]
+    vm = DV.map_of(coors, GRID, batch=2)
+    assert vm.host_counts() == (0, 0)
+    g = torch.Generator().manual_seed(5)
+    pts = torch.randn(n, 4, generator=g).to(DEV)
+    w = torch.randn(64, 10, generator=g).to(DEV).requires_grad_(True)
+    gamma = (torch.rand(64, generator=g) + 0.5).to(DEV).requires_grad_(True)
+    beta = torch.randn(64, generator=g).to(DEV).requires_grad_(True)
+    rm, rv = torch.randn(64, generator=g).to(DEV), (torch.rand(64, generator=g) + 0.5).to(DEV)
+    rm0, rv0 = rm.clone(), rv.clone()
+    prm = F.pfn_params(VS, [VS[a] / 2 + RNG[a] for a in range(3)], 1e-3, 0.01, True)
+    out = DV.fused_pfn(pts, coors, vm, w, gamma, beta, rm, rv, prm)              # capacity form: n rows
+    assert out.shape == (n, 64) and torch.equal(out, torch.zeros_like(out))
+    assert torch.equal(rm, rm0) and torch.equal(rv, rv0)                         # bit for bit
+    saved = out.grad_fn.saved_tensors[7]
+    assert saved.numel() == _lib.PFN_SAVED_DOUBLES and float(saved[_lib.PFN_SAVED_DOUBLES - 1]) == 1.0
+    out.backward(torch.randn(n, 64, generator=g).to(DEV))
+    for p in (w, gamma, beta):
+        assert bool(torch.isfinite(p.grad).all()) and torch.equal(p.grad, torch.zeros_like(p.grad))
+
+
 # ---- detector -------------------------------------------------------------------------------------------------------------
 DV_CFGS = {'pp': ('gga_kitti_dv_pointpillars_config.py', 'gga_kitti_pointpillars_config.py', synthetic.RANGE_PP),
            'second': ('gga_kitti_dv_config.py', 'gga_kitti_config.py', synthetic.RANGE_SECOND)}

@@ -374,6 +374,87 @@ def test_fused_pfn_full_size():
         assert err < 1e-3, err
 
 
+PFN_SMALL_SEED = 5
+
+
+def _pfn_capacity_case(seed=PFN_SMALL_SEED, dtype=torch.float32):
+    """-> (PillarFeatureNet on the CPU, voxels [37, 5, 4], num_points [37], coors [37, 4], grad_out [37, 64]): 29 pillars of the
+    PointPillars grid with 1 .. 5 points (padding points zero, as the voxelizer leaves them), then 8 capacity rows of garbage."""
+    from gga_amd.voxel_encoders import PillarFeatureNet
+    m, valid, P = 37, 29, 5
+    vs, rng = (0.16, 0.16, 4), synthetic.RANGE_PP
+    g = torch.Generator().manual_seed(seed)
+    n = torch.randint(1, P + 1, (m,), generator=g, dtype=torch.int32)
+    n[0], n[1:4] = 1, P                                         # one single point, three full pillars (no padding row in the max)
+    c = torch.stack([torch.randint(0, 2, (m,), generator=g), torch.zeros(m, dtype=torch.int64),
+                     torch.randint(0, 496, (m,), generator=g), torch.randint(0, 432, (m,), generator=g)], 1).int()
+    lo = torch.tensor([rng[0], rng[1], rng[2]]) + torch.tensor(vs) * c[:, [3, 2, 1]].float()
+    v = torch.rand(m, P, 4, generator=g)
+    v[:, :, :3] = lo[:, None, :] + v[:, :, :3] * torch.tensor(vs)
+    v = v * (torch.arange(P)[None, :] < n[:, None])[:, :, None]
+    v[valid:] = torch.randn(m - valid, P, 4, generator=g) * 1e6
+    n[valid:] = torch.tensor([77, -3, 0, 5, 1 << 30, -(1 << 31), 6, 2], dtype=torch.int32)
+    c[valid:] = torch.randint(-(1 << 20), 1 << 20, (m - valid, 4), generator=g).int()
+    torch.manual_seed(seed)
+    pfn = PillarFeatureNet(in_channels=4, feat_channels=(64,), voxel_size=vs, point_cloud_range=rng)
+    with torch.no_grad():
+        bn = pfn.pfn_layers[0].norm
+        bn.weight.copy_(torch.rand(64, generator=g) + 0.5)
+        bn.bias.copy_(torch.rand(64, generator=g) * 0.6 - 0.3)
+    gy = torch.randn(m, 64, generator=g)
+    return pfn.to(dtype).train(), v.to(dtype), n, c, gy.to(dtype)
+
+
+def test_fused_pfn_capacity_rows_small():
+    """gga_pfn_fwd / gga_pfn_bwd called directly on a capacity-sized buffer: m = 37 rows of which the device-side count marks 29
+    valid, P = 5. The reference is the eager path on the [:29] slices, which normalises over 29 * 5 rows as the kernels do.
+    Tolerances are the suite's existing ones (forward rtol = atol = 1e-4 as the other eager comparisons, running statistics as
+    the golden test, parameter gradients relative 1e-3 as test_fused_pfn_full_size). The seed was checked on the CPU: with
+    PFN_SMALL_SEED, forward_eager in float32 stays within a quarter of each of these bounds of forward_eager in float64 on the
+    same inputs (training forward 0.125 of its bound, running mean 0.04, running variance 0.004, the three gradients 0.007,
+    the eval forward 0.02; the seeds 0 .. 5 give 0.125 .. 0.29 at worst, and seed 0 is the one above a quarter)."""
+    from gga_amd import _lib
+    ref, v, n, c, gy = _pfn_capacity_case()
+    ref = ref.to(DEV)
+    v, n, c, gy = v.to(DEV), n.to(DEV), c.to(DEV), gy.to(DEV)
+    m, valid, P = v.shape[0], 29, v.shape[1]
+    assert int(n[0]) == 1 and int((n[:valid] == P).sum()) >= 3 and int(n[:valid].min()) >= 1 and int(n[:valid].max()) <= P
+    num_valid = torch.tensor([valid], dtype=torch.int32, device=DEV)
+    l0 = ref.pfn_layers[0]
+    w, gamma, beta = (p.detach().clone().requires_grad_(True) for p in (l0.linear.weight, l0.norm.weight, l0.norm.bias))
+    rm, rv = l0.norm.running_mean.clone(), l0.norm.running_var.clone()
+    prm = lambda training: F.pfn_params((ref.vx, ref.vy, ref.vz), (ref.x_offset, ref.y_offset, ref.z_offset), l0.norm.eps,
+                                        l0.norm.momentum, training)
+
+    def check_forward(y, yr):
+        np.testing.assert_allclose(y[:valid].detach().cpu().numpy(), yr.detach().cpu().numpy(), rtol=1e-4, atol=1e-4)
+        assert y.shape == (m, 64) and torch.equal(y[valid:], torch.zeros_like(y[valid:]))
+        argmax = y.grad_fn.saved_tensors[6]
+        assert argmax.dtype == torch.uint8 and bool((argmax[valid:] == 255).all())
+        assert bool((argmax[1:4] < P).all())                    # full pillars: a point, never the padding row
+
+    y = F.fused_pfn(v, n, c, w, gamma, beta, rm, rv, prm(True), num_valid=num_valid)
+    yr = ref.forward_eager(v[:valid], n[:valid], c[:valid])
+    check_forward(y, yr)
+    saved = y.grad_fn.saved_tensors[7]
+    assert saved.numel() == _lib.PFN_SAVED_DOUBLES and float(saved[_lib.PFN_SAVED_DOUBLES - 1]) == valid * P == 145
+    np.testing.assert_allclose(rm.cpu().numpy(), l0.norm.running_mean.cpu().numpy(), rtol=1e-4, atol=1e-7)
+    np.testing.assert_allclose(rv.cpu().numpy(), l0.norm.running_var.cpu().numpy(), rtol=1e-5)
+    y.backward(gy)
+    yr.backward(gy[:valid])
+    for got, want in ((w.grad, l0.linear.weight.grad), (gamma.grad, l0.norm.weight.grad), (beta.grad, l0.norm.bias.grad)):
+        err = float((got - want).abs().max() / want.abs().max())
+        assert err < 1e-3, err
+    # eval mode: the running statistics, which the call leaves untouched
+    ref.eval()
+    rm0, rv0 = rm.clone(), rv.clone()
+    with torch.no_grad():
+        l0.norm.running_mean.copy_(rm), l0.norm.running_var.copy_(rv)
+    check_forward(F.fused_pfn(v, n, c, w, gamma, beta, rm, rv, prm(False), num_valid=num_valid),
+                  ref.forward_eager(v[:valid], n[:valid], c[:valid]))
+    assert torch.equal(rm, rm0) and torch.equal(rv, rv0)
+
+
 @pytest.mark.parametrize('shape,cl', [((70001, 16), False), ((3000, 128), False), ((4, 64, 62, 54), True),
                                        ((2, 256, 31, 27), True), ((3, 8, 5, 7), True)])
 @pytest.mark.parametrize('relu,res', [(True, False), (False, False), (True, True)])
