@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgga_hip.so')
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 _lib = None
 
@@ -151,10 +151,8 @@ SIGNATURES = {
     'gga_timing_collect': (i32, [i32, vp, i32]),
     'gga_voxel_grid_size': (None, [C.POINTER(VoxelParams), C.POINTER(C.c_int32 * 3)]),
     'gga_hard_voxelize_workspace_bytes': (sz, [i32, i64]),
-    'gga_hard_voxelize_batch': (i32, [vp, i32, C.POINTER(C.c_int64), i32, C.POINTER(VoxelParams),
+    'gga_hard_voxelize_batch': (i32, [vp, i32, C.POINTER(C.c_int64), vp, i32, C.POINTER(VoxelParams),
                                        vp, vp, vp, vp, vp, sz, vp]),
-    'gga_hard_voxelize_prepared': (i32, [vp, i32, C.POINTER(C.c_int64), vp, i32, C.POINTER(VoxelParams),
-                                          vp, vp, vp, vp, vp, sz, vp]),
     'gga_dynamic_voxelize': (i32, [vp, i32, C.POINTER(C.c_int64), vp, i32, C.POINTER(VoxelParams), vp, vp, vp]),
     'gga_dynamic_voxel_map_workspace_bytes': (sz, [i64]),
     'gga_dynamic_voxel_map': (i32, [vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -1,7 +1,7 @@
 // Dynamic voxelization for gfx950: every point keeps its cell, nothing is capped (mmcv.ops.Voxelization with
 // max_num_points = -1 / max_voxels = -1, and mmcv.ops.DynamicScatter).
 //
-//   coors     one thread per point: cell (b, z, y, x) through gga_voxel_cell (the hard voxelizer's function) and a u32 key
+//   coors     one thread per point: cell (b, z, y, x) through gga_point_cell (the hard voxelizer's function) and a u32 key
 //             ((b Z + z) Y + y) X + x; a point outside the grid, past its frame's device-side count or with a non-finite
 //             coordinate gets (b, -1, -1, -1) and the key 0xFFFFFFFF ("dropped").
 //   map       stable LSD radix sort of (key, point index) over the significant key bits (rocPRIM), segment heads, an
@@ -21,59 +21,30 @@
 // All writes are plain vector stores. Every buffer is sized by the caller from the point count before launch; every index
 // read from `order` / `point2voxel` / arg-max is bounded by construction (order is a permutation of [0, n), voxel ids are
 // < the device-side voxel count <= n) and the voxel count is clamped to the rows the caller allocated.
-#include "gga_common.h"
+#include "gga_index.h"
 #include "pfn_common.h"
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #define DV_DROPPED 0xFFFFFFFFu
 #define DV_CHUNK 256           // split rule: longest segment one lane group walks alone = positions per tile
 #define DV_NO_POINT 0x7FFFFFFF
 
-struct DvFrames {
-    int32_t off[GGA_MAX_BATCH + 1];
-    const int32_t* cnt;     // optional device-side point counts (frames stored at capacity offsets)
-};
-
-struct DvGeom {
-    float vs[3];
-    float lo[3];
-    int32_t grid[3];  // x, y, z
-};
-
-__global__ __launch_bounds__(256) void dv_coors_kernel(const float* __restrict__ points, int ndim, DvFrames fo, DvGeom g,
+__global__ __launch_bounds__(256) void dv_coors_kernel(const float* __restrict__ points, int ndim, GgaFrames fo, GgaVoxGeom g,
                                                       int4* __restrict__ coors, uint32_t* __restrict__ keys) {
     const int b = blockIdx.y;
-    const int cap = fo.off[b + 1] - fo.off[b];
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= cap) return;
-    int n = cap;
-    if (fo.cnt) {
-        const int c = fo.cnt[b];
-        n = c < 0 ? 0 : (c < cap ? c : cap);
-    }
+    if (i >= fo.off[b + 1] - fo.off[b]) return;          // every row of the frame's capacity is written
     const int64_t gi = (int64_t)fo.off[b] + i;
-    bool ok = i < n;
-    float cf[3] = {0.0f, 0.0f, 0.0f};
-    if (ok) {
-        const float* p = points + gi * ndim;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            cf[j] = gga_voxel_cell(p[j], g.lo[j], g.vs[j]);
-            ok = ok && (cf[j] >= 0.0f) && (cf[j] < (float)g.grid[j]);
-        }
-    }
-    if (!ok) {
+    int32_t c[3];                                           // x, y, z
+    if (i >= fo.n(b) || !gga_point_cell(points + gi * ndim, g, c)) {
         coors[gi] = make_int4(b, -1, -1, -1);
         keys[gi] = DV_DROPPED;
         return;
     }
-    const int cx = (int)cf[0], cy = (int)cf[1], cz = (int)cf[2];
-    coors[gi] = make_int4(b, cz, cy, cx);
-    keys[gi] = (((uint32_t)b * (uint32_t)g.grid[2] + (uint32_t)cz) * (uint32_t)g.grid[1] + (uint32_t)cy) * (uint32_t)g.grid[0] +
-               (uint32_t)cx;
+    coors[gi] = make_int4(b, c[2], c[1], c[0]);
+    keys[gi] = (((uint32_t)b * (uint32_t)g.grid[2] + (uint32_t)c[2]) * (uint32_t)g.grid[1] + (uint32_t)c[1]) * (uint32_t)g.grid[0] +
+               (uint32_t)c[0];
 }
 
 // keys of caller-supplied coordinates ([n, 3] (z, y, x) or [n, 4] (b, z, y, x)): any entry outside the grid / batch drops the row
@@ -128,14 +99,6 @@ __global__ __launch_bounds__(256) void dv_finalize_kernel(const uint32_t* __rest
     }
 }
 
-typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 4096> dv_sort_config;
-static size_t dv_sort_temp_bytes(int64_t n, int bits) {
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs<dv_sort_config>(nullptr, tb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                    rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (size_t)n, 0,
-                                                    (unsigned)bits, (hipStream_t)0);
-    return gga_align_up(tb, 256);
-}
 static size_t dv_scan_temp_bytes(int64_t n) {
     size_t tb = 0;
     (void)rocprim::inclusive_scan(nullptr, tb, (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, rocprim::plus<int32_t>(),
@@ -172,26 +135,12 @@ extern "C" int gga_dynamic_voxelize(const float* points, int ndim, const int64_t
     GGA_REQUIRE(points && offsets_host && prm && coors && keys, "gga_dynamic_voxelize: null pointer argument");
     GGA_REQUIRE(batch >= 1 && batch <= GGA_MAX_BATCH, "gga_dynamic_voxelize: batch %d not in [1, %d]", batch, GGA_MAX_BATCH);
     GGA_REQUIRE(ndim >= 3 && ndim <= 16, "gga_dynamic_voxelize: ndim %d not in [3, 16]", ndim);
-    const int64_t total = offsets_host[batch];
-    GGA_REQUIRE(offsets_host[0] == 0 && total >= 0 && total < (1ll << 30),
-                "gga_dynamic_voxelize: offsets must start at 0 and total points < 2^30");
-    DvFrames fo;
-    fo.cnt = counts_dev;
-    int max_n = 0;
-    for (int b = 0; b <= batch; ++b) {
-        fo.off[b] = (int32_t)offsets_host[b];
-        if (b > 0) {
-            GGA_REQUIRE(offsets_host[b] >= offsets_host[b - 1], "gga_dynamic_voxelize: offsets not monotone");
-            const int nb = (int)(offsets_host[b] - offsets_host[b - 1]);
-            max_n = nb > max_n ? nb : max_n;
-        }
-    }
-    DvGeom g;
-    for (int j = 0; j < 3; ++j) { g.vs[j] = prm->voxel_size[j]; g.lo[j] = prm->pc_range[j]; }
-    gga_voxel_grid_size(prm, g.grid);
+    GgaFrames fo;
+    int max_n;
+    if (int rc = gga_frames_from_host("gga_dynamic_voxelize", offsets_host, counts_dev, batch, &fo, &max_n)) return rc;
+    const GgaVoxGeom g = gga_vox_geom(prm);
     uint64_t cells;
-    const int rc = dv_cells("gga_dynamic_voxelize", batch, g.grid[0], g.grid[1], g.grid[2], &cells);
-    if (rc != GGA_OK) return rc;
+    if (int rc = dv_cells("gga_dynamic_voxelize", batch, g.grid[0], g.grid[1], g.grid[2], &cells)) return rc;
     if (max_n == 0) return GGA_OK;
     hipLaunchKernelGGL(dv_coors_kernel, dim3((max_n + 255) / 256, batch), dim3(256), 0, stream, points, ndim, fo, g,
                        reinterpret_cast<int4*>(coors), keys);
@@ -202,7 +151,7 @@ extern "C" int gga_dynamic_voxelize(const float* points, int ndim, const int64_t
 extern "C" size_t gga_dynamic_voxel_map_workspace_bytes(int64_t n_points) {
     if (n_points < 1) return 0;
     // sort temp | scan temp | keys (built from coors) | sorted keys | head flags | scanned flags
-    return dv_sort_temp_bytes(n_points, 32) + dv_scan_temp_bytes(n_points) + 4 * dv_rows_bytes(n_points);
+    return gga_argsort_temp_bytes<uint32_t>(n_points, 32) + dv_scan_temp_bytes(n_points) + 4 * dv_rows_bytes(n_points);
 }
 
 extern "C" int gga_dynamic_voxel_map(const uint32_t* keys, const int32_t* coors, int coor_cols, int64_t n_points, int batch,
@@ -232,7 +181,7 @@ extern "C" int gga_dynamic_voxel_map(const uint32_t* keys, const int32_t* coors,
     GGA_CHECK_HIP(hipMemsetAsync(voxel_coors, 0, (size_t)n_points * 4 * sizeof(int32_t), stream), "dynamic map memset(coors)");
     const int bits = dv_key_bits(cells);
     char* w = (char*)workspace;
-    void* sort_tmp = w;      w += dv_sort_temp_bytes(n_points, 32);
+    void* sort_tmp = w;      w += gga_argsort_temp_bytes<uint32_t>(n_points, 32);
     void* scan_tmp = w;      w += dv_scan_temp_bytes(n_points);
     uint32_t* own_keys = (uint32_t*)w; w += dv_rows_bytes(n_points);
     uint32_t* sk = (uint32_t*)w;       w += dv_rows_bytes(n_points);
@@ -245,17 +194,11 @@ extern "C" int gga_dynamic_voxel_map(const uint32_t* keys, const int32_t* coors,
         GGA_CHECK_LAUNCH("dv_keys_kernel");
         keys = own_keys;
     }
-    size_t tb = dv_sort_temp_bytes(n_points, bits);
-    hipError_t e = rocprim::radix_sort_pairs<dv_sort_config>(sort_tmp, tb, keys, sk, rocprim::counting_iterator<int32_t>(0), order,
-                                                             (size_t)n_points, 0, (unsigned)bits, stream);
-    if (e != hipSuccess) {
-        gga_set_error("gga_dynamic_voxel_map: rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-        return GGA_ERR_LAUNCH;
-    }
+    if (int rc = gga_argsort("gga_dynamic_voxel_map", sort_tmp, keys, sk, order, n_points, bits, stream)) return rc;
     hipLaunchKernelGGL(dv_heads_kernel, grid, dim3(256), 0, stream, sk, n_points, flags);
     GGA_CHECK_LAUNCH("dv_heads_kernel");
-    tb = dv_scan_temp_bytes(n_points);
-    e = rocprim::inclusive_scan(scan_tmp, tb, (const int32_t*)flags, incl, (size_t)n_points, rocprim::plus<int32_t>(), stream);
+    size_t tb = dv_scan_temp_bytes(n_points);
+    const hipError_t e = rocprim::inclusive_scan(scan_tmp, tb, (const int32_t*)flags, incl, (size_t)n_points, rocprim::plus<int32_t>(), stream);
     if (e != hipSuccess) {
         gga_set_error("gga_dynamic_voxel_map: rocprim::inclusive_scan: %s", hipGetErrorString(e));
         return GGA_ERR_LAUNCH;

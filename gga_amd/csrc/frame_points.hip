@@ -11,7 +11,7 @@
 //   frame_points_scatter_kernel  the rows inside `reduce_poly`, in input order, to `reduced` (a stable compaction).
 // Arithmetic: a float32 coordinate widens to float64 exactly, so the face test is points_in_polyhedra_kernel's to the bit:
 // s = ((x*n0 + y*n1) + z*n2) + d with every product rounded on its own (no fma), inside iff s < 0 for every face.
-#include "gga_common.h"
+#include "gga_index.h"
 
 #pragma clang fp contract(off)
 
@@ -101,20 +101,13 @@ __global__ __launch_bounds__(FP_THREADS) void frame_points_test_kernel(const flo
 // `chunk` consecutive entries.
 __global__ __launch_bounds__(FP_SCAN_THREADS) void frame_points_scan_kernel(int32_t* __restrict__ block_counts, int n_blocks,
                                                                            int32_t* __restrict__ n_reduced) {
-    __shared__ int wave_sum_lds[FP_SCAN_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int chunk = (n_blocks + FP_SCAN_THREADS - 1) / FP_SCAN_THREADS;
     const int b0 = min(n_blocks, tid * chunk), b1 = min(n_blocks, b0 + chunk);
     int own = 0;
     for (int b = b0; b < b1; ++b) own += block_counts[b];
-    int incl = own;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    if (lane == 63) wave_sum_lds[wave] = incl;
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int w = 0; w < FP_SCAN_THREADS / 64; ++w) { if (w < wave) base += wave_sum_lds[w]; total += wave_sum_lds[w]; }
-    int run = base + incl - own;
+    int total;
+    int run = gga_block_scan<FP_SCAN_THREADS>(own, total);
     for (int b = b0; b < b1; ++b) { const int c = block_counts[b]; block_counts[b] = run; run += c; }
     if (tid == 0) *n_reduced = total;
 }
@@ -124,16 +117,11 @@ __global__ __launch_bounds__(FP_THREADS) void frame_points_scatter_kernel(const 
                                                                          const uint32_t* __restrict__ member_word, int bit,
                                                                          const int32_t* __restrict__ block_offsets,
                                                                          float* __restrict__ reduced) {
-    __shared__ int wave_cnt[FP_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = blockIdx.x * FP_THREADS + tid;
+    const int i = blockIdx.x * FP_THREADS + threadIdx.x;
     const bool keep = i < n && ((member_word[i] >> bit) & 1u);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
+    int kept;
+    const int dst = block_offsets[blockIdx.x] + gga_block_scan_flag<FP_THREADS>(keep, kept);
     if (!keep) return;
-    int dst = block_offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) dst += wave_cnt[w];
     if (ROW4) {
         ((float4*)reduced)[dst] = ((const float4*)pts)[i];
     } else {

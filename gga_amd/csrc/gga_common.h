@@ -61,13 +61,6 @@ __host__ __device__ static inline size_t gga_align_up(size_t x, size_t a) { retu
 // frames per call of the batched point ops (per-frame offsets travel to the kernels by value)
 #define GGA_MAX_BATCH 128
 
-// Cell of a point along one axis: floor((p - lo) / vs) in f32 with a true division (voxel_generator.py:189). The hard and the
-// dynamic voxelizer both go through this one function, so they cannot disagree on a point's cell. NaN and +-inf come out as
-// NaN / +-inf and fail the callers' `0 <= cell < grid` test: such a point is out of range.
-__device__ __forceinline__ float gga_voxel_cell(float p, float lo, float vs) {
-    return floorf(__fdiv_rn(__fsub_rn(p, lo), vs));
-}
-
 // ---- wave / block reductions (wave = 64 lanes on CDNA) ----------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

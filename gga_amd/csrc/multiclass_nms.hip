@@ -19,11 +19,8 @@
 // survivors then resolve among themselves on a 64 x 64 bit mask as nms_scan_kernel does, and are appended to the kept list.
 // The overlap is rotated_iou_rot(kept, candidate) of rotated_iou.h for oriented and axis-aligned boxes alike (heading 0 for
 // the latter, as nms3d_normal calls the rotated routine): the earlier box first, the float operations of nms_mask_kernel.
-#include "gga_common.h"
+#include "gga_index.h"
 #include "rotated_iou.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #define MCN_THREADS 1024
 #define MCN_WAVES (MCN_THREADS / 64)
@@ -180,15 +177,6 @@ __global__ __launch_bounds__(256) void mcn_pack_kernel(const int32_t* __restrict
     }
 }
 
-typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 4096> mcn_sort_config;
-static size_t mcn_sort_temp_bytes(int64_t n_pairs) {
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs<mcn_sort_config>(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (size_t)n_pairs, 0,
-                                                     64u, (hipStream_t)0);
-    return gga_align_up(tb, 256);
-}
-
 static bool mcn_sizes_ok(int64_t n, int C, int n_scenes) {
     return n >= 0 && C >= 1 && C <= GGA_MULTICLASS_NMS_MAX_CLASSES && n_scenes >= 1 && n_scenes <= MCN_MAX_SCENES &&
            n * C < ((int64_t)1 << 31) && (int64_t)n_scenes * C < ((int64_t)1 << 31);
@@ -198,7 +186,7 @@ static bool mcn_sizes_ok(int64_t n, int C, int n_scenes) {
 extern "C" size_t gga_multiclass_nms3d_workspace_bytes(int64_t n, int n_classes, int n_scenes) {
     if (!mcn_sizes_ok(n, n_classes, n_scenes)) return 0;
     const size_t np = (size_t)n * n_classes, ns = (size_t)n_scenes * n_classes;
-    return (np ? mcn_sort_temp_bytes((int64_t)np) : 0) + 2 * gga_align_up(np * 8, 256) + 2 * gga_align_up(np * 4, 256) +
+    return (np ? gga_argsort_temp_bytes<uint64_t>((int64_t)np, 64) : 0) + 2 * gga_align_up(np * 8, 256) + 2 * gga_align_up(np * 4, 256) +
            gga_align_up(3 * ns * 4, 256);
 }
 
@@ -225,7 +213,7 @@ extern "C" int gga_multiclass_nms3d(const float* boxes, const float* scores, con
     const int64_t np = n * C;
     const int ns = n_scenes * C;
     unsigned char* w = static_cast<unsigned char*>(workspace);
-    const size_t tb_max = mcn_sort_temp_bytes(np);
+    const size_t tb_max = gga_argsort_temp_bytes<uint64_t>(np, 64);
     uint64_t* keys = reinterpret_cast<uint64_t*>(w + tb_max);
     uint64_t* keys_sorted = reinterpret_cast<uint64_t*>(w + tb_max + gga_align_up((size_t)np * 8, 256));
     int32_t* order = reinterpret_cast<int32_t*>(w + tb_max + 2 * gga_align_up((size_t)np * 8, 256));
@@ -239,14 +227,8 @@ extern "C" int gga_multiclass_nms3d(const float* boxes, const float* scores, con
     hipLaunchKernelGGL(mcn_key_kernel, dim3(pair_blocks), dim3(256), 0, stream, scores, scene, np, C, n_scenes, score_thr, sentinel,
                        keys);
     GGA_CHECK_LAUNCH("mcn_key_kernel");
-    size_t tb = tb_max;
-    const hipError_t e = rocprim::radix_sort_pairs<mcn_sort_config>(w, tb, (const uint64_t*)keys, keys_sorted,
-                                                                    rocprim::counting_iterator<int32_t>(0), order, (size_t)np, 0,
-                                                                    (unsigned)(MCN_SCENE_SHIFT + sbits + 1), stream);
-    if (e != hipSuccess) {
-        gga_set_error("gga_multiclass_nms3d: rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-        return GGA_ERR_LAUNCH;
-    }
+    if (int rc = gga_argsort("gga_multiclass_nms3d", w, (const uint64_t*)keys, keys_sorted, order, np, MCN_SCENE_SHIFT + sbits + 1, stream))
+        return rc;
     hipLaunchKernelGGL(mcn_segment_kernel, dim3(pair_blocks), dim3(256), 0, stream, keys_sorted, np, C, sentinel, seg_begin, seg_end);
     GGA_CHECK_LAUNCH("mcn_segment_kernel");
     hipLaunchKernelGGL(mcn_nms_kernel, dim3((unsigned)ns), dim3(MCN_THREADS), 0, stream, boxes, C, order, seg_begin, seg_end, iou_thr,

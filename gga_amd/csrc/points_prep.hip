@@ -11,8 +11,8 @@
 // points, its scene points]; rows are compacted in order (stable), so with seed 0 the output
 // equals the reference's row for row. Output rows of frame f start at its capacity offset
 // (pasted + scene rows before it); the kept count stays on the device for the voxelizer
-// (gga_hard_voxelize_prepared) - no host round trip.
-#include "gga_common.h"
+// (gga_hard_voxelize_batch's counts_dev) - no host round trip.
+#include "gga_index.h"
 
 #define PP_CHUNK 256
 
@@ -63,15 +63,9 @@ __global__ __launch_bounds__(PP_CHUNK) void pp_flag_kernel(const float* __restri
         keep = pp_keep(p, is_scene, centers + 2 * (int64_t)fr.ctr_off[f], fr.ctr_off[f + 1] - fr.ctr_off[f], min_distance, rng);
         flags[fr.cap_off[f] + i] = keep ? 1 : 0;
     }
-    __shared__ int wsum[PP_CHUNK / 64];
-    const int c = __popcll(__ballot(keep));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < PP_CHUNK / 64; ++w) t += wsum[w];
-        chunk_cnt[f * chunks_per_frame + blockIdx.x] = t;
-    }
+    int t;
+    gga_block_scan_flag<PP_CHUNK>(keep, t);
+    if (threadIdx.x == 0) chunk_cnt[f * chunks_per_frame + blockIdx.x] = t;
 }
 
 // pass 2: exclusive scan of a frame's chunk counts (one workgroup per frame), kept total -> counts[f]
@@ -79,25 +73,13 @@ __global__ __launch_bounds__(1024) void pp_scan_kernel(int32_t* __restrict__ chu
                                                       int32_t* __restrict__ counts) {
     const int f = blockIdx.x, tid = threadIdx.x;
     int32_t* c = chunk_cnt + (int64_t)f * chunks_per_frame;
-    __shared__ int part[1024];
-    __shared__ int carry;
-    if (tid == 0) carry = 0;
-    __syncthreads();
+    int carry = 0;                                    // every thread keeps the running total
     for (int base = 0; base < chunks_per_frame; base += 1024) {
         const int i = base + tid;
-        const int v = i < chunks_per_frame ? c[i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {          // Hillis-Steele inclusive scan
-            const int t = tid >= d ? part[tid - d] : 0;
-            __syncthreads();
-            part[tid] += t;
-            __syncthreads();
-        }
-        if (i < chunks_per_frame) c[i] = carry + part[tid] - v;
-        __syncthreads();
-        if (tid == 0) carry += part[1023];
-        __syncthreads();
+        int tot;
+        const int e = gga_block_scan<1024>(i < chunks_per_frame ? c[i] : 0, tot);
+        if (i < chunks_per_frame) c[i] = carry + e;
+        carry += tot;
     }
     if (tid == 0) counts[f] = carry;
 }
@@ -135,14 +117,9 @@ __global__ __launch_bounds__(PP_CHUNK) void pp_write_kernel(const float* __restr
     const int f = blockIdx.y, i = blockIdx.x * PP_CHUNK + threadIdx.x;
     const int n = fr.cap_off[f + 1] - fr.cap_off[f];
     const bool keep = i < n && flags[fr.cap_off[f] + i];
-    __shared__ int wsum[PP_CHUNK / 64];
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
+    int kept;
+    const int rank = chunk_base[f * chunks_per_frame + blockIdx.x] + gga_block_scan_flag<PP_CHUNK>(keep, kept);
     if (!keep) return;
-    int rank = chunk_base[f * chunks_per_frame + blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += wsum[w];
     const uint64_t seed = fr.seed[f];
     const uint32_t dst = seed ? pp_permute((uint32_t)rank, (uint32_t)counts[f], seed) : (uint32_t)rank;
     bool is_scene;

@@ -22,14 +22,10 @@
 //              chunk, accumulates X^T G in registers, one float atomicAdd per weight per chunk.
 #include <stdlib.h>
 
-#include "gga_common.h"
+#include "gga_index.h"
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#define SP_EMPTY 0xFFFFFFFFFFFFFFFFull
 
 struct SpDims { int B, D, H, W; };
 struct SpConvGeom { int kz, ky, kx, sz, sy, sx, pz, py, px; };
@@ -40,45 +36,26 @@ struct SpIndex {              // view into a caller-provided buffer
     uint32_t mask;
 };
 
-static inline uint64_t sp_cap(int64_t n) {
-    uint64_t c = 1024;
-    while (c < (uint64_t)(2 * n + 2)) c <<= 1;
-    return c;
-}
-
-__device__ __forceinline__ uint32_t sp_hash(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (uint32_t)k;
-}
 __device__ __forceinline__ unsigned long long sp_key(const SpDims d, int b, int z, int y, int x) {
     return (((unsigned long long)b * d.D + z) * d.H + y) * d.W + x;
 }
-__device__ __forceinline__ uint32_t sp_insert(const SpIndex ix, unsigned long long key) {
-    uint32_t h = sp_hash(key) & ix.mask;
-    while (true) {
-        const unsigned long long prev = atomicCAS(&ix.keys[h], SP_EMPTY, key);
-        if (prev == SP_EMPTY || prev == key) return h;
-        h = (h + 1) & ix.mask;
-    }
-}
 __device__ __forceinline__ int32_t sp_lookup(const SpIndex ix, unsigned long long key) {
-    uint32_t h = sp_hash(key) & ix.mask;
+    uint32_t h = gga_hash64(key) & ix.mask;
     while (true) {
         const unsigned long long k = ix.keys[h];
         if (k == key) return ix.vals[h];
-        if (k == SP_EMPTY) return -1;
+        if (k == GGA_HASH_EMPTY) return -1;
         h = (h + 1) & ix.mask;
     }
 }
 __device__ __forceinline__ uint32_t sp_find_slot(const SpIndex ix, unsigned long long key) {
-    uint32_t h = sp_hash(key) & ix.mask;
+    uint32_t h = gga_hash64(key) & ix.mask;
     while (ix.keys[h] != key) h = (h + 1) & ix.mask;
     return h;
 }
 
 static SpIndex sp_index_view(void* buf, int64_t n) {
-    const uint64_t cap = sp_cap(n);
+    const uint64_t cap = gga_hash_capacity(n);
     SpIndex ix;
     ix.keys = (unsigned long long*)buf;
     ix.vals = (int32_t*)((char*)buf + cap * 8);
@@ -86,7 +63,7 @@ static SpIndex sp_index_view(void* buf, int64_t n) {
     return ix;
 }
 
-extern "C" size_t gga_sparse_index_bytes(int64_t n) { return sp_cap(n) * 12; }
+extern "C" size_t gga_sparse_index_bytes(int64_t n) { return gga_hash_capacity(n) * 12; }
 
 // ------------------------------------------------------------------------------ index build
 __global__ __launch_bounds__(256) void sp_index_insert_kernel(const int4* __restrict__ coors, int64_t n, SpDims d,
@@ -97,7 +74,7 @@ __global__ __launch_bounds__(256) void sp_index_insert_kernel(const int4* __rest
     if ((unsigned)c.x >= (unsigned)d.B || (unsigned)c.y >= (unsigned)d.D || (unsigned)c.z >= (unsigned)d.H ||
         (unsigned)c.w >= (unsigned)d.W)
         return;
-    const uint32_t h = sp_insert(ix, sp_key(d, c.x, c.y, c.z, c.w));
+    const uint32_t h = gga_hash_insert(ix.keys, ix.mask, sp_key(d, c.x, c.y, c.z, c.w));
     atomicMax(&ix.vals[h], (int32_t)i);      // duplicate coordinates: the highest row wins
 }
 
@@ -111,7 +88,7 @@ extern "C" int gga_sparse_build_index(const int32_t* coors, int64_t n, int B, in
                       gga_sparse_index_bytes(n));
         return GGA_ERR_WORKSPACE;
     }
-    const uint64_t cap = sp_cap(n);
+    const uint64_t cap = gga_hash_capacity(n);
     SpIndex ix = sp_index_view(index, n);
     GGA_CHECK_HIP(hipMemsetAsync(ix.keys, 0xFF, cap * 12, stream), "sparse index memset");   // keys empty, the values behind them -1: one fill
     if (n > 0) {
@@ -146,7 +123,7 @@ __global__ __launch_bounds__(256) void sp_sites_propose_kernel(const int4* __res
     const int4 c = in_coors[i];
     int oz, oy, ox;
     if (!sp_out_coord(g, od, c.y, c.z, c.w, k, oz, oy, ox)) return;
-    const uint32_t h = sp_insert(ox_, sp_key(od, c.x, oz, oy, ox));
+    const uint32_t h = gga_hash_insert(ox_.keys, ox_.mask, sp_key(od, c.x, oz, oy, ox));
     atomicMin(&first[h], (unsigned long long)t);
 }
 
@@ -170,40 +147,22 @@ __global__ __launch_bounds__(256) void sp_sites_count_kernel(const int4* __restr
 // three-step exclusive scan of cnt[n] (block sums -> scan of sums -> apply), 1024 per block
 __global__ __launch_bounds__(1024) void sp_scan_block_kernel(const int32_t* __restrict__ cnt, int64_t n,
                                                             int32_t* __restrict__ excl, int32_t* __restrict__ bsum) {
-    __shared__ int wsum[16];
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-    const int v = i < n ? cnt[i] : 0;
-    int s = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o, 64); if ((threadIdx.x & 63) >= o) s += t; }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-    if (i < n) excl[i] = base + s - v;
-    if (threadIdx.x == 1023) bsum[blockIdx.x] = base + s;
+    int total;
+    const int e = gga_block_scan<1024>(i < n ? cnt[i] : 0, total);
+    if (i < n) excl[i] = e;
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(1024) void sp_scan_sums_kernel(int32_t* __restrict__ bsum, int nblk,
                                                            int32_t* __restrict__ total) {
-    // single block, serial over chunks of 1024 (nblk is n/1024: a few hundred)
-    __shared__ int wsum[16];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    // single block, serial over chunks of 1024 (nblk is n/1024: a few hundred); every thread keeps the running total
+    int carry = 0;
     for (int c0 = 0; c0 < nblk; c0 += 1024) {
         const int i = c0 + threadIdx.x;
-        const int v = i < nblk ? bsum[i] : 0;
-        int s = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o, 64); if ((threadIdx.x & 63) >= o) s += t; }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = s;
-        __syncthreads();
-        int base = carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-        if (i < nblk) bsum[i] = base + s - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = base + s;
-        __syncthreads();
+        int chunk;
+        const int e = gga_block_scan<1024>(i < nblk ? bsum[i] : 0, chunk);
+        if (i < nblk) bsum[i] = carry + e;
+        carry += chunk;
     }
     if (threadIdx.x == 0) *total = carry;
 }
@@ -232,7 +191,7 @@ __global__ __launch_bounds__(256) void sp_sites_assign_kernel(const int4* __rest
 
 extern "C" size_t gga_sparse_out_sites_workspace_bytes(int64_t n_in, int kvol) {
     const int64_t cap = n_in * kvol;       // upper bound on distinct output cells
-    return sp_cap(cap) * 8 + gga_align_up((size_t)n_in * 4, 256) * 2 + gga_align_up((size_t)((n_in + 1023) / 1024 + 1) * 4, 256);
+    return gga_hash_capacity(cap) * 8 + gga_align_up((size_t)n_in * 4, 256) * 2 + gga_align_up((size_t)((n_in + 1023) / 1024 + 1) * 4, 256);
 }
 extern "C" size_t gga_sparse_out_index_bytes(int64_t n_in, int kvol) { return gga_sparse_index_bytes(n_in * kvol); }
 
@@ -258,7 +217,7 @@ extern "C" int gga_sparse_conv_out_sites(const int32_t* in_coors, int64_t n_in, 
         return GGA_ERR_WORKSPACE;
     }
     const int64_t ncand = n_in * kvol;
-    const uint64_t cap = sp_cap(ncand);
+    const uint64_t cap = gga_hash_capacity(ncand);
     SpIndex ox_ = sp_index_view(out_index, ncand);
     char* w = (char*)workspace;
     unsigned long long* first = (unsigned long long*)w; w += cap * 8;
@@ -367,19 +326,10 @@ extern "C" int gga_sparse_rowmask(const int32_t* map, int64_t n_rows, int kvol, 
 // radix_sort_pairs, a counting iterator as the values: 8-10 launches) instead of the framework's stable sort of int32 keys,
 // which is a merge sort on this stack - 22 launches of merge-path kernels per rule book, 1.3-1.8 ms of the sparse config's step.
 // A stable sort has one answer, so the order is the same.
-// (rocPRIM's default hands anything up to 2^20 items to its merge sort - the 42 launches per rule book this entry point exists
-// to avoid; with the limit at 4096 a level goes through Onesweep: one histogram and one pass per 8 mask bits)
-typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 4096> sp_order_config;
-static size_t sp_order_temp_bytes(int64_t n_rows, int bits) {
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs<sp_order_config>(nullptr, tb, (const int32_t*)nullptr, (int32_t*)nullptr, rocprim::counting_iterator<int32_t>(0),
-                                    (int32_t*)nullptr, (size_t)n_rows, 0, (unsigned)bits, (hipStream_t)0);
-    return (tb + 255) / 256 * 256;
-}
-
+// (gga_argsort of gga_index.h; the keys are the masks as int32, see below)
 extern "C" size_t gga_sparse_mask_order_workspace_bytes(int64_t n_rows) {
     if (n_rows < 1) return 0;
-    return sp_order_temp_bytes(n_rows, 32) + ((size_t)n_rows * sizeof(int32_t) + 255) / 256 * 256;      // temporaries + the sorted keys
+    return gga_argsort_temp_bytes<int32_t>(n_rows, 32) + gga_align_up((size_t)n_rows * sizeof(int32_t), 256);      // temporaries + the sorted keys
 }
 
 extern "C" int gga_sparse_mask_order(const uint32_t* mask, int64_t n_rows, int kvol, int32_t* order, void* workspace,
@@ -391,16 +341,9 @@ extern "C" int gga_sparse_mask_order(const uint32_t* mask, int64_t n_rows, int k
         return GGA_ERR_WORKSPACE;
     }
     // (kvol == 32: bit 31 is the sign of the int32 the mask is kept in; the keys are compared as signed, like the sort this replaces)
-    size_t tb = sp_order_temp_bytes(n_rows, kvol);
-    int32_t* keys_out = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(workspace) + sp_order_temp_bytes(n_rows, 32));
-    const hipError_t e = rocprim::radix_sort_pairs<sp_order_config>(workspace, tb, reinterpret_cast<const int32_t*>(mask), keys_out,
-                                                   rocprim::counting_iterator<int32_t>(0), order, (size_t)n_rows, 0, (unsigned)kvol,
-                                                   (hipStream_t)stream);
-    if (e != hipSuccess) {
-        gga_set_error("gga_sparse_mask_order: rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-        return GGA_ERR_LAUNCH;
-    }
-    return GGA_OK;
+    int32_t* keys_out = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(workspace) + gga_argsort_temp_bytes<int32_t>(n_rows, 32));
+    return gga_argsort("gga_sparse_mask_order", workspace, reinterpret_cast<const int32_t*>(mask), keys_out, order, n_rows, kvol,
+                       (hipStream_t)stream);
 }
 
 // Rows of a level along a Z-order curve per sample (the halo form's tiles, gather_gemm.py: morton_order): key = sample, then the
@@ -424,19 +367,11 @@ __global__ __launch_bounds__(256) void sp_morton_key_kernel(const int4* __restri
     keys[i] = ((uint64_t)(uint32_t)c.x << (3 * cbits)) | (sp_spread3((uint32_t)c.y) << 2) | (sp_spread3((uint32_t)c.z) << 1) |
               sp_spread3((uint32_t)c.w);
 }
-typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 4096> sp_morton_config;
-static size_t sp_morton_temp_bytes(int64_t n, int bits) {
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs<sp_morton_config>(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                      rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (size_t)n, 0,
-                                                      (unsigned)bits, (hipStream_t)0);
-    return (tb + 255) / 256 * 256;
-}
-static inline size_t sp_morton_keys_bytes(int64_t n) { return ((size_t)n * 8 + 255) / 256 * 256; }
+static inline size_t sp_morton_keys_bytes(int64_t n) { return gga_align_up((size_t)n * 8, 256); }
 
 extern "C" size_t gga_sparse_morton_order_workspace_bytes(int64_t n_rows) {
     if (n_rows < 1) return 0;
-    return sp_morton_temp_bytes(n_rows, 64) + 2 * sp_morton_keys_bytes(n_rows);
+    return gga_argsort_temp_bytes<uint64_t>(n_rows, 64) + 2 * sp_morton_keys_bytes(n_rows);
 }
 
 extern "C" int gga_sparse_morton_order(const int32_t* coors, int64_t n_rows, int batch_size, int max_extent, int32_t* order,
@@ -452,19 +387,11 @@ extern "C" int gga_sparse_morton_order(const int32_t* coors, int64_t n_rows, int
     while ((1 << cbits) < max_extent) ++cbits;                          // bits of a coordinate: 3 * cbits interleaved bits
     while ((1 << bbits) < batch_size) ++bbits;
     const int bits = 3 * cbits + bbits;
-    unsigned char* w = static_cast<unsigned char*>(workspace) + sp_morton_temp_bytes(n_rows, 64);
+    unsigned char* w = static_cast<unsigned char*>(workspace) + gga_argsort_temp_bytes<uint64_t>(n_rows, 64);
     uint64_t* keys = reinterpret_cast<uint64_t*>(w);
     uint64_t* keys_out = reinterpret_cast<uint64_t*>(w + sp_morton_keys_bytes(n_rows));
     hipLaunchKernelGGL(sp_morton_key_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, stream, (const int4*)coors,
                        n_rows, cbits, keys);
     GGA_CHECK_LAUNCH("sp_morton_key_kernel");
-    size_t tb = sp_morton_temp_bytes(n_rows, bits);
-    const hipError_t e = rocprim::radix_sort_pairs<sp_morton_config>(workspace, tb, (const uint64_t*)keys, keys_out,
-                                                                     rocprim::counting_iterator<int32_t>(0), order,
-                                                                     (size_t)n_rows, 0, (unsigned)bits, stream);
-    if (e != hipSuccess) {
-        gga_set_error("gga_sparse_morton_order: rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-        return GGA_ERR_LAUNCH;
-    }
-    return GGA_OK;
+    return gga_argsort("gga_sparse_morton_order", workspace, (const uint64_t*)keys, keys_out, order, n_rows, bits, stream);
 }

@@ -18,26 +18,11 @@
 //               point also writes coors / num_points.
 //
 // No dense (D,H,W) index grid (360 MB for the KITTI config) as the CPU reference uses.
-#include "gga_common.h"
+#include "gga_index.h"
 
-#define VOX_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 #define VOX_ROUND_HI 0x7FFFFFFFu
 
-struct FrameOffsets {
-    int32_t off[GGA_MAX_BATCH + 1];
-    const int32_t* cnt;     // optional device-side point counts (frames stored at capacity offsets)
-    __device__ __forceinline__ int n(int b) const {
-        const int cap = off[b + 1] - off[b];
-        if (!cnt) return cap;
-        const int c = cnt[b];
-        return c < 0 ? 0 : (c < cap ? c : cap);
-    }
-};
-
-struct VoxGeom {
-    float vs[3];
-    float lo[3];
-    int32_t grid[3];  // x, y, z
+struct VoxGeom : GgaVoxGeom {
     int32_t max_points, max_voxels;
 };
 
@@ -49,58 +34,31 @@ struct VoxWorkspace {
     int32_t* slot;             // [total]
     int32_t* rank;             // [total]
     int32_t* act0;             // [total]
-    int32_t* act1;             // [total]
     uint32_t cap_mask;
 };
 
-static inline uint64_t vox_cap(int64_t total_points) {
-    uint64_t cap = 1024;
-    while (cap < (uint64_t)(2 * total_points + 2)) cap <<= 1;
-    return cap;
-}
-
-__device__ __forceinline__ uint32_t vox_hash(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (uint32_t)k;
-}
-
 __global__ __launch_bounds__(256) void vox_insert_kernel(const float* __restrict__ points, int ndim,
-                                                        FrameOffsets fo, VoxGeom g, VoxWorkspace ws) {
+                                                        GgaFrames fo, VoxGeom g, VoxWorkspace ws) {
     const int b = blockIdx.y;
     const int n = fo.n(b);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t gi = (int64_t)fo.off[b] + i;
-    const float* p = points + gi * ndim;
     int32_t c[3];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        // floor((p - lo) / vs) in f32, true division (voxel_generator.py:189)
-        float cf = gga_voxel_cell(p[j], g.lo[j], g.vs[j]);
-        ok = ok && (cf >= 0.0f) && (cf < (float)g.grid[j]);
-        c[j] = (int32_t)cf;
-    }
-    if (!ok) {
+    if (!gga_point_cell(points + gi * ndim, g, c)) {
         ws.slot[gi] = -1;
         ws.rank[gi] = -2;
         return;
     }
     unsigned long long key =
         (((unsigned long long)b * g.grid[2] + c[2]) * g.grid[1] + c[1]) * g.grid[0] + c[0];
-    uint32_t h = vox_hash(key) & ws.cap_mask;
-    while (true) {
-        unsigned long long prev = atomicCAS(&ws.keys[h], VOX_EMPTY_KEY, key);
-        if (prev == VOX_EMPTY_KEY || prev == key) break;
-        h = (h + 1) & ws.cap_mask;
-    }
+    const uint32_t h = gga_hash_insert(ws.keys, ws.cap_mask, key);
     atomicMin(&ws.cur[h], ((unsigned long long)VOX_ROUND_HI << 32) | (uint32_t)i);
     atomicAdd(&ws.count[h], 1);
     ws.slot[gi] = (int32_t)h;
 }
 
-__global__ __launch_bounds__(256) void vox_flag_kernel(FrameOffsets fo, VoxWorkspace ws) {
+__global__ __launch_bounds__(256) void vox_flag_kernel(GgaFrames fo, VoxWorkspace ws) {
     const int b = blockIdx.y;
     const int n = fo.n(b);
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -123,26 +81,18 @@ __global__ __launch_bounds__(256) void vox_flag_kernel(FrameOffsets fo, VoxWorks
 // `cur[h]` is free after K2 and is reused as (region start, fill counter).
 struct BlkOffsets { int32_t off[GGA_MAX_BATCH + 1]; };      // first 1024-point block of every frame (kernel argument, by value)
 
-__global__ __launch_bounds__(1024) void vox_count_kernel(FrameOffsets fo, VoxWorkspace ws, BlkOffsets bo,
+__global__ __launch_bounds__(1024) void vox_count_kernel(GgaFrames fo, VoxWorkspace ws, BlkOffsets bo,
                                                         int32_t* __restrict__ blk_cnt) {
     const int32_t* blk_off = bo.off;
     const int b = blockIdx.y;
     if ((int)blockIdx.x >= blk_off[b + 1] - blk_off[b]) return;
     const int n = fo.n(b), i = blockIdx.x * 1024 + threadIdx.x;
-    const bool flag = (i < n) && (ws.rank[fo.off[b] + i] == 0);
-    __shared__ int wave_tot[16];
-    const unsigned long long bal = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) t += wave_tot[w];
-        blk_cnt[blk_off[b] + blockIdx.x] = t;
-    }
+    int t;
+    gga_block_scan_flag<1024>((i < n) && (ws.rank[fo.off[b] + i] == 0), t);
+    if (threadIdx.x == 0) blk_cnt[blk_off[b] + blockIdx.x] = t;
 }
 
-__global__ __launch_bounds__(1024) void vox_assign_kernel(FrameOffsets fo, VoxGeom g, VoxWorkspace ws,
+__global__ __launch_bounds__(1024) void vox_assign_kernel(GgaFrames fo, VoxGeom g, VoxWorkspace ws,
                                                          BlkOffsets bo,
                                                          const int32_t* __restrict__ blk_cnt, int32_t* __restrict__ cursor,
                                                          int32_t* __restrict__ voxel_num) {
@@ -150,30 +100,20 @@ __global__ __launch_bounds__(1024) void vox_assign_kernel(FrameOffsets fo, VoxGe
     const int b = blockIdx.y;
     const int nblk = blk_off[b + 1] - blk_off[b];
     if ((int)blockIdx.x >= nblk) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int base = fo.off[b], n = fo.n(b);
-    __shared__ int wave_tot[16];
     __shared__ int running_s;
-    if (wave == 0) {                                   // sum of the earlier blocks' counts
+    if (tid < 64) {                                    // sum of the earlier blocks' counts
         int s = 0;
-        for (int x = lane; x < (int)blockIdx.x; x += 64) s += blk_cnt[blk_off[b] + x];
+        for (int x = tid; x < (int)blockIdx.x; x += 64) s += blk_cnt[blk_off[b] + x];
         s = wave_sum(s);
-        if (lane == 0) running_s = s;
+        if (tid == 0) running_s = s;
     }
     const int i = blockIdx.x * 1024 + tid;
     const bool flag = (i < n) && (ws.rank[base + i] == 0);
-    const unsigned long long bal = __ballot(flag);
-    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int wpre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int t = wave_tot[w];
-        wpre += (w < wave) ? t : 0;
-        tot += t;
-    }
-    const int v = running_s + wpre + pre;
+    int tot;
+    int v = gga_block_scan_flag<1024>(flag, tot);
+    v += running_s;                                    // (written before the scan's barriers)
     if (flag) {
         const int32_t h = ws.slot[base + i];
         if (v < g.max_voxels) {
@@ -192,7 +132,7 @@ __global__ __launch_bounds__(1024) void vox_assign_kernel(FrameOffsets fo, VoxGe
     }
 }
 
-__global__ __launch_bounds__(256) void vox_fill_kernel(FrameOffsets fo, VoxWorkspace ws) {
+__global__ __launch_bounds__(256) void vox_fill_kernel(GgaFrames fo, VoxWorkspace ws) {
     const int b = blockIdx.y;
     const int n = fo.n(b), i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -204,7 +144,7 @@ __global__ __launch_bounds__(256) void vox_fill_kernel(FrameOffsets fo, VoxWorks
     ws.act0[fo.off[b] + pos] = i;
 }
 
-__global__ __launch_bounds__(256) void vox_rank_kernel(FrameOffsets fo, VoxGeom g, VoxWorkspace ws) {
+__global__ __launch_bounds__(256) void vox_rank_kernel(GgaFrames fo, VoxGeom g, VoxWorkspace ws) {
     const int b = blockIdx.y;
     const int n = fo.n(b), i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -220,7 +160,7 @@ __global__ __launch_bounds__(256) void vox_rank_kernel(FrameOffsets fo, VoxGeom 
 }
 
 __global__ __launch_bounds__(256) void vox_write_kernel(const float* __restrict__ points, int ndim,
-                                                       FrameOffsets fo, int batch, VoxGeom g, VoxWorkspace ws,
+                                                       GgaFrames fo, int batch, VoxGeom g, VoxWorkspace ws,
                                                        const int32_t* __restrict__ voxel_num_in,
                                                        int32_t* __restrict__ voxel_total,
                                                        float* __restrict__ voxels, int32_t* __restrict__ coors,
@@ -269,39 +209,17 @@ extern "C" void gga_voxel_grid_size(const gga_voxel_params* prm, int32_t grid_xy
 }
 
 extern "C" size_t gga_hard_voxelize_workspace_bytes(int batch, int64_t total_points) {
-    const uint64_t cap = vox_cap(total_points);
+    const uint64_t cap = gga_hash_capacity(total_points);
     size_t bytes = cap * (8 + 8 + 4 + 4);
-    bytes += gga_align_up((size_t)total_points * 4, 256) * 4;
+    bytes += gga_align_up((size_t)total_points * 4, 256) * 3;
     bytes += gga_align_up(((size_t)total_points / 1024 + 3 * (size_t)batch + 16) * 4, 256);     // block offsets / counts, cursors
     return bytes + 1024;
 }
 
-static int hard_voxelize_impl(const float* points, int ndim, const int64_t* offsets_host, const int32_t* counts_dev,
-                              int batch, const gga_voxel_params* prm, float* voxels, int32_t* coors,
-                              int32_t* num_points, int32_t* voxel_num, void* workspace, size_t workspace_bytes,
-                              void* stream_);
-
-extern "C" int gga_hard_voxelize_batch(const float* points, int ndim, const int64_t* offsets_host, int batch,
-                                       const gga_voxel_params* prm, float* voxels, int32_t* coors,
-                                       int32_t* num_points, int32_t* voxel_num, void* workspace,
-                                       size_t workspace_bytes, void* stream_) {
-    return hard_voxelize_impl(points, ndim, offsets_host, nullptr, batch, prm, voxels, coors, num_points, voxel_num,
-                              workspace, workspace_bytes, stream_);
-}
-
-extern "C" int gga_hard_voxelize_prepared(const float* points, int ndim, const int64_t* capacity_offsets_host,
-                                          const int32_t* counts_dev, int batch, const gga_voxel_params* prm,
-                                          float* voxels, int32_t* coors, int32_t* num_points, int32_t* voxel_num,
-                                          void* workspace, size_t workspace_bytes, void* stream_) {
-    GGA_REQUIRE(counts_dev, "gga_hard_voxelize_prepared: null pointer argument");
-    return hard_voxelize_impl(points, ndim, capacity_offsets_host, counts_dev, batch, prm, voxels, coors, num_points,
-                              voxel_num, workspace, workspace_bytes, stream_);
-}
-
-static int hard_voxelize_impl(const float* points, int ndim, const int64_t* offsets_host, const int32_t* counts_dev,
-                              int batch, const gga_voxel_params* prm, float* voxels, int32_t* coors,
-                              int32_t* num_points, int32_t* voxel_num, void* workspace, size_t workspace_bytes,
-                              void* stream_) {
+extern "C" int gga_hard_voxelize_batch(const float* points, int ndim, const int64_t* offsets_host, const int32_t* counts_dev,
+                                       int batch, const gga_voxel_params* prm, float* voxels, int32_t* coors,
+                                       int32_t* num_points, int32_t* voxel_num, void* workspace, size_t workspace_bytes,
+                                       void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GGA_REQUIRE(points && offsets_host && prm && voxels && coors && num_points && voxel_num && workspace,
                 "gga_hard_voxelize_batch: null pointer argument");
@@ -309,33 +227,15 @@ static int hard_voxelize_impl(const float* points, int ndim, const int64_t* offs
                 GGA_MAX_BATCH);
     GGA_REQUIRE(ndim >= 3 && ndim <= 16, "gga_hard_voxelize_batch: ndim %d not in [3, 16]", ndim);
     GGA_REQUIRE(prm->max_points >= 1 && prm->max_voxels >= 1, "gga_hard_voxelize_batch: max_points/max_voxels < 1");
+    GgaFrames fo;
+    int max_n;
+    if (int rc = gga_frames_from_host("gga_hard_voxelize_batch", offsets_host, counts_dev, batch, &fo, &max_n)) return rc;
     const int64_t total = offsets_host[batch];
-    GGA_REQUIRE(offsets_host[0] == 0 && total >= 0 && total < (1ll << 30),
-                "gga_hard_voxelize_batch: offsets must start at 0 and total points < 2^30");
-    FrameOffsets fo;
-    fo.cnt = counts_dev;
-    int max_n = 0;
-    for (int b = 0; b <= batch; ++b) {
-        fo.off[b] = (int32_t)offsets_host[b];
-        if (b > 0) {
-            GGA_REQUIRE(offsets_host[b] >= offsets_host[b - 1], "gga_hard_voxelize_batch: offsets not monotone");
-            const int nb = (int)(offsets_host[b] - offsets_host[b - 1]);
-            max_n = nb > max_n ? nb : max_n;
-        }
-    }
-    if (gga_hard_voxelize_workspace_bytes(batch, total) > workspace_bytes) {
-        gga_set_error("gga_hard_voxelize_batch: workspace %zu B < required %zu B", workspace_bytes,
-                      gga_hard_voxelize_workspace_bytes(batch, total));
-        return GGA_ERR_WORKSPACE;
-    }
-    VoxGeom g;
-    for (int j = 0; j < 3; ++j) { g.vs[j] = prm->voxel_size[j]; g.lo[j] = prm->pc_range[j]; }
-    gga_voxel_grid_size(prm, g.grid);
+    GGA_REQUIRE_WORKSPACE("gga_hard_voxelize_batch", workspace_bytes, gga_hard_voxelize_workspace_bytes(batch, total));
+    const VoxGeom g = { gga_vox_geom(prm), prm->max_points, prm->max_voxels };
     GGA_REQUIRE(g.grid[0] > 0 && g.grid[1] > 0 && g.grid[2] > 0, "gga_hard_voxelize_batch: empty grid");
-    g.max_points = prm->max_points;
-    g.max_voxels = prm->max_voxels;
 
-    const uint64_t cap = vox_cap(total);
+    const uint64_t cap = gga_hash_capacity(total);
     VoxWorkspace ws;
     char* w = (char*)workspace;
     ws.cur = (unsigned long long*)w;  w += cap * 8;
@@ -346,7 +246,6 @@ static int hard_voxelize_impl(const float* points, int ndim, const int64_t* offs
     ws.slot = (int32_t*)w; w += per;
     ws.rank = (int32_t*)w; w += per;
     ws.act0 = (int32_t*)w; w += per;
-    ws.act1 = (int32_t*)w; w += per;
     ws.cap_mask = (uint32_t)(cap - 1);
     // small tables: per-frame block offsets [batch + 1] (host -> kernel argument copy), block counts, cursors [batch]
     int32_t* small = (int32_t*)w;

@@ -101,6 +101,29 @@ def voxel_grid_size(prm):
 
 
 @torch.no_grad()
+def _hard_voxelize(points, offsets, counts, voxel_size, point_cloud_range, max_points, max_voxels, sync):
+    """``gga_hard_voxelize_batch`` on frames concatenated in ``points`` at the int64 row ``offsets``; ``counts``: None, or the
+    device-side point counts of frames stored at capacity offsets."""
+    B, ndim, dev = len(offsets) - 1, points.shape[1], points.device
+    prm = voxel_params(voxel_size, point_cloud_range, max_points, max_voxels)
+    cap = B * int(max_voxels)
+    voxels = torch.empty((cap, int(max_points), ndim), dtype=torch.float32, device=dev)
+    coors = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    num_points = torch.empty((cap,), dtype=torch.int32, device=dev)
+    voxel_num = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _workspace('vox', L.gga_hard_voxelize_workspace_bytes(B, int(offsets[-1])), dev)
+    check(L.gga_hard_voxelize_batch(_p(points), ndim, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _p(counts), B,
+                                    C.byref(prm), _p(voxels), _p(coors), _p(num_points), _p(voxel_num),
+                                    _p(ws), ws.numel(), _stream()), 'gga_hard_voxelize_batch')
+    if sync:
+        m = int(voxel_num[-1].item())
+        return voxels[:m], num_points[:m], coors[:m], voxel_num
+    coors.num_valid = voxel_num[B:]           # device count travels with the coordinates (see num_valid_of)
+    return voxels, num_points, coors, voxel_num
+
+
+@torch.no_grad()
 def hard_voxelize_batch(points, voxel_size, point_cloud_range, max_points, max_voxels, sync=True):
     """Batched hard voxelization (mvx_two_stage_gga.py:211-236 in one call).
 
@@ -111,32 +134,12 @@ def hard_voxelize_batch(points, voxel_size, point_cloud_range, max_points, max_v
     ``B*max_voxels`` (rows >= M zero) and ``voxel_num[-1]`` carries M on the device.
     """
     _need_cuda(*points)
-    B = len(points)
-    ndim = points[0].shape[1]
-    dev = points[0].device
-    offs = np.zeros(B + 1, np.int64)
+    offs = np.zeros(len(points) + 1, np.int64)
     offs[1:] = np.cumsum([p.shape[0] for p in points])
-    cat = points[0].contiguous() if B == 1 else torch.cat(points, 0)
+    cat = points[0].contiguous() if len(points) == 1 else torch.cat(points, 0)
     if cat.dtype != torch.float32:
         cat = cat.float()
-    total = int(offs[-1])
-    prm = voxel_params(voxel_size, point_cloud_range, max_points, max_voxels)
-    cap = B * int(max_voxels)
-    voxels = torch.empty((cap, int(max_points), ndim), dtype=torch.float32, device=dev)
-    coors = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-    num_points = torch.empty((cap,), dtype=torch.int32, device=dev)
-    voxel_num = torch.empty((B + 1,), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    wsb = L.gga_hard_voxelize_workspace_bytes(B, total)
-    ws = _workspace('vox', wsb, dev)
-    check(L.gga_hard_voxelize_batch(_p(cat), ndim, offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
-                                    C.byref(prm), _p(voxels), _p(coors), _p(num_points), _p(voxel_num),
-                                    _p(ws), ws.numel(), _stream()), 'gga_hard_voxelize_batch')
-    if sync:
-        m = int(voxel_num[-1].item())
-        return voxels[:m], num_points[:m], coors[:m], voxel_num
-    coors.num_valid = voxel_num[B:]           # device count travels with the coordinates (see num_valid_of)
-    return voxels, num_points, coors, voxel_num
+    return _hard_voxelize(cat, offs, None, voxel_size, point_cloud_range, max_points, max_voxels, sync)
 
 
 def num_valid_of(coors):
@@ -257,25 +260,9 @@ def points_prepare_batch(scene, sampled, centers, min_distance, point_cloud_rang
 
 def hard_voxelize_prepared(prep, voxel_size, point_cloud_range, max_points, max_voxels, sync=True):
     """``hard_voxelize_batch`` on a ``PreparedPoints`` (frames at capacity offsets, counts on the device)."""
-    _need_cuda(prep.points)
-    B, ndim, dev = len(prep), prep.points.shape[1], prep.points.device
-    prm = voxel_params(voxel_size, point_cloud_range, max_points, max_voxels)
-    cap = B * int(max_voxels)
-    voxels = torch.empty((cap, int(max_points), ndim), dtype=torch.float32, device=dev)
-    coors = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-    num_points = torch.empty((cap,), dtype=torch.int32, device=dev)
-    voxel_num = torch.empty((B + 1,), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = _workspace('vox', L.gga_hard_voxelize_workspace_bytes(B, int(prep.capacity_offsets[-1])), dev)
-    offs = np.ascontiguousarray(prep.capacity_offsets, np.int64)
-    check(L.gga_hard_voxelize_prepared(_p(prep.points), ndim, offs.ctypes.data_as(C.POINTER(C.c_int64)), _p(prep.counts), B,
-                                       C.byref(prm), _p(voxels), _p(coors), _p(num_points), _p(voxel_num), _p(ws),
-                                       ws.numel(), _stream()), 'gga_hard_voxelize_prepared')
-    if sync:
-        m = int(voxel_num[-1].item())
-        return voxels[:m], num_points[:m], coors[:m], voxel_num
-    coors.num_valid = voxel_num[B:]
-    return voxels, num_points, coors, voxel_num
+    _need_cuda(prep.points, prep.counts)
+    return _hard_voxelize(prep.points, np.ascontiguousarray(prep.capacity_offsets, np.int64), prep.counts, voxel_size,
+                          point_cloud_range, max_points, max_voxels, sync)
 
 
 @torch.no_grad()

@@ -86,6 +86,9 @@ size_t gga_hard_voxelize_workspace_bytes(int batch, int64_t total_points);
 /*
  * points         [total_points, ndim] f32, frames concatenated
  * offsets_host   [batch + 1] i64 row offsets of each frame in `points`
+ * counts_dev     null, or [batch] i32 on the device: frame b's points are the first min(counts_dev[b], capacity) rows of
+ *                its range (frames at capacity offsets with their real counts on the device, the output of
+ *                gga_points_prepare_batch): no host synchronisation
  * voxels         [batch * max_voxels, max_points, ndim] f32  (zero-filled here)
  * coors          [batch * max_voxels, 4] i32  (b, z, y, x)
  * num_points     [batch * max_voxels] i32
@@ -93,18 +96,10 @@ size_t gga_hard_voxelize_workspace_bytes(int batch, int64_t total_points);
  * Frames are compacted: frame b occupies rows [sum_{b'<b} M_b', +M_b); rows >= M
  * are left zero.
  */
-int gga_hard_voxelize_batch(const float* points, int ndim, const int64_t* offsets_host, int batch,
-                            const gga_voxel_params* prm, float* voxels, int32_t* coors,
+int gga_hard_voxelize_batch(const float* points, int ndim, const int64_t* offsets_host, const int32_t* counts_dev,
+                            int batch, const gga_voxel_params* prm, float* voxels, int32_t* coors,
                             int32_t* num_points, int32_t* voxel_num, void* workspace,
                             size_t workspace_bytes, void* stream);
-
-/* Same, for frames that sit at capacity offsets with their real point counts on the device
- * (the output of gga_points_prepare_batch): frame b's points are rows
- * [capacity_offsets_host[b], +min(counts_dev[b], capacity)). No host synchronisation. */
-int gga_hard_voxelize_prepared(const float* points, int ndim, const int64_t* capacity_offsets_host,
-                               const int32_t* counts_dev, int batch, const gga_voxel_params* prm,
-                               float* voxels, int32_t* coors, int32_t* num_points, int32_t* voxel_num,
-                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* a0. Point-level tail of the train data pipeline,    */

@@ -122,3 +122,12 @@ def test_product_never_imports_oracle():
             if f.endswith(('.py', '.hip', '.cc', '.h')):
                 txt = open(os.path.join(root, f)).read()
                 assert 'import oracle' not in txt and 'from oracle' not in txt and 'gga_oracle' not in txt, f
+
+
+def test_hard_voxelize_workspace_did_not_grow():
+    # (batch, total points) -> bytes before the unused fourth per-point array left the workspace: one 256 B-aligned int32 per point less
+    before = {(1, 0): 25856, (1, 1): 26880, (1, 65537): 7342592, (2, 40000): 3787008, (6, 87002): 7685632, (16, 320000): 30288384}
+    L = _lib.lib()
+    for (batch, total), old in before.items():
+        new = L.gga_hard_voxelize_workspace_bytes(batch, total)
+        assert new == old - (total * 4 + 255) // 256 * 256 <= old, (batch, total, new, old)

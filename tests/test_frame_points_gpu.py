@@ -141,3 +141,17 @@ def test_raw_entry_unused_bits_and_rows_behind_the_last(boxes):
     rows = reduced.cpu().numpy()
     assert rows[:k].tobytes() == pts[want[:, 0]].tobytes() and (rows[k:] == -5.0).all()
     assert LG.frame_point_tests(pts, surf, 0)[3].shape == (k, stride)
+
+
+@pytest.mark.parametrize('n', [262144, 262145, 262401])
+def test_scan_thread_owns_more_than_one_block_count(n, boxes):
+    """frame_points_scan_kernel has 1024 threads: 262 144 points are 1024 workgroup counts (one per thread), 262 145 are 1025 and
+    262 401 are 1026 (two per thread, the last threads none). Both row forms of the scatter."""
+    surf = rbbox_surfaces(boxes[[0, 5, P_MAX - 1]])
+    normal, d = LG.surface_equ_3d(surf[:, :, :3, :])
+    for stride in (4, 5):
+        pts = _points(n, stride, seed=n)
+        want = face_test(pts, normal, d)
+        got = LG.frame_point_tests(pts, surf, 0)
+        assert 1000 < got[4] < n
+        _check(pts, surf, 0, got, want)

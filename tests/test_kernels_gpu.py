@@ -1533,3 +1533,35 @@ def test_weight_bank_operands_equal_the_per_call_packing(planes):
         assert bank.generation == 2
     finally:
         WB.BANK = old_bank
+
+
+@pytest.mark.parametrize('n', [65536 + 700, 65 * 1024 + 700])
+def test_voxelize_block_prefix_beyond_one_wave_and_counts_path(n):
+    """One frame of just over 65 536 points, i.e. more than 64 blocks of 1024: 65 blocks (the last one sums 64 earlier block
+    counts, a full wave) and 66 blocks (the last one sums 65 - the second step of vox_assign_kernel's wave-0 prefix loop).
+    max_voxels is a few below the number of occupied voxels, so the cap binds inside the last block. Then the same frame
+    through the counts path: stored at a larger capacity with its count on the device, and at its exact capacity with a
+    count above it (the clamp)."""
+    vs, rng, mp = [0.16, 0.16, 4], synthetic.RANGE_PP, 5
+    g = np.random.default_rng(n)
+    pts = np.concatenate([g.uniform(np.array(rng[:3]) - 1, np.array(rng[3:]) + 1, (n, 3)), g.uniform(0, 1, (n, 1))], 1).astype(np.float32)
+    _, oc_all, _ = O.hard_voxelize(pts, vs, rng, mp, 1 << 20)
+    mv = len(oc_all) - 7
+    head = (n - 1) // 1024 * 1024                               # points before the last block
+    assert len(O.hard_voxelize(pts[:head], vs, rng, mp, 1 << 20)[1]) < mv       # voxels kept and voxels dropped open in the last block
+    ov, oc, on = O.hard_voxelize(pts, vs, rng, mp, mv)
+    assert len(oc) == mv
+    v, k, c, vn = _vox_gpu([pts], vs, rng, mp, mv)
+    assert vn.tolist() == [mv, mv]
+    assert np.array_equal(c[:, 1:], oc) and (c[:, 0] == 0).all() and np.array_equal(k, on) and np.array_equal(v, ov)
+    # counts path, two frames: [pts + 1000 rows that are not the frame's] with count n, [pts] with count n + 12345
+    dev_pts = torch.from_numpy(pts).to(DEV)
+    junk = torch.from_numpy(pts[:1000] + np.float32(0.5)).to(DEV)
+    prep = F.PreparedPoints(torch.cat([dev_pts, junk, dev_pts]), np.array([0, n + 1000, 2 * n + 1000], np.int64),
+                            torch.tensor([n, n + 12345], dtype=torch.int32, device=DEV))
+    a = F.hard_voxelize_prepared(prep, vs, rng, mp, mv)
+    b = F.hard_voxelize_batch([dev_pts, dev_pts], vs, rng, mp, mv)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)
+    assert a[3].cpu().tolist() == [mv, mv, 2 * mv]
+    assert np.array_equal(a[0][mv:].cpu().numpy(), ov) and np.array_equal(a[2][mv:, 1:].cpu().numpy(), oc) and (a[2][mv:, 0] == 1).all()

@@ -211,3 +211,30 @@ def test_device_point_tail_boundaries_and_voxelizer_handover():
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     assert int(a[3][-1]) > 1000
+
+
+@pytest.mark.gpu
+def test_device_point_tail_scan_carries_across_rounds():
+    """262 145 virtual rows = 1025 chunks of 256: pp_scan_kernel (1024 chunk counts per round) needs a second round, so its
+    carry is live - rows and count bit for bit against the C oracle; then the same frame followed by an empty one."""
+    from gga_amd import functional as F
+    rng, g = MG.PIPELINE_RANGE, np.random.default_rng(262145)
+    margin = np.array([2, 2, 0.25], np.float32)
+    lo, hi = np.array(rng[:3], np.float32) - margin, np.array(rng[3:], np.float32) + margin
+    n_samp = 145
+    n_scene = 1024 * 256 + 1 - n_samp
+    scene = np.concatenate([g.uniform(lo, hi, (n_scene, 3)), g.uniform(0, 1, (n_scene, 1))], 1).astype(np.float32)
+    scene[-1, :3] = [40.0, 30.0, -1.0]                           # the one row of chunk 1024: in range, far from the centres
+    samp = np.concatenate([g.uniform(lo, hi, (n_samp, 3)), g.uniform(0, 1, (n_samp, 1))], 1).astype(np.float32)
+    ctr = np.array([[20.0, 5.0], [50.0, -20.0], [8.0, -3.0]])
+    want = O.points_prepare(scene, samp, ctr, 5.0, rng)
+    assert 0.5 * n_scene < len(want) < n_scene and np.array_equal(want[-1], scene[-1])
+    none4 = torch.zeros((0, 4))
+    prep = F.points_prepare_batch([torch.from_numpy(scene)], [torch.from_numpy(samp)], [ctr], 5.0, rng, [0], 'cuda:0')
+    assert prep.counts.cpu().tolist() == [len(want)]
+    assert np.array_equal(prep.to_list()[0].cpu().numpy(), want)
+    prep = F.points_prepare_batch([torch.from_numpy(scene), none4], [torch.from_numpy(samp), none4], [ctr, np.zeros((0, 2))], 5.0,
+                                  rng, [0, 0], 'cuda:0')
+    assert prep.counts.cpu().tolist() == [len(want), 0]
+    got = prep.to_list()
+    assert np.array_equal(got[0].cpu().numpy(), want) and got[1].shape == (0, 4)

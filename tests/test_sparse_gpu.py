@@ -588,3 +588,30 @@ def test_morton_order_entry_point_equals_the_tensor_expression(B, shape, n):
     got = morton_order(coors, B, max(shape))
     want = morton_order(coors)                                   # no extent: the tensor expression
     assert got.dtype == torch.int32 and torch.equal(got.long(), want)
+
+
+def test_out_sites_scan_of_block_sums_takes_a_second_round():
+    """1 050 624 input sites are 1026 blocks of 1024: sp_scan_sums_kernel (1024 block sums per round) makes a second round with a
+    live carry. Kernel (1, 1, 1) - the smallest volume, so the output index stays at 48 MiB - with stride 2: a site proposes
+    one output, (z, y, x) / 2, iff its coordinates are all even."""
+    from gga_amd.sparse import _Level
+    shape, n = (41, 1600, 1408), 1024 * 1024 + 2048
+    D, H, W = shape
+    g = torch.Generator().manual_seed(n)
+    flat = torch.unique(torch.randint(0, D * H * W, (n + n // 8,), generator=g))
+    assert len(flat) >= n
+    flat = flat[torch.randperm(len(flat), generator=g)[:n]]
+    coors = torch.stack([torch.zeros_like(flat), flat // (H * W), (flat // W) % H, flat % W], 1).int()
+    even = (coors[:, 1:] % 2 == 0).all(1)
+    want = torch.cat([coors[even, :1], coors[even, 1:] // 2], 1)
+    assert even[-2048:].any() and 100_000 < len(want) < n // 4
+    out, nbr, nbr_t = _Level(coors.to(DEV), shape, 1).strided((1, 1, 1), (2, 2, 2), (0, 0, 0))
+    assert out.shape == (21, 800, 704) and out.n == len(want)
+    got = out.coors.cpu()
+    assert torch.equal(torch.unique(got, dim=0), torch.unique(want, dim=0)) and len(torch.unique(got, dim=0)) == len(got)
+    assert torch.equal(got, want)                                 # owners are numbered in input order
+    # the rule book round-trips: the input under an output is the site that proposed it, and back
+    fwd, back = nbr.nbr.cpu()[0].long(), nbr_t.nbr.cpu()[0].long()
+    assert fwd.shape == (len(want),) and back.shape == (n,)
+    assert torch.equal(fwd, torch.nonzero(even)[:, 0]) and torch.equal(coors[fwd][:, 1:], 2 * got[:, 1:])
+    assert (back[~even] == -1).all() and torch.equal(fwd[back[even]], torch.nonzero(even)[:, 0])
